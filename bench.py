@@ -6,8 +6,10 @@ path (event detection -> normalisation -> match -> FM path forest -> seed cluste
 of reads that is already resident in HBM.  `--gpus N` runs as N ranks (started by the driver's torch.distributed.run, or by this script);
 reads shard across ranks (index replicated per GPU, no data-path collective), per-GPU work fixed => weak scaling.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
-  roofline      k_map: algorithmic bytes per launch / HIP-event launch time against the 8 TB/s HBM peak
+Rank 0 prints ONE JSON line.  A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+contract fields with `config` and `roofline`; `--dump-outputs DIR` also writes the hits of the last timed step (dump_hits).
+`--full` adds everything else:
+  roofline      k_map: algorithmic bytes per launch / HIP-event launch time against the 8 TB/s HBM peak (plain runs too)
   cpu_baseline  the reference's own object code (oracle/_ref) on this box's host cores: thread-count sweep, best N,
                 mean / median ms per read, the as-shipped MapPool hand-shake ("B2"), PAF mismatches against the GPU
   verify        sha256 of the hits of every timed step (all equal), reads checked against the CPU reference
@@ -368,9 +370,32 @@ def issue_roofline(a, workload, launch_ms, clock_hz):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_hits(out_dir, hits):
+    """--dump-outputs: the hits of the last timed step -- what a caller of the mapping path receives -- one float64 array per
+    result field (`DIR/<field>.npy`; map_ms, a wall-clock measurement, and the padding left out).  Past 64 MB a fixed, seeded
+    sample of the reads is written, and `read_index.npy` names them."""
+    from uncalled_amd import capi
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    fields = [f for f in capi.RESULT_FIELDS if f != "pad_"]
+    n = hits.shape[0]
+    cap = DUMP_LIMIT_BYTES // (8 * (len(fields) + 1))
+    if n > cap:
+        pick = np.sort(np.random.default_rng(2024).choice(n, size=cap, replace=False))
+        hits = hits[pick]
+        np.save(out_dir / "read_index.npy", pick.astype(np.float64))
+    for f in fields:
+        np.save(out_dir / f"{f}.npy", hits[f].astype(np.float64))
+    log(f"outputs of the last timed step ({hits.shape[0]} of {n} reads, {len(fields)} fields) -> {out_dir}")
+
+
 def run_workload(a, workload, n_reads, steps, warmup, rank, world, local_rank, dist, barrier, cache, lib, dev_name, extras, cpu_budget,
-                 warmup_reads=None):
-    """index (built once, cached) -> reads synthesised in HBM -> warm-up + timed steps -> result dict"""
+                 warmup_reads=None, full=True, dump_dir=None):
+    """index (built once, cached) -> reads synthesised in HBM -> warm-up + timed steps -> result dict.
+    full=False (a plain bench run): no step digests, no extra passes, no CPU leg -- only what the headline figure needs."""
     import torch
     from tools.simulate_reads import CAL_DIGITISATION, CAL_OFFSET, CAL_RANGE
     from tools.simulate_reads_torch import simulate_reads_torch
@@ -441,7 +466,8 @@ def run_workload(a, workload, n_reads, steps, warmup, rank, world, local_rank, d
             e, m = mapper.last_timing()
             ms_ev.append(e)
             ms_map.append(m)
-            kept.append(hits)
+            if full:
+                kept.append(hits)
     else:
         ts = time.perf_counter()
         begin(pair[0])
@@ -457,11 +483,14 @@ def run_workload(a, workload, n_reads, steps, warmup, rank, world, local_rank, d
             ms_map.append(m)
             if hasattr(mapper.L, "unc_mapper_last_window"):
                 windows.append(pair[k % 2].last_window())
-            kept.append(hits)
+            if full:
+                kept.append(hits)
     sync()
     barrier()
     dt = time.perf_counter() - t0
-    # self-verification, outside the timed region: every step must have produced the same bytes
+    if dump_dir and rank == 0:
+        dump_hits(dump_dir, hits)
+    # self-verification (--full), outside the timed region: every step must have produced the same bytes
     digests = [capi.hits_digest(h) for h in kept]      # (every result field; map_ms is a wall-clock measurement)
     del kept
     per_rank = None
@@ -475,7 +504,7 @@ def run_workload(a, workload, n_reads, steps, warmup, rank, world, local_rank, d
         per_rank = {"min": 1e3 * ts_[0] / steps, "median": 1e3 * ts_[len(ts_) // 2] / steps, "max": 1e3 * ts_[-1] / steps,
                     "unit": "ms per step, each rank's own timed region"}
         dt = ts_[-1]
-    assert len(set(digests)) == 1, f"{workload}: hits differ between timed steps: {digests}"
+    assert not full or len(set(digests)) == 1, f"{workload}: hits differ between timed steps: {digests}"
 
     wave_busy = mapper.last_wave_busy()
     remap_n, remap_ms = mapper.last_remap()
@@ -584,14 +613,15 @@ def run_workload(a, workload, n_reads, steps, warmup, rank, world, local_rank, d
                          "whole_path_bytes_per_step": ev_bytes + map_bytes,
                          "k_events": {"algorithmic_bytes_per_launch": ev_bytes, "launch_ms": ev_ms,
                                       "achieved": ev_bytes / (ev_ms * 1e-3) / 1e9 if ev_ms > 0 else None}},
-            "verify": {"steps_hashed": len(digests), "all_steps_identical": True, "hits_sha256": digests[0],
-                       # the only state the reference's Mapper carries from one read into the next (sources_added_, mapper.cpp:88,612-623)
-                       # exists only after a read that filled its path buffer: counted per read by the kernel (unc_hit_t::notes)
-                       "reads_that_filled_max_paths": int(((hits["notes"] & capi.NOTE_PATHS_FULL) != 0).sum()),
-                       "reads_ending_with_sources_added_set": int(((hits["notes"] & capi.NOTE_FLAGS_LEFT) != 0).sum()),
-                       "carry_over_note": "both 0: every read of the batch is mapped exactly as `uncalled map -t 1` maps it in any order",
-                       "t1_order": t1_info},
         })
+        if full:
+            res["verify"] = {"steps_hashed": len(digests), "all_steps_identical": True, "hits_sha256": digests[0],
+                             # the only state the reference's Mapper carries from one read into the next (sources_added_, mapper.cpp:88,612-623)
+                             # exists only after a read that filled its path buffer: counted per read by the kernel (unc_hit_t::notes)
+                             "reads_that_filled_max_paths": int(((hits["notes"] & capi.NOTE_PATHS_FULL) != 0).sum()),
+                             "reads_ending_with_sources_added_set": int(((hits["notes"] & capi.NOTE_FLAGS_LEFT) != 0).sum()),
+                             "carry_over_note": "both 0: every read of the batch is mapped exactly as `uncalled map -t 1` maps it in any order",
+                             "t1_order": t1_info}
         if world == 1 and cpu_budget > 0:
             # the CPU leg and the PAF check run on reads SAMPLED ACROSS the batch (seeded), not on its first reads
             n_cpu = min(n_reads, 12288)
@@ -616,7 +646,8 @@ def run_workload(a, workload, n_reads, steps, warmup, rank, world, local_rank, d
     return res
 
 
-def realtime_workload(a, ix, prefix, codes, lens, local_rank, ref_label, steps, warmup, verify_channels=24, cpu_budget_s=20.0, reads_per_ch=6):
+def realtime_workload(a, ix, prefix, codes, lens, local_rank, ref_label, steps, warmup, verify_channels=24, cpu_budget_s=20.0, reads_per_ch=6,
+                      dump_dir=None):
     """BASELINE config 5: 512 channels x 4000-sample chunks, deterministic MAP_ORD-style scheduling; one step = one
     chunk round (every channel hands over its next chunk, all chunks are mapped completely).  Latency is per round.
     verify: the reads `verify_channels` channels finished during the run, against the CPU chunk path (the reference's own
@@ -670,6 +701,8 @@ def realtime_workload(a, ix, prefix, codes, lens, local_rank, ref_label, steps, 
                 cur_chunk[c] = 0
                 cur_read[c] += 1
                 finished += 1
+    if dump_dir:
+        dump_hits(dump_dir, res["hit"][:k])          # (the chunks of the last round; a read still mapping has no result yet)
     lat = np.array(lat)
     out = {"metric": "chunk_round_latency_ms", "value": float(lat.mean()), "unit": "ms", "n_gpus": 1, "steps": steps,
            "warmup": warmup, "ms_per_step": float(lat.mean()), "higher_is_better": False, "scaling": "weak", "vs_baseline": None,
@@ -762,15 +795,17 @@ def compact_block(blk, top=True):
 LINE_LIMIT = 8192       # the driver keeps a bounded tail of stdout: the line must fit in it whole (round 4's 21.7 KB line did not parse)
 
 
-def emit(out):
-    """Full record -> bench_detail.json (path on stderr); ONE compact JSON line -> stdout."""
-    detail = Path(os.environ.get("UNC_BENCH_DETAIL", ROOT / "gpurun_out" / "bench_detail.json"))
-    try:
-        detail.parent.mkdir(parents=True, exist_ok=True)
-        detail.write_text(json.dumps(out, indent=1))
-        log(f"full record (prose notes, thread sweeps, phase shares, code object): {detail}")
-    except OSError as e:
-        log(f"could not write {detail}: {e}")
+def emit(out, detail=True):
+    """Full record -> bench_detail.json (path on stderr; a plain run writes it only where UNC_BENCH_DETAIL names it); ONE compact
+    JSON line -> stdout."""
+    if detail or os.environ.get("UNC_BENCH_DETAIL"):
+        path = Path(os.environ.get("UNC_BENCH_DETAIL", ROOT / "bench_out" / "bench_detail.json"))
+        try:
+            path.parent.mkdir(parents=True, exist_ok=True)
+            path.write_text(json.dumps(out, indent=1))
+            log(f"full record (prose notes, thread sweeps, phase shares, code object): {path}")
+        except OSError as e:
+            log(f"could not write {path}: {e}")
     line = compact_block(out)
     line["config"]["workload"] = out["config"]["workload"][:200]
     line["config"]["parallelism"] = out["config"].get("parallelism")
@@ -813,6 +848,12 @@ def launch_ranks(n):
         sys.exit(rc)
 
 
+# wall time of a secondary block on one MI355X with a cold index cache, with a margin (chr20 128 s in r06_bench_detail_final.json;
+# grch38 262 s there, but more than 380 s -- 132 s of them the index -- on a box with 16 host cores; realtime 5-6 s): with the default
+# --budget-s a --full run ends inside ten minutes, and the grch38 block needs a larger --budget-s
+BLOCK_S = {"grch38": 480.0, "chr20": 140.0}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs of this node (default: WORLD_SIZE when a launcher set it, else 1)")
@@ -833,11 +874,16 @@ def main():
                          "realtime:chr20, grch38 at N = 1, grch38 -- BASELINE config 4, every rank its 250 k reads -- at N > 1)")
     ap.add_argument("--grch38-reads", type=int, default=250000, help="reads of the grch38 block (config 4: 2 M reads over 8 GPUs = 250 k per GPU)")
     ap.add_argument("--chr20-reads", type=int, default=200000, help="reads of the chr20 block (config 3)")
-    ap.add_argument("--budget-s", type=float, default=float(os.environ.get("UNC_BENCH_BUDGET_S", 1500)),
-                    help="secondary blocks are skipped once this much wall time has gone")
+    ap.add_argument("--budget-s", type=float, default=float(os.environ.get("UNC_BENCH_BUDGET_S", 570)),
+                    help="a secondary block is skipped when it would end past this much wall time (BLOCK_S: its expected length)")
     ap.add_argument("--secondary-steps", type=int, default=3, help="timed steps of the chr20 / grch38 blocks (after one untimed step over the whole batch)")
     ap.add_argument("--channels", type=int, default=512)
     ap.add_argument("--rt-ref", choices=["ecoli", "chr20", "grch38"], default="ecoli", help="reference of the realtime workload")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: step digests, the extra untimed passes, the CPU baseline and the "
+                         "secondary blocks (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hits of the last timed step as DIR/<field>.npy (float64; a seeded sample past 64 MB)")
     ap.add_argument("--cpu-leg", default=None, help=argparse.SUPPRESS)      # internal: cpu_baseline_subprocess
     ap.add_argument("--cpu-leg-rt", default=None, help=argparse.SUPPRESS)   # internal: cpu_baseline_realtime_subprocess
     a = ap.parse_args()
@@ -845,6 +891,8 @@ def main():
         return cpu_leg_main(a.cpu_leg)
     if a.cpu_leg_rt:
         return cpu_leg_rt_main(a.cpu_leg_rt)
+    if a.secondary and not a.full:
+        ap.error("--secondary blocks are measured with --full only")
     if a.reads is None:
         a.reads = a_reads(argparse.Namespace(reads=int(os.environ.get("UNC_BENCH_READS", 50000)), chr20_reads=a.chr20_reads,
                                              grch38_reads=a.grch38_reads), a.workload)
@@ -895,23 +943,25 @@ def main():
         prefix, codes, lens = ensure_index(cache, rank, barrier, a.rt_ref, dev_name)
         ix = capi.Index(prefix, device=local_rank)
         out = realtime_workload(a, ix, prefix, codes, lens, local_rank, a.rt_ref, a.steps, a.warmup,
-                                cpu_budget_s=0.0 if a.no_cpu_baseline else 20.0)
+                                cpu_budget_s=20.0 if a.full and not a.no_cpu_baseline else 0.0, dump_dir=a.dump_outputs)
         if rank == 0:
-            emit(out)
+            emit(out, detail=a.full)
         return
 
-    extras = not a.no_profile_pass
-    cpu_budget = 0.0 if (a.no_cpu_baseline or not have_gpu) else 100.0
+    extras = a.full and not a.no_profile_pass
+    cpu_budget = 100.0 if (a.full and have_gpu and not a.no_cpu_baseline) else 0.0
     head = run_workload(a, a.workload, a.reads, a.steps, a.warmup, rank, world, local_rank, dist, barrier, cache, lib, dev_name,
-                        extras, cpu_budget)
+                        extras, cpu_budget, full=a.full, dump_dir=a.dump_outputs)
     out = None
     if rank == 0:
         out = {
             "metric": "reads_mapped_per_sec", "value": head["value"], "unit": "reads/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": head["ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64+f32/f64", "data": "synthetic",
-            "config": head["config"], "roofline": head["roofline"], "verify": head["verify"],
+            "config": head["config"], "roofline": head["roofline"],
         }
+        if "verify" in head:
+            out["verify"] = head["verify"]
         if "cpu_baseline" in head:
             out["cpu_baseline"] = head["cpu_baseline"]
         if "per_rank" in head:
@@ -927,7 +977,7 @@ def main():
     # N > 1: config 4 as BASELINE.json states it -- the GRCh38 index replicated on every GPU, every rank its own 250 k reads
     # (2 M reads over 8 GPUs), no collective on the data path; timed like the headline (barriers, MAX over ranks)
     if a.secondary is None:
-        a.secondary = "" if not (have_gpu and a.workload == "ecoli") else \
+        a.secondary = "" if not (a.full and have_gpu and a.workload == "ecoli") else \
             ("realtime:ecoli,chr20,realtime:chr20,grch38" if world == 1 else "grch38")
     if a.secondary:
         sec = {}
@@ -939,8 +989,8 @@ def main():
                 t = torch.tensor([spent], dtype=torch.float64, device=dev_name if have_gpu else "cpu")
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 spent = float(t.item())
-            if spent > a.budget_s:
-                sec[w] = {"skipped": f"time budget: {spent:.0f} s of {a.budget_s:.0f} s gone"}
+            if spent + BLOCK_S.get(w, 15.0) > a.budget_s:
+                sec[w] = {"skipped": f"time budget: {spent:.0f} s of {a.budget_s:.0f} s gone, the block takes ~{BLOCK_S.get(w, 15.0):.0f} s"}
                 continue
             try:
                 t0 = time.time()
@@ -977,7 +1027,7 @@ def main():
             out["secondary"] = sec
     if rank == 0:
         out["bench_wall_s"] = time.time() - T_START
-        emit(out)
+        emit(out, detail=a.full)
     if dist is not None:
         dist.destroy_process_group()
 

@@ -97,9 +97,9 @@ def ref_lib():
     """TEST INFRASTRUCTURE: the reference's own object code; only where /root/reference exists."""
     from oracle import pyref
     if not pyref.available():
-        if not Path("/root/reference/src/mapper.cpp").exists():
-            pytest.skip("reference sources not present (GPU box): oracle/_ref was not prebuilt")
-        locked_make("-C", str(ROOT / "oracle"), "ref")
+        locked_make("-C", str(ROOT / "oracle"), "ref")        # (an empty target where the reference's sources cannot be read)
+    if not pyref.available():
+        pytest.skip("reference sources not readable here and oracle/_ref/libunc_ref.so not prebuilt")
     return pyref
 
 

@@ -73,10 +73,10 @@ def test_bench_py_two_ranks_gloo(sim_lib, tmp_path):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     env = dict(os.environ, UNC_DIST_BACKEND="gloo", UNC_BENCH_LIB=str(ROOT / "tests" / "lanesim" / "_build" / "libuncalled_sim.so"),
-               UNC_BENCH_CACHE=str(tmp_path))
+               UNC_BENCH_CACHE=str(tmp_path), UNC_BENCH_DETAIL=str(tmp_path / "bench_detail.json"))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--workload", "example", "--reads", "3"], env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+                        "--workload", "example", "--reads", "3", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -95,11 +95,11 @@ def test_bench_py_launches_its_own_ranks(sim_lib, tmp_path):
     import json
     import subprocess
     env = dict(os.environ, UNC_DIST_BACKEND="gloo", UNC_BENCH_LIB=str(ROOT / "tests" / "lanesim" / "_build" / "libuncalled_sim.so"),
-               UNC_BENCH_CACHE=str(tmp_path))
+               UNC_BENCH_CACHE=str(tmp_path), UNC_BENCH_DETAIL=str(tmp_path / "bench_detail.json"))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "example",
-                        "--reads", "2", "--secondary", "example"], env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+                        "--reads", "2", "--secondary", "example", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -129,7 +129,7 @@ def test_bench_py_eight_ranks_dry_run(sim_lib, tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--workload", "example",
-                        "--reads", "1", "--secondary", "example", "--secondary-steps", "1"], env=env, capture_output=True, text=True,
+                        "--reads", "1", "--secondary", "example", "--secondary-steps", "1", "--full"], env=env, capture_output=True, text=True,
                        timeout=1500, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -142,6 +142,35 @@ def test_bench_py_eight_ranks_dry_run(sim_lib, tmp_path):
     assert "cpu_baseline" not in b                                                            # N > 1: no rank runs (or waits for) a CPU leg
     detail = json.loads((tmp_path / "bench_detail.json").read_text())
     assert detail["n_gpus"] == 8 and detail["secondary"]["example"]["n_gpus"] == 8
+
+
+def test_plain_run_dumps_the_last_step(sim_lib, tmp_path):
+    """A plain `bench.py --steps K --warmup W` (no --full) times K steps and prints the contract fields without the checks, CPU legs
+    and secondary blocks of --full; --dump-outputs writes the hits of the last timed step as float64 .npy files, the same from run to
+    run (the inputs are seeded)."""
+    import subprocess
+    from test_bench_contract import strict_line
+    from uncalled_amd import capi
+    env = dict(os.environ, UNC_BENCH_LIB=str(ROOT / "tests" / "lanesim" / "_build" / "libuncalled_sim.so"), UNC_BENCH_CACHE=str(tmp_path))
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "UNC_BENCH_DETAIL"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "example",
+                            "--reads", "2", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+        assert r.returncode == 0, r.stderr[-3000:]
+        b = strict_line([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert b["steps"] == 2 and b["warmup"] == 1 and b["ms_per_step"] > 0 and b["metric"] == "reads_mapped_per_sec"
+        assert abs(b["value"] - 2 / (b["ms_per_step"] * 1e-3)) / b["value"] < 1e-4
+        assert not {"verify", "cpu_baseline", "secondary"} & set(b)
+        files = sorted(d.glob("*.npy"))
+        assert {f.stem for f in files} == set(capi.RESULT_FIELDS) - {"pad_"}
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(x.dtype == np.float64 and x.shape == (2,) for x in arrs.values())
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_launcher_without_gpus_flag_is_adopted(sim_lib, tmp_path):

@@ -25,7 +25,7 @@ pmc|pmc_chr20|pmc_grch38)
   cp $OUT/pmc_$W/summary.json profiles/r06_pmc_sq_summary_$W.json; cp $OUT/pmc_$W/pmc_k_map.json profiles/r06_pmc_k_map_$W.json
   mkdir -p $OUT/profiles_out; cp profiles/r06_pmc_sq_summary_$W.json profiles/r06_pmc_k_map_$W.json $OUT/profiles_out/ ;;
 bench)
-  UNC_BENCH_DETAIL=$OUT/bench_detail.json timeout 1700 python bench.py --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 400 $OUT/bench_default.json; echo ;;
+  UNC_BENCH_DETAIL=$OUT/bench_detail.json timeout 1700 python bench.py --steps 20 --warmup 5 --full --budget-s 1500 > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 400 $OUT/bench_default.json; echo ;;
 stats)
   cd /tmp; export TMPDIR=/tmp
   UNC_BENCH_DETAIL=$OUT/bench_detail_rocprof.json timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o r06 -- python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile-pass --no-pipeline --secondary "" > $OUT/bench_rocprof.json 2> $OUT/bench_rocprof.err
