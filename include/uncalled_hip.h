@@ -207,8 +207,9 @@ int unc_map_batch(unc_mapper_t *m, uint32_t n_reads, const int16_t *raw, const u
                   const unc_calib_t *calib, int on_device, void *stream, unc_hit_t *hits);
 /* The same batch in two halves (unc_map_batch = the two in a row).  _begin stages the reads and launches the kernels on `stream` (NULL:
  * the mapper's own stream) and returns at once; _end waits, maps again the few reads that need it and fills hits[0 .. n_reads).  `raw`
- * (on_device != 0: a device pointer) must stay valid until _end; `offsets` and `calib` are copied by _begin.  One batch per mapper at a
- * time.  What it is for: the worker loop of MapPool::MapperThread::run (map_pool.cpp:130-158) with TWO mappers over one index -- batch
+ * (on_device != 0: a device pointer) must stay valid until _end; `offsets` and `calib` are copied by _begin (into the mapper, before it
+ * returns: the caller may reuse them at once, page-locked or not).  One batch per mapper at a time; while it is in flight
+ * unc_detect_events, unc_trace_begin and unc_trace_step on the same mapper fail with UNC_ERR_ARG.  What it is for: the worker loop of MapPool::MapperThread::run (map_pool.cpp:130-158) with TWO mappers over one index -- batch
  * k + 1 is begun on the second while batch k's last long reads finish on the first, and moves into the compute units as they fall idle
  * (a persistent launch ends with a few wavefronts on a few long reads: 6 % of a 50 k-read E. coli launch). */
 int unc_map_batch_begin(unc_mapper_t *m, uint32_t n_reads, const int16_t *raw, const uint64_t *offsets,

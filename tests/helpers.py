@@ -2,10 +2,46 @@
 import numpy as np
 
 from oracle import pyoracle as po
+from tools.simulate_reads import CAL_DIGITISATION, CAL_OFFSET, CAL_RANGE
 from uncalled_amd import capi
 
 HIT_INT_FIELDS = ("mapped", "fwd", "rd_st", "rd_en", "rd_len", "rf_st", "rf_en", "rf_len", "matches",
                   "n_events", "event_i", "n_nbr", "n_sa", "n_lf", "notes")
+
+
+# Channel calibrations (range, offset, digitisation).  The simulators, the goldens and the example read all carry the first one; the others
+# reach what it never does: another range with a small negative offset, a PromethION-like digitisation of 2048 with a large negative offset
+# (illustrative values, not measured from a run), a non-integer offset, and identity (pA = the stored sample).  With an integer negative
+# offset a stored -offset is exactly 0 pA and anything below it is negative.
+REGIMES = {
+    "minion": (CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION),
+    "minion_b": (1472.38, -7.0, 8192.0),
+    "promethion": (748.6, -243.0, 2048.0),
+    "frac_offset": (1398.7, 13.37, 8192.0),
+    "identity": (8192.0, 0.0, 8192.0),
+}
+
+
+def calibrate_np(raw_i16, rng, offset, digitisation):
+    """ReadBuffer's calibration restated in numpy float32: the stored int16 taken as u16, then add, multiply, divide, each rounded once."""
+    u = np.asarray(raw_i16, dtype=np.int16).view(np.uint16).astype(np.float32)
+    return (np.float32(rng) * (u + np.float32(offset))) / np.float32(digitisation)
+
+
+def redigitise(raw_i16, from_cal, to_cal):
+    """int16 samples recorded under `from_cal` -> the samples a channel calibrated with `to_cal` records for the same pA signal:
+    rint(pA * digitisation / range - offset), kept inside [0, 32767]."""
+    pa = calibrate_np(raw_i16, *from_cal).astype(np.float64)
+    rng, offset, digit = to_cal
+    return np.clip(np.rint(pa * digit / rng - offset), 0, 32767).astype(np.int16)
+
+
+def calib_of(cals):
+    """[(range, offset, digitisation)] -> CALIB array"""
+    c = capi.make_calib(len(cals), 0.0, 0.0, 0.0)
+    for i, (r, o, d) in enumerate(cals):
+        c[i]["range"], c[i]["offset"], c[i]["digitisation"] = r, o, d
+    return c
 
 
 def oracle_hits(oix, raw, offsets, calib, params=None, fresh_mapper_per_read=False):
@@ -54,7 +90,10 @@ def oracle_hits_threads(oix, raw, offsets, calib, dev_hits=None, threads=None):
     is mapped once more by a FRESH oracle Mapper before it counts (tests/dev/parity_sweep.py does the same against the reference)."""
     import os
     threads = threads or max(1, min(offsets.size - 1, len(os.sched_getaffinity(0))))
-    sig = po.calibrate(raw, float(calib["range"][0]), float(calib["offset"][0]), float(calib["digitisation"][0]))
+    sig = np.zeros(raw.size, dtype=np.float32)
+    for i in range(offsets.size - 1):            # every read under its own calibration
+        a, b = int(offsets[i]), int(offsets[i + 1])
+        sig[a:b] = po.calibrate(raw[a:b], float(calib["range"][i]), float(calib["offset"][i]), float(calib["digitisation"][i]))
     want, secs = po.map_batch(oix, sig, offsets, threads)
     redone = 0
     if dev_hits is not None:

@@ -202,15 +202,17 @@ def case_read_order_t1(lib, oracle_lib, example, goldens, max_paths, n_reads, sp
     assert_hits_equal(m.map_batch(raw, off, cal), indep, "independent order")
 
 
-def case_trace_matches_oracle_every_event(lib, oracle_lib, example, goldens, dev_index=None):
+def case_trace_matches_oracle_every_event(lib, oracle_lib, example, goldens, dev_index=None, raw=None, cal=None):
     """Path buffer (order, ranges, k-mers, prob-sum windows, flags) and the seed-cluster set after every map_next."""
     dev_index = dev_index or _index(lib, example)
-    raw = example["signal"][:6000]
-    cal = capi.make_calib(1, example["range"], example["offset"], example["digitisation"])
+    if raw is None:
+        raw = example["signal"][:6000]
+        cal = (example["range"], example["offset"], example["digitisation"])
     m = capi.Mapper(dev_index, n_slots=1)
     oix = oracle_lib.Index(example["prefix"])
     om = oracle_lib.Mapper(oix)
-    sig = oracle_lib.calibrate(raw, example["range"], example["offset"], example["digitisation"])
+    sig = oracle_lib.calibrate(raw, *cal)
+    cal = capi.make_calib(1, *cal)
     steps = 0
     for (dd, dpaths, dclus, dmm, dls, dnl), (od, oe, opaths, oclus, omm, ols, onl) in zip(m.trace(raw, cal), om.trace(sig)):
         assert dd == od, steps
@@ -841,3 +843,302 @@ def case_batch_in_two_halves(lib, oracle_lib, example, goldens, n_reads=6):
     with pytest.raises(capi.UncalledHipError):
         a.end_batch()                          # nothing begun
     assert_hits_equal(a.map_batch(raw, off, cal), want, "unc_map_batch after the halves")
+
+
+# ---- calibrations other than the simulators' (tests/helpers.py REGIMES): per value, per read, per channel
+
+def _wide_bounds(lib):
+    """default parameters with no event dropped for its mean"""
+    p = capi.default_params(lib)
+    p.min_mean, p.max_mean = -3.0e38, 3.0e38
+    return p
+
+
+def _assert_events_equal(po, means, moff, info, reads, cals, params, what):
+    """every kept mean, both counters, the mean event length and the normaliser's scale / shift of every read against the oracle"""
+    for i, (r, c) in enumerate(zip(reads, cals)):
+        ev, mel, tot = po.detect_events(po.calibrate(r, *c), params)
+        assert info["n_events"][i] == len(ev) and info["total_events"][i] == tot, (what, i, int(info["n_events"][i]), len(ev))
+        got = means[int(moff[i]):int(moff[i + 1])]
+        assert np.array_equal(got.view(np.uint32), ev["mean"].astype(np.float32).view(np.uint32)), (what, i)
+        if tot:
+            assert np.float32(info["len_sum"][i] / info["total_events"][i]) == np.float32(mel), (what, i)
+        if len(ev):
+            _, sc, sh = po.normalize(ev["mean"])
+            assert np.float32(sc).tobytes() == np.float32(info["scale"][i]).tobytes(), (what, i)
+            assert np.float32(sh).tobytes() == np.float32(info["shift"][i]).tobytes(), (what, i)
+
+
+def case_calibration_through_event_means(lib, oracle_lib, example):
+    """Step signals -- runs of 20 equal samples over the whole int16 range, negative values (u16 above 32767) included -- one read per
+    calibration regime in ONE batch: an event inside a run has the run's calibrated value as its mean, so k_events' calibration of each
+    read shows value by value (against the numpy restatement), and every event against the oracle.  No event is dropped for its mean."""
+    from tests.helpers import REGIMES, calibrate_np, calib_of
+    po = oracle_lib
+    p = _wide_bounds(lib)
+    rng = np.random.default_rng(11)
+    reads, cals = [], list(REGIMES.values())
+    for _ in cals:
+        vals = np.concatenate((rng.integers(-32768, 32768, 100), rng.integers(0, 1024, 20), [0, -1, 1, 32767, -32768, 243, 242, 244, 7, 6]))
+        rng.shuffle(vals)
+        r = np.repeat(vals, 20).astype(np.int16)
+        r[rng.integers(0, r.size, 40)] += 1          # a few runs broken: events that straddle a change
+        reads.append(r)
+    raw = np.concatenate(reads)
+    off = np.concatenate(([0], np.cumsum([r.size for r in reads]))).astype(np.uint64)
+    m = capi.Mapper(_index(lib, example), params=p, n_slots=1)
+    means, moff, info = m.detect_events(raw, off, calib_of(cals))
+    _assert_events_equal(po, means, moff, info, reads, cals, to_oracle_params(p), "step signals")
+    for i, (r, c) in enumerate(zip(reads, cals)):
+        ev = po.detect_events(po.calibrate(r, *c), to_oracle_params(p))[0]
+        st, ln = ev["start"].astype(np.int64), ev["length"].astype(np.int64)
+        inside = np.array([ln[j] > 0 and np.all(r[st[j]:st[j] + ln[j]] == r[st[j]]) for j in range(len(ev))], dtype=bool)
+        assert inside.sum() >= 100, (i, int(inside.sum()))
+        got = means[int(moff[i]):int(moff[i + 1])][inside]
+        assert np.array_equal(got.view(np.uint32), calibrate_np(r[st[inside]], *c).view(np.uint32)), i
+
+
+def case_event_mean_bounds(lib, oracle_lib, example):
+    """Identity calibration (pA = the stored sample): steps at exactly min_mean - 1, min_mean, max_mean, max_mean + 1 pA -- the inclusive
+    bounds keep and drop the same events as the oracle, and the bounds' own values are kept."""
+    from tests.helpers import REGIMES, calib_of
+    po = oracle_lib
+    cal = REGIMES["identity"]
+    rng = np.random.default_rng(12)
+    reads, params = [], []
+    for lo, hi in ((55, 130), (0, 400)):
+        p = capi.default_params(lib)
+        p.min_mean, p.max_mean = float(lo), float(hi)
+        levels = [lo, hi, hi + 1, 90, 170] + ([lo - 1] if lo > 0 else [])
+        vals = rng.choice(levels, 160)
+        vals[1:][vals[1:] == vals[:-1]] = 100           # no two equal neighbouring runs
+        reads.append(np.repeat(vals, 20).astype(np.int16))
+        params.append(p)
+    for r, p in zip(reads, params):
+        off = np.array([0, r.size], dtype=np.uint64)
+        means, moff, info = capi.Mapper(_index(lib, example), params=p, n_slots=1).detect_events(r, off, calib_of([cal]))
+        _assert_events_equal(po, means, moff, info, [r], [cal], to_oracle_params(p), "bounds %g..%g" % (p.min_mean, p.max_mean))
+        assert np.float32(p.min_mean) in means and np.float32(p.max_mean) in means and means.min() >= p.min_mean and means.max() <= p.max_mean
+        assert int(info["total_events"][0]) > int(info["n_events"][0])     # events beyond the bounds were detected and dropped
+
+
+def case_zero_pa_windows(lib, oracle_lib, example):
+    """Integer negative offsets: runs of samples at exactly 0 pA, runs of negative pA and mixtures of the two inside one t-statistic
+    window (the sums of a window are then exactly zero or of either sign: the exact division's fallback, k_events.hip div_w), between
+    ordinary levels; every kept mean and both counters against the oracle, default bounds and none, at several alignments in the batch."""
+    from tests.helpers import REGIMES, calib_of
+    po = oracle_lib
+    rng = np.random.default_rng(13)
+    for name in ("promethion", "minion_b"):
+        cal = REGIMES[name]
+        z = int(-cal[1])                               # the stored value of 0 pA
+        parts = []
+        for k in range(120):
+            kind = k % 4
+            ln = int(rng.integers(2, 16))
+            if kind == 0:
+                parts.append(np.full(ln, z))
+            elif kind == 1:
+                parts.append(np.full(ln, int(rng.integers(max(0, z - 40), z))))
+            elif kind == 2:
+                parts.append(rng.integers(max(0, z - 3), z + 1, ln))
+            else:
+                parts.append(rng.integers(z + 150, z + 400, ln))
+        r = np.concatenate(parts).astype(np.int16)
+        for p in (capi.default_params(lib), _wide_bounds(lib)):
+            m = capi.Mapper(_index(lib, example), params=p, n_slots=2)
+            for pad in (0, 1, 5, 13):
+                full = np.concatenate((np.full(pad, z + 300, np.int16), r))
+                off = np.array([0, pad, pad + r.size], dtype=np.uint64) if pad else np.array([0, r.size], dtype=np.uint64)
+                cals = [REGIMES["minion"], cal] if pad else [cal]
+                reads = [full[:pad], r] if pad else [r]
+                means, moff, info = m.detect_events(full, off, calib_of(cals))
+                _assert_events_equal(po, means, moff, info, reads, cals, to_oracle_params(p), "%s pad %d min_mean %g" % (name, pad, p.min_mean))
+        ev = po.detect_events(po.calibrate(r, *cal), to_oracle_params(_wide_bounds(lib)))[0]
+        assert (ev["mean"] == 0).any() and (ev["mean"] < 0).any(), name
+
+
+def per_read_regime_batch(goldens, n_reads, seed=21):
+    """golden simulated reads re-digitised, each under a regime of its own, neighbours under different ones -> (raw, offsets, calib, names)"""
+    from tests.helpers import REGIMES, calib_of, redigitise
+    names = list(REGIMES)
+    rng = np.random.default_rng(seed)
+    pick = [int(rng.integers(0, len(names)))]
+    while len(pick) < n_reads:
+        k = int(rng.integers(0, len(names)))
+        if k != pick[-1]:
+            pick.append(k)
+    off_all = goldens["sim_offsets"]
+    order = rng.permutation(off_all.size - 1)[:n_reads]
+    reads = [redigitise(goldens["sim_signal"][int(off_all[j]):int(off_all[j + 1])], REGIMES["minion"], REGIMES[names[k]]) for j, k in zip(order, pick)]
+    off = np.concatenate(([0], np.cumsum([r.size for r in reads]))).astype(np.uint64)
+    return np.concatenate(reads), off, calib_of([REGIMES[names[k]] for k in pick]), [names[k] for k in pick]
+
+
+def case_per_read_calibration_batch(lib, oracle_lib, example, goldens, n_reads=10, device=None):
+    """One batch, every read under its own calibration (re-digitised simulated reads), through every batch entry point: unc_map_batch,
+    _begin / _end with two mappers in flight, unc_detect_events, UNC_ORDER_T1 and (device: a function that puts the samples in HBM and
+    returns their address) the device-resident path -- against the oracle mapping each read under its own calibration."""
+    from tests.helpers import calibrate_np
+    po = oracle_lib
+    raw, off, cal, names = per_read_regime_batch(goldens, n_reads)
+    oix = po.Index(example["prefix"])
+    want = oracle_hits(oix, raw, off, cal, fresh_mapper_per_read=True)
+    share = {n: (int(sum(want["mapped"][i] for i in range(n_reads) if names[i] == n)), names.count(n)) for n in sorted(set(names))}
+    assert int(want["mapped"].sum()) >= 0.8 * n_reads, share          # the reads are seeded and mapped, not just left unmapped
+    dev_index = _index(lib, example)
+    a = capi.Mapper(dev_index, n_slots=4, n_waves=2, slice_events=50)
+    assert_hits_equal(a.map_batch(raw, off, cal), want, "per-read calibration, unc_map_batch")
+    half = n_reads // 2
+    b = capi.Mapper(dev_index, n_slots=3, n_waves=3)
+    a.begin_batch(raw, off, cal)
+    b.begin_batch(raw[int(off[half]):], (off[half:] - off[half]).astype(np.uint64), cal[half:])
+    assert_hits_equal(a.end_batch(), want, "per-read calibration, _begin / _end")
+    assert_hits_equal(b.end_batch(), want[half:], "per-read calibration, second half on a second mapper")
+    means, moff, info = a.detect_events(raw, off, cal)
+    reads = [raw[int(off[i]):int(off[i + 1])] for i in range(n_reads)]
+    _assert_events_equal(po, means, moff, info, reads, [tuple(float(c[f]) for f in ("range", "offset", "digitisation")) for c in cal],
+                         po.default_params(), "per-read calibration, detect_events")
+    t1 = capi.Mapper(dev_index, n_slots=3)
+    t1.set_read_order(capi.ORDER_T1)
+    assert_hits_equal(t1.map_batch(raw, off, cal), oracle_hits(oix, raw, off, cal, fresh_mapper_per_read=False), "per-read calibration, -t 1 order")
+    if device is not None:
+        ptr = device(raw)
+        assert_hits_equal(a.map_batch_device(ptr, off, cal), want, "per-read calibration, samples in HBM")
+        a.begin_batch(ptr, off, cal, on_device=True)
+        assert_hits_equal(a.end_batch(), want, "per-read calibration, _begin on device")
+    # the calibration reaches the kernels as the numpy restatement says (a sample of every read)
+    for i in range(n_reads):
+        c = cal[i]
+        assert np.array_equal(po.calibrate(reads[i][:64], *(float(c[f]) for f in ("range", "offset", "digitisation"))),
+                              calibrate_np(reads[i][:64], c["range"], c["offset"], c["digitisation"]))
+    return share
+
+
+def case_trace_under_another_calibration(lib, oracle_lib, example, goldens):
+    """the step-wise trace of the example read re-digitised for a PromethION-like channel"""
+    from tests.helpers import REGIMES, calib_of, redigitise
+    cal = REGIMES["promethion"]
+    raw = redigitise(example["signal"], (example["range"], example["offset"], example["digitisation"]), cal)
+    case_trace_matches_oracle_every_event(lib, oracle_lib, example, goldens, raw=raw[:6000], cal=cal)
+
+
+def case_refused_while_pending(lib, oracle_lib, example, goldens, n_reads=4):
+    """unc_detect_events and unc_trace_begin stage into the buffers a batch begun with unc_map_batch_begin is still reading: both are
+    refused until unc_map_batch_end, which still returns the oracle's hits; afterwards both work again."""
+    from tests.helpers import REGIMES
+    raw, off, cal, _ = per_read_regime_batch(goldens, n_reads, seed=22)
+    want = oracle_hits(oracle_lib.Index(example["prefix"]), raw, off, cal, fresh_mapper_per_read=True)
+    m = capi.Mapper(_index(lib, example), n_slots=2)
+    other = np.ascontiguousarray(raw[::-1][:int(off[-1]) // 2])
+    m.begin_batch(raw, off, cal)
+    with pytest.raises(capi.UncalledHipError):
+        m.detect_events(other, np.array([0, 3000, other.size], dtype=np.uint64), capi.make_calib(2, *REGIMES["identity"]))
+    with pytest.raises(capi.UncalledHipError):
+        next(m.trace(other, capi.make_calib(1, *REGIMES["promethion"])))
+    assert_hits_equal(m.end_batch(), want, "batch with refused calls in between")
+    means, moff, info = m.detect_events(raw, off, cal)
+    assert int(info["n_events"].sum()) == means.size > 0
+
+
+class _ShuffledRt:
+    """stands in for a MapPoolOrd's capi.Realtime: hands each round's chunks over in a random order (the results are put back in the
+    caller's), and with `f32` as floats -- calibrated here with the chunk's calibration -- with nonsense in the chunks' calibration,
+    which unc_rt_process_chunks_f32 ignores"""
+
+    def __init__(self, rt, po, rng, f32):
+        self.rt, self.po, self.rng, self.f32, self.params = rt, po, rng, f32, rt.params
+
+    def process_chunks(self, chunks, raw):
+        p = self.rng.permutation(chunks.size)
+        ch = chunks[p].copy()
+        if self.f32:
+            sig = np.zeros(raw.size, dtype=np.float32)
+            for c in ch:
+                a, n = int(c["offset"]), int(c["n_samples"])
+                sig[a:a + n] = self.po.calibrate(raw[a:a + n], float(c["calib"]["range"]), float(c["calib"]["offset"]), float(c["calib"]["digitisation"]))
+            ch["calib"]["range"], ch["calib"]["offset"], ch["calib"]["digitisation"] = np.nan, 3.0e38, 0.0
+            res = self.rt.process_chunks_f32(ch, sig)
+        else:
+            res = self.rt.process_chunks(ch, raw)
+        out = np.empty_like(res)
+        out[p] = res
+        return out
+
+
+def case_chunked_per_channel_calibration(lib, oracle_lib, example, goldens, n_channels=3, reads_per_channel=2, shuffle=False, f32=False,
+                                         cut=None, seed=31):
+    """The chunked path with a calibration per channel AND per read (a channel's successive reads differ: a value kept from the
+    channel's first read shows), reads re-digitised for them.  shuffle: every round's chunks in a random order and random channels left
+    out of some rounds -- no channel's sequence changes, so a mix-up of the active-chunk index and the channel (descriptors, slot map,
+    event-means offsets) shows.  f32: the chunks as floats with nonsense calibrations, which that entry ignores.  Each channel against
+    one oracle Mapper fed the same reads in the same order (on the host's threads)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from tests.helpers import REGIMES, redigitise
+    from uncalled_amd.realtime import MapPoolOrd
+    po = oracle_lib
+    dev_index = _index(lib, example)
+    oix = po.Index(example["prefix"])
+    names = list(REGIMES)
+    off = goldens["sim_offsets"]
+    n_src = off.size - 1
+    reads = {}                                   # key -> (channel, raw, calibration)
+    for ch in range(n_channels):
+        for j in range(reads_per_channel):
+            k = ch * reads_per_channel + j
+            base = REGIMES[names[(ch + j) % len(names)]]
+            cal = (float(np.float32(base[0] * (1.0 + 1e-4 * (k + 1)))), base[1], base[2])      # every channel and read its own range
+            src = goldens["sim_signal"][int(off[k % n_src]):int(off[k % n_src + 1])]
+            raw = redigitise(src[:cut] if cut else src, REGIMES["minion"], cal)
+            reads[k] = (ch, raw, cal)
+    pool = MapPoolOrd(dev_index, n_channels=n_channels)
+    rng = np.random.default_rng(seed)
+    pool.rt = _ShuffledRt(pool.rt, po, rng, f32) if (shuffle or f32) else pool.rt
+    for k, (ch, raw, cal) in reads.items():
+        pool.add_read(ch, k, raw, cal, key=k)
+
+    def oracle_channel(ch):
+        om = po.Mapper(oix)
+        out = {}
+        for k in range(ch * reads_per_channel, (ch + 1) * reads_per_channel):
+            _, raw, cal = reads[k]
+            h, used = om.chunk_read(po.calibrate(raw, *cal), pool.chunk_len)
+            out[k] = (h, used, om.rt_ended())
+        return out
+    import os
+    with ThreadPoolExecutor(max_workers=max(1, min(16, len(os.sched_getaffinity(0))))) as ex:
+        futs = [ex.submit(oracle_channel, ch) for ch in range(n_channels)]
+    want = {}
+    for f in futs:
+        want.update(f.result())
+    got, rounds, skipped = {}, 0, 0
+    while pool.running():
+        held = {}
+        if shuffle:
+            busy = [ch for ch, q in enumerate(pool.queues) if q]
+            for ch in busy[:-1] if len(busy) > 1 else []:
+                if rng.random() < 0.25:
+                    held[ch], pool.queues[ch] = pool.queues[ch], []
+            skipped += len(held)
+        try:
+            for key, r in pool.update():
+                got[key] = r
+        finally:
+            for ch, q in held.items():
+                pool.queues[ch] = q
+        rounds += 1
+        assert rounds < 4000
+    assert not shuffle or skipped > 0
+    ref_names, dev_names = oix.ref_names(), dev_index.seq_names()
+    for k in reads:
+        h, (o, used, ended) = got[k]["hit"], want[k]
+        assert int(h["status"]) == 0, k
+        assert capi.hit_paf_cols(h, dev_names) == po.hit_paf_cols(o, ref_names), k
+        for f in ("event_i", "n_nbr", "n_sa", "n_lf", "notes"):
+            assert int(h[f]) == int(o[f]), (k, f)
+        assert got[k]["state"] == (capi.RT_MAPPED if o["mapped"] else capi.RT_FAILED), k
+        assert (pool.chunks_used[k], bool(got[k]["ended"])) == (used, ended), k
+    mapped = sum(int(want[k][0]["mapped"]) for k in reads)
+    assert mapped >= 0.6 * len(reads), (mapped, len(reads))
+    assert all(reads[k][1].size > pool.chunk_len for k in reads) and any(want[k][1] > 1 for k in reads)     # reads of several chunks
+    return mapped, len(reads)

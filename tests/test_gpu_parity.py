@@ -246,3 +246,125 @@ def test_team_round_that_fills_the_buffer_exactly(hip_lib, team):
     from pathlib import Path
     from tests.test_lanesim_parity import _fuzz_round
     _fuzz_round(Path(__file__).resolve().parents[1] / "uncalled_amd" / "libuncalled_hip.so", 9512, "rt", team)
+
+
+# ---- calibrations other than the simulators' (tests/helpers.py REGIMES)
+
+def test_calibration_through_event_means(hip_lib, oracle_lib, example):
+    pc.case_calibration_through_event_means(hip_lib, oracle_lib, example)
+
+
+def test_event_mean_bounds(hip_lib, oracle_lib, example):
+    pc.case_event_mean_bounds(hip_lib, oracle_lib, example)
+
+
+def test_zero_pa_windows(hip_lib, oracle_lib, example):
+    pc.case_zero_pa_windows(hip_lib, oracle_lib, example)
+
+
+def test_per_read_calibration_batch(hip_lib, oracle_lib, example, goldens):
+    import torch
+    held = []
+
+    def to_device(raw):
+        t = torch.from_numpy(np.ascontiguousarray(raw)).to("cuda:0")
+        torch.cuda.synchronize()
+        held.append(t)
+        return t.data_ptr()
+    share = pc.case_per_read_calibration_batch(hip_lib, oracle_lib, example, goldens, n_reads=40, device=to_device)
+    print("per-read calibration batch, mapped / reads per regime:", share)
+
+
+def test_trace_under_another_calibration(hip_lib, oracle_lib, example, goldens):
+    pc.case_trace_under_another_calibration(hip_lib, oracle_lib, example, goldens)
+
+
+def test_refused_while_pending(hip_lib, oracle_lib, example, goldens):
+    pc.case_refused_while_pending(hip_lib, oracle_lib, example, goldens)
+
+
+@pytest.mark.parametrize("shuffle,f32", [(False, False), (True, False), (True, True)])
+def test_chunked_per_channel_calibration(hip_lib, oracle_lib, example, goldens, shuffle, f32):
+    pc.case_chunked_per_channel_calibration(hip_lib, oracle_lib, example, goldens, n_channels=6, reads_per_channel=3, shuffle=shuffle, f32=f32)
+
+
+def test_chunked_512_channels_per_channel_calibration(hip_lib, oracle_lib, example, goldens, monkeypatch):
+    """config 5's width: 512 channels on teams of 8, two reads each, every channel and read under a calibration of its own, rounds
+    shuffled and thinned; every read against its channel's oracle Mapper"""
+    monkeypatch.setenv("UNC_RT_TEAM", "8")
+    mapped, n = pc.case_chunked_per_channel_calibration(hip_lib, oracle_lib, example, goldens, n_channels=512, reads_per_channel=2, shuffle=True)
+    print(f"512 channels: {mapped} of {n} reads mapped")
+
+
+def test_staging_buffers_reused_after_begin(hip_lib, oracle_lib, example, goldens):
+    """`offsets` and `calib` are copied by unc_map_batch_begin (include/uncalled_hip.h): in page-locked memory (unc_host_alloc), begun on
+    a stream with another mapper's batch queued ahead, and overwritten -- other calibrations, read boundaries moved by a few samples --
+    as soon as _begin returns, the batch still maps what it was given.  (The overwriting values are valid: a copy that ran late would
+    give wrong hits, never an access out of bounds.)"""
+    import ctypes as C
+    import torch
+    from tests.helpers import assert_hits_equal
+    raw, off, cal, _ = pc.per_read_regime_batch(goldens, 24, seed=23)
+    n = off.size - 1
+    want = oracle_hits(oracle_lib.Index(example["prefix"]), raw, off, cal, fresh_mapper_per_read=True)
+    ix = capi.Index(example["prefix"], lib=hip_lib)
+    go = goldens["sim_offsets"]
+    big_raw = np.tile(goldens["sim_signal"][:int(go[-1])], 4)
+    big_off = np.concatenate([go[:-1] + k * go[-1] for k in range(4)] + [[4 * go[-1]]]).astype(np.uint64)
+    blocker = capi.Mapper(ix, n_slots=4, n_waves=4)
+    m = capi.Mapper(ix, n_slots=8)
+    nb_off, nb_cal = (n + 1) * 8, n * capi.CALIB.itemsize
+    buf = hip_lib.unc_host_alloc(nb_off + nb_cal)
+    assert buf
+    try:
+        a = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_uint8)), shape=(nb_off + nb_cal,))
+        p_off, p_cal = a[:nb_off].view(np.uint64), a[nb_off:].view(capi.CALIB)
+        p_off[:] = off
+        p_cal[:] = cal
+        moved = off.copy()
+        moved[1:-1] = off[1:-1] + np.where(np.arange(1, n) % 2 == 1, 3, -3).astype(np.uint64)     # same first and last offset
+        s = torch.cuda.Stream()
+        blocker.begin_batch(big_raw, big_off, capi.make_calib(big_off.size - 1, CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION), stream=s.cuda_stream)
+        m.begin_batch(raw, p_off, p_cal, stream=s.cuda_stream)
+        p_off[:] = moved
+        p_cal[:] = np.roll(cal, 1)               # every read another regime
+        hits = m.end_batch()
+        blocker.end_batch()
+        assert_hits_equal(hits, want, "offsets and calib reused after _begin")
+    finally:
+        torch.cuda.synchronize()
+        hip_lib.unc_host_free(buf)
+
+
+def test_ecoli_scale_per_read_calibration(hip_lib, oracle_lib, ecoli):
+    """1 024 E. coli reads, each re-digitised for a calibration regime of its own (neighbours differ), against the oracle on all host
+    threads -- which calibrates every read with its own entry (tests/helpers.py oracle_hits_threads)"""
+    from tests.helpers import REGIMES, calib_of, oracle_hits_threads, redigitise
+    from tools.simulate_reads_torch import simulate_reads_torch
+    n = 1024
+    sim = simulate_reads_torch(ecoli["codes"], ecoli["lens"], n, seed=44, device="cuda:0")
+    raw0 = sim["signal"].cpu().numpy()
+    off = sim["offsets"]
+    names = list(REGIMES)
+    rng = np.random.default_rng(44)
+    pick = [0]
+    while len(pick) < n:
+        k = int(rng.integers(0, len(names)))
+        if k != pick[-1]:
+            pick.append(k)
+    raw = raw0.copy()
+    for i, k in enumerate(pick):
+        a, b = int(off[i]), int(off[i + 1])
+        raw[a:b] = redigitise(raw0[a:b], REGIMES["minion"], REGIMES[names[k]])
+    cal = calib_of([REGIMES[names[k]] for k in pick])
+    ix = capi.Index(ecoli["prefix"], lib=hip_lib)
+    hits = capi.Mapper(ix).map_batch(raw, off, cal)
+    want, _secs, redone = oracle_hits_threads(oracle_lib.Index(ecoli["prefix"]), raw, off, cal, hits)
+    assert_hits_equal(hits, want, "ecoli, per-read calibration")
+    assert redone <= 2
+    share = {}
+    for j, name in enumerate(names):
+        sel = np.array(pick) == j
+        share[name] = (int(hits["mapped"][sel].sum()), int(sel.sum()))
+        assert share[name][0] >= 0.6 * share[name][1], share
+    print("ecoli per-read calibration, mapped / reads per regime:", share)

@@ -218,3 +218,38 @@ def test_team_round_that_fills_the_buffer_exactly(sim_lib):
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
     _fuzz_round(root / "tests" / "lanesim" / "_build" / "libuncalled_sim.so", 9512, "rt", 2)
+
+
+def test_calibration_through_event_means(sim_lib, oracle_lib, example):
+    pc.case_calibration_through_event_means(sim_lib, oracle_lib, example)
+
+
+def test_event_mean_bounds(sim_lib, oracle_lib, example):
+    pc.case_event_mean_bounds(sim_lib, oracle_lib, example)
+
+
+def test_zero_pa_windows(sim_lib, oracle_lib, example):
+    pc.case_zero_pa_windows(sim_lib, oracle_lib, example)
+
+
+def test_per_read_calibration_batch(sim_lib, oracle_lib, example, goldens):
+    pc.case_per_read_calibration_batch(sim_lib, oracle_lib, example, goldens, n_reads=8)
+
+
+def test_trace_under_another_calibration(sim_lib, oracle_lib, example, goldens):
+    pc.case_trace_under_another_calibration(sim_lib, oracle_lib, example, goldens)
+
+
+def test_refused_while_pending(sim_lib, oracle_lib, example, goldens):
+    pc.case_refused_while_pending(sim_lib, oracle_lib, example, goldens)
+
+
+@pytest.mark.parametrize("shuffle,f32", [(False, False), (True, False), (True, True)])
+def test_chunked_per_channel_calibration(sim_lib, oracle_lib, example, goldens, shuffle, f32):
+    pc.case_chunked_per_channel_calibration(sim_lib, oracle_lib, example, goldens, n_channels=3, reads_per_channel=2, shuffle=shuffle, f32=f32,
+                                            cut=8000)
+
+
+def test_chunked_per_channel_calibration_many_channels(sim_lib, oracle_lib, example, goldens):
+    """the 512-channel case of the GPU suite on 20 channels (reads cut to 6000 samples), rounds shuffled"""
+    pc.case_chunked_per_channel_calibration(sim_lib, oracle_lib, example, goldens, n_channels=20, reads_per_channel=2, shuffle=True, cut=6000)

@@ -394,3 +394,17 @@ def test_tie_order_of_the_unstable_sort_is_counted_not_assumed(ref_lib, example,
         assert seen[mode][2][0] == sorts
     # the order is not without effect: some read's work counters move under the reversed order
     assert seen[pr.SORT_REVERSED_TIES][1] != seen[pr.SORT_STABLE][1]
+
+
+def test_calibrate_equals_numpy_restatement_every_value(oracle_lib):
+    """po.calibrate against the float32 restatement (u16 reinterpretation, then add, multiply, divide, each rounded once) for every
+    int16 value under every calibration regime: the oracle side of the calibration cases, pinned without the reference"""
+    from tests.helpers import REGIMES, calibrate_np
+    raw = np.arange(-32768, 32768, dtype=np.int32).astype(np.int16)
+    for name, cal in REGIMES.items():
+        got = oracle_lib.calibrate(raw, *cal)
+        assert np.array_equal(got.view(np.uint32), calibrate_np(raw, *cal).view(np.uint32)), name
+    u = raw.view(np.uint16).astype(np.float64)
+    assert np.array_equal(oracle_lib.calibrate(raw, *REGIMES["identity"]), u.astype(np.float32))      # identity: pA = the stored u16
+    z = REGIMES["promethion"]
+    assert oracle_lib.calibrate(np.array([int(-z[1]), int(-z[1]) - 1], np.int16), *z).tolist()[0] == 0.0

@@ -7,9 +7,28 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests.helpers import REGIMES, redigitise
 from tools.simulate_reads import CAL_DIGITISATION, CAL_OFFSET, CAL_RANGE
 
 G = Path(__file__).resolve().parent / "golden"
+# a calibration for read i: the regimes in turn, one of them with more significant digits than a fast5 attribute keeps on its way
+# through Fast5Reader (6: unc_pool.cpp attr_double)
+_CALS = list(REGIMES.values()) + [(1472.3817, -7.0, 8192.0)]
+
+
+def _read_cal(i):
+    return _CALS[i % len(_CALS)]
+
+
+def _as_read(cal):
+    """the calibration Fast5Reader hands on for `cal` written into a fast5: each value as a float, printed with 6 significant digits"""
+    return tuple(float(f"{float(np.float32(x)):.6g}") for x in cal)
+
+
+def _sim_read(goldens, i, cal=None):
+    """golden simulated read i, re-digitised for `cal` (default _read_cal(i))"""
+    off = goldens["sim_offsets"]
+    return redigitise(goldens["sim_signal"][int(off[i]):int(off[i + 1])], REGIMES["minion"], cal or _read_cal(i))
 
 
 def case_chunk_class(unc):
@@ -40,8 +59,8 @@ def case_realtime_pool_ordered_replay(unc, po, example, goldens, n_reads=9):
     n_channels, chunk_len = 3, 4000
     off = goldens["sim_offsets"]
     reads = [po.calibrate(example["signal"], example["range"], example["offset"], example["digitisation"])]
-    for i in range(n_reads - 1):
-        reads.append(po.calibrate(goldens["sim_signal"][int(off[i]):int(off[i + 1])], CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION))
+    for i in range(n_reads - 1):                        # every read under a calibration of its own
+        reads.append(po.calibrate(_sim_read(goldens, i), *_read_cal(i)))
     oix = po.Index(G / "example_index" / "example_ref")
     oms = [po.Mapper(oix) for _ in range(n_channels)]
     want = {i: oms[i % n_channels].chunk_read(reads[i], chunk_len)[0] for i in range(n_reads)}
@@ -148,8 +167,9 @@ def case_oversized_chunk_is_refused(unc):
 def case_client_sim_feeds_the_decision_loop(unc, tmp_path, goldens):
     """ClientSim-shaped source over fast5 files + the enrich/deplete loop of scripts/uncalled:216-256 (uncalled_amd sim)."""
     off = goldens["sim_offsets"]
-    reads = [dict(id="sim-%d" % i, channel=1 + i % 2, number=i, start=1000 * i, range=CAL_RANGE, offset=CAL_OFFSET, digitisation=CAL_DIGITISATION,
-                  signal=goldens["sim_signal"][int(off[i]):int(off[i + 1])].tolist()) for i in range(4)]
+    cals = [_read_cal(i + 3) for i in range(4)]          # (the one with seven significant digits among them)
+    reads = [dict(id="sim-%d" % i, channel=1 + i % 2, number=i, start=1000 * i, range=cals[i][0], offset=cals[i][1], digitisation=cals[i][2],
+                  signal=_sim_read(goldens, i, cals[i]).tolist()) for i in range(4)]
     f5 = tmp_path / "reads.fast5"
     assert unc.write_fast5(str(f5), reads, True, 4000.0)
     conf = _conf(unc, 2)
@@ -160,6 +180,10 @@ def case_client_sim_feeds_the_decision_loop(unc, tmp_path, goldens):
     first = client.get_read_chunks()
     assert [(ch, c.id, c.number, c.size()) for ch, c in first] == [(1, "sim-0", 0, 4000), (2, "sim-1", 1, 4000)]
     assert first[0][1].start == 0 and first[1][1].start == 1000
+    from oracle import pyoracle as po
+    for k, (ch, c) in enumerate(first):                 # calibrated with the read's own calibration, as Fast5Reader reads it back
+        want = po.calibrate(np.array(reads[k]["signal"][:4000], dtype=np.int16), *_as_read(cals[k]))
+        assert np.array_equal(np.array(c.pop(), dtype=np.float32).view(np.uint32), want.view(np.uint32)), k
     client.stop_receiving_read(1, 0)                       # channel 1 moves on to its next read
     second = client.get_read_chunks()
     assert [(ch, c.id, c.start) for ch, c in second] == [(1, "sim-2", 2000), (2, "sim-1", 1000 + 4000)]
@@ -187,8 +211,13 @@ def case_map_pool_pipeline(unc, po, tmp_path, goldens):
     batches: every read comes out once, PAF columns as the oracle maps the same signal."""
     off = goldens["sim_offsets"]
     n = 7
-    reads = [dict(id="sim-%d" % i, channel=1 + i, number=i, start=100 * i, range=CAL_RANGE, offset=CAL_OFFSET, digitisation=CAL_DIGITISATION,
-                  signal=goldens["sim_signal"][int(off[i]):int(off[i + 1])].tolist()) for i in range(n)]
+    # a calibration per read.  Mapping hardly depends on it (the detector's t-statistics and the normaliser undo an affine map of the
+    # signal), except where event means leave [min_mean, max_mean]: each batch opens with the PromethION-like read, under whose
+    # calibration the others' samples are negative pA -- a batch staged with its first read's calibration maps them to nothing
+    mp = [REGIMES["promethion"], REGIMES["identity"], (1999.9375, 0.0, 2000.0)]       # (1999.9375: more digits than a fast5 keeps)
+    cals = [mp[i % 3] for i in range(n - 1)] + [REGIMES["minion"]]
+    reads = [dict(id="sim-%d" % i, channel=1 + i, number=i, start=100 * i, range=cals[i][0], offset=cals[i][1],
+                  digitisation=cals[i][2], signal=_sim_read(goldens, i, cals[i]).tolist()) for i in range(n)]
     assert unc.write_fast5(str(tmp_path / "a.fast5"), reads[:4], True, 4000.0)
     assert unc.write_fast5(str(tmp_path / "b.fast5"), reads[4:6], True, 4000.0)
     assert unc.write_fast5(str(tmp_path / "c.fast5"), reads[6:], True, 4000.0)
@@ -217,15 +246,19 @@ def case_map_pool_pipeline(unc, po, tmp_path, goldens):
     om = po.Mapper(oix)
     got = {l.split("\t")[0]: l.split("\t") for l in lines}
     assert sorted(got) == sorted(r["id"] for r in reads) and len(lines) == n
+    n_mapped = 0
     for i, r in enumerate(reads):
-        o = om.map_read(po.calibrate(np.array(r["signal"], dtype=np.int16), CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION))
+        o = om.map_read(po.calibrate(np.array(r["signal"], dtype=np.int16), *_as_read(cals[i])))
         want = po.hit_paf_cols(o, oix.ref_names())
         c = got[r["id"]]
         if o["mapped"]:
+            assert c[2] != "*", (r["id"], "unmapped; the oracle maps it")
             assert (int(c[1]), int(c[2]), int(c[3]), c[4], c[5], int(c[6]), int(c[7]), int(c[8]), int(c[9]), int(c[10]), int(c[11])) == want
+            n_mapped += 1
         else:
             assert int(c[1]) == want[0] and c[2] == "*"
         assert "ch:i:%d" % r["channel"] in c and "st:i:%d" % r["start"] in c
+    assert n_mapped >= n - 2
 
 
 def case_map_pool_short_of_staging_memory(unc, po, tmp_path, goldens, monkeypatch):

@@ -537,6 +537,8 @@ struct unc_mapper {
     unc_evt_info_t *d_info = nullptr; DevResult *d_results = nullptr; size_t reads_cap = 0;
     float *d_means = nullptr; size_t means_cap = 0;
     std::vector<uint64_t> h_moff;
+    std::vector<uint64_t> h_offsets;        // the caller's offsets and calibrations, copied by stage_batch: the copies to the device
+    std::vector<unc_calib_t> h_calib;       // read these, so the caller may reuse its arrays as soon as the call returns
     std::vector<unc_evt_info_t> h_info;
     std::vector<DevResult> h_results;
     // trace state
@@ -826,10 +828,16 @@ static int ensure_batch(unc_mapper *m, uint32_t n_reads, uint64_t total_samples,
     return UNC_OK;
 }
 
-// uploads metadata, returns the DevReads view
-static int stage_batch(unc_mapper *m, uint32_t n_reads, const int16_t *raw, const uint64_t *offsets, const unc_calib_t *calib,
+// uploads metadata, returns the DevReads view.  `offsets` and `calib` are copied into the mapper first and only the copies are
+// validated and handed to hipMemcpyAsync: from page-locked caller memory, or behind work queued on the stream, the copy to the device
+// runs after the call has returned, when the caller may already have reused its arrays (include/uncalled_hip.h)
+static int stage_batch(unc_mapper *m, uint32_t n_reads, const int16_t *raw, const uint64_t *caller_offsets, const unc_calib_t *caller_calib,
                        int on_device, hipStream_t st, DevReads *rd) {
     if (n_reads == 0) return fail(UNC_ERR_ARG, "empty batch");
+    m->h_offsets.assign(caller_offsets, caller_offsets + (size_t)n_reads + 1);
+    m->h_calib.assign(caller_calib, caller_calib + n_reads);
+    const uint64_t *offsets = m->h_offsets.data();
+    const unc_calib_t *calib = m->h_calib.data();
     for (uint32_t i = 0; i < n_reads; ++i) {
         if (offsets[i + 1] < offsets[i]) return fail(UNC_ERR_ARG, "offsets must be non-decreasing");
         if (offsets[i + 1] - offsets[i] >= (1ull << 31)) return fail(UNC_ERR_ARG, "read %u too long", i);
@@ -1023,7 +1031,7 @@ extern "C" int unc_map_batch_begin(unc_mapper_t *m, uint32_t n_reads, const int1
     HIPCHK(hipGetLastError());
     m->pend.active = true; m->pend.n_reads = n_reads; m->pend.grid = grid; m->pend.st = st; m->pend.rd = rd; m->pend.t1 = t1;
     m->pend.lens.resize(n_reads);
-    for (uint32_t i = 0; i < n_reads; ++i) m->pend.lens[i] = offsets[i + 1] - offsets[i];
+    for (uint32_t i = 0; i < n_reads; ++i) m->pend.lens[i] = m->h_offsets[i + 1] - m->h_offsets[i];
     return UNC_OK;
 }
 
@@ -1334,6 +1342,7 @@ extern "C" int unc_detect_events(unc_mapper_t *m, uint32_t n_reads, const int16_
                                  const unc_calib_t *calib, float *means, uint64_t means_cap, uint64_t *means_offsets,
                                  unc_evt_info_t *info) {
     if (!m || !raw || !offsets || !calib || !means || !means_offsets || !info) return fail(UNC_ERR_ARG, "null argument");
+    if (m->pend.active) return fail(UNC_ERR_ARG, "unc_detect_events: the mapper has a batch in flight (unc_map_batch_end first)");
     HIPCHK(hipSetDevice(m->ix->device));
     hipStream_t st = m->stream;
     DevReads rd;
@@ -1497,6 +1506,7 @@ extern "C" int unc_calib_chase(int device, const void *base, uint64_t bytes, uin
 // ------------------------------------------------------------------ step-wise trace of one read
 extern "C" int unc_trace_begin(unc_mapper_t *m, const int16_t *raw, uint32_t n, const unc_calib_t *calib) {
     if (!m || !raw || !calib) return fail(UNC_ERR_ARG, "null argument");
+    if (m->pend.active) return fail(UNC_ERR_ARG, "unc_trace_begin: the mapper has a batch in flight (unc_map_batch_end first)");
     HIPCHK(hipSetDevice(m->ix->device));
     hipStream_t st = m->stream;
     uint64_t offsets[2] = {0, n};
@@ -1528,6 +1538,7 @@ static int trace_reads(unc_mapper *m, DevReads *rd) {
 
 extern "C" int unc_trace_step(unc_mapper_t *m, uint32_t n_events, int *done) {
     if (!m || !m->trace_active) return fail(UNC_ERR_ARG, "no trace in progress");
+    if (m->pend.active) return fail(UNC_ERR_ARG, "unc_trace_step: the mapper has a batch in flight (unc_map_batch_end first)");
     HIPCHK(hipSetDevice(m->ix->device));
     DevReads rd;
     trace_reads(m, &rd);
