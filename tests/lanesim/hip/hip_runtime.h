@@ -246,9 +246,18 @@ static inline hipError_t hipSetDevice(int) { return 0; }
 static inline hipError_t hipGetDevice(int *d) { *d = 0; return 0; }
 static inline hipError_t hipGetDeviceCount(int *n) { *n = 1; return 0; }
 static inline hipError_t hipDeviceGetPCIBusId(char *out, int cap, int dev) { std::snprintf(out, (size_t)cap, "0000:%02X:00.0", 0xC1 + dev); return 0; }
-static inline hipError_t hipMalloc(void **p, size_t n) { *p = std::calloc(n ? n : 1, 1); return *p ? 0 : 2; }
+// what tests/test_lanesim_memory.py watches and arms (defined in lanesim.cpp, exported): the hipMalloc allocations not yet freed,
+// and a countdown -- the k-th next hipMalloc fails, 0 = never
+extern "C" int lanesim_live_allocs, lanesim_fail_malloc_in;
+static inline hipError_t hipMalloc(void **p, size_t n) {
+    *p = nullptr;
+    if (lanesim_fail_malloc_in > 0 && --lanesim_fail_malloc_in == 0) return 2;
+    *p = std::calloc(n ? n : 1, 1);
+    if (*p) ++lanesim_live_allocs;
+    return *p ? 0 : 2;
+}
 template <class T> static inline hipError_t hipMalloc(T **p, size_t n) { return hipMalloc((void **)p, n); }
-static inline hipError_t hipFree(void *p) { std::free(p); return 0; }
+static inline hipError_t hipFree(void *p) { if (p) --lanesim_live_allocs; std::free(p); return 0; }
 static inline hipError_t hipHostMalloc(void **p, size_t n, unsigned = 0) { *p = std::calloc(n ? n : 1, 1); return *p ? 0 : 2; }
 template <class T> static inline hipError_t hipHostMalloc(T **p, size_t n, unsigned f = 0) { return hipHostMalloc((void **)p, n, f); }
 static inline hipError_t hipHostFree(void *p) { std::free(p); return 0; }

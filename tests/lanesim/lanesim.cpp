@@ -1,6 +1,11 @@
 // TEST INFRASTRUCTURE -- scheduler of the lanesim CPU SIMT emulator (see hip/hip_runtime.h).
 #include <hip/hip_runtime.h>
 
+extern "C" {
+int lanesim_live_allocs = 0;
+int lanesim_fail_malloc_in = 0;
+}
+
 namespace lanesim {
 
 thread_local Block *g_blk = nullptr;

@@ -1,0 +1,145 @@
+"""Who owns the host library's device memory (uncalled_amd/csrc/unc_host.cpp), watched through the emulator's runtime: every
+hipMalloc is given back, and an allocation that fails in the middle of a growth leaves a long-lived mapper usable.  The emulator
+(tests/lanesim) counts the live allocations and can make the k-th next hipMalloc fail; the product sources know of neither."""
+import ctypes as C
+import gc
+import itertools
+
+import numpy as np
+import pytest
+
+from uncalled_amd import capi
+
+pytestmark = pytest.mark.lanesim
+
+UNC_ERR_HIP = -3     # include/uncalled_hip.h
+
+
+def _live(lib):
+    return C.c_int.in_dll(lib, "lanesim_live_allocs").value
+
+
+def _arm(lib, k):
+    """the k-th next hipMalloc fails (0: none does)"""
+    C.c_int.in_dll(lib, "lanesim_fail_malloc_in").value = k
+
+
+def _batch(example, n):
+    raw = np.tile(example["signal"], n)
+    off = np.arange(n + 1, dtype=np.uint64) * example["signal"].size
+    return raw, off, capi.make_calib(n, example["range"], example["offset"], example["digitisation"])
+
+
+def _chunk(example, read_number, n_samples):
+    """the first chunk of a new read on channel 0"""
+    ch = np.zeros(1, dtype=capi.RT_CHUNK)
+    ch["channel"], ch["read_number"], ch["flags"], ch["n_samples"], ch["offset"] = 0, read_number, capi.RT_FIRST, n_samples, 0
+    ch["calib"] = capi.make_calib(1, example["range"], example["offset"], example["digitisation"])[0]
+    return ch
+
+
+def _same(a, b):
+    return all(np.array_equal(a[f], b[f]) for f in capi.RESULT_FIELDS)
+
+
+def test_everything_is_given_back(sim_lib, example):
+    """Every entry point that allocates device memory, once, and a unc_mapper_create that fails after its slots and its node pool
+    exist: when everything is freed, no allocation is left."""
+    gc.collect()
+    start = _live(sim_lib)
+    ix = capi.Index(example["prefix"], lib=sim_lib)
+    assert _live(sim_lib) > start
+    m = capi.Mapper(ix, n_slots=2, n_waves=2)
+    raw, off, cal = _batch(example, 2)
+    first = m.map_batch(raw, off, cal)
+    assert first[0]["mapped"] and _same(first[0], first[1])
+    m.set_read_order(capi.ORDER_T1)
+    assert _same(m.map_batch(raw, off, cal), first)
+    m.set_read_order(capi.ORDER_INDEPENDENT)
+    mt = capi.Mapper(ix, n_slots=2, n_waves=2)       # (a trace reads slot 0 as a new mapper leaves it: a mapper of its own)
+    assert len(list(itertools.islice(mt.trace(example["signal"], cal[:1]), 3))) == 3
+    mt.trace_finish()
+    rt = capi.Realtime(ix, n_channels=1)
+    assert rt.process_chunks(_chunk(example, 1, 1000), raw_i16=example["signal"])[0]["state"] == capi.RT_MAPPING
+    text = np.random.default_rng(5).integers(0, 4, size=300).astype(np.uint8)
+    sa = capi.build_suffix_array(text, 0, sim_lib)
+    assert sorted(sa.tolist()) == list(range(300))
+    keys = np.random.default_rng(6).integers(0, 1 << 40, size=500, dtype=np.uint64)
+    assert np.array_equal(capi.sort_pairs(keys, key_bits=40, lib=sim_lib)[0], np.sort(keys))
+    a = np.zeros(6, dtype=np.uint64)
+    sim_lib.unc_mapper_device_addresses.argtypes = [C.c_void_p, C.c_void_p]
+    sim_lib.unc_calib_chase.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+    assert sim_lib.unc_mapper_device_addresses(m.h, a.ctypes.data) == 0
+    ms = C.c_float(-1.0)
+    assert sim_lib.unc_calib_chase(0, int(a[0]), int(a[1]) * 2, 2, 16, C.byref(ms)) == 0 and ms.value >= 0.0
+    # (five slots on two wavefronts want the sliced scheduler, whose seven parts do not divide them: refused after the slots and the pool)
+    before = _live(sim_lib)
+    with pytest.raises(capi.UncalledHipError, match="sched_parts"):
+        capi.Mapper(ix, n_slots=5, n_waves=2, sched_parts=7)
+    assert _live(sim_lib) == before
+    rt.close()
+    mt.close()
+    m.close()
+    ix.close()
+    assert _live(sim_lib) == start
+
+
+def test_failed_growth_leaves_the_mapper_usable(sim_lib, example):
+    """A batch (a chunk round) larger than the last one grows the mapper's buffers.  Whichever of the growth's allocations fails, the
+    call returns UNC_ERR_HIP and the mapper goes on mapping what it mapped before, with the same answer.
+
+    Before the buffers owned their capacity this case wrote through a null pointer for some k: the buffers were freed and set to null,
+    and the capacity beside them kept its old value when an allocation failed, so that the next smaller batch skipped the growth.
+
+    (A chunk round has ONE allocation that grows -- the raw signal --, so there is one k to fail on the chunked path; a batch has
+    seven: the raw signal, the five per-read arrays and the event means.)"""
+    gc.collect()
+    start = _live(sim_lib)
+    ix = capi.Index(example["prefix"], lib=sim_lib)
+    # (a pool of a given size: pool_fit, whose failed resizes are swallowed by design, stays out of the way)
+    m = capi.Mapper(ix, n_slots=2, n_waves=2, pool_chunks=16)
+    raw1, off1, cal1 = _batch(example, 1)
+    raw2, off2, cal2 = _batch(example, 2)
+    hits2 = np.zeros(2, dtype=capi.HIT)
+    first = m.map_batch(raw1, off1, cal1)
+    assert first[0]["mapped"]
+    failed = 0
+    for k in itertools.count(1):
+        assert k < 100
+        _arm(sim_lib, k)
+        rc = sim_lib.unc_map_batch(m.h, 2, raw2.ctypes.data, off2.ctypes.data, cal2.ctypes.data, 0, None, hits2.ctypes.data)
+        _arm(sim_lib, 0)
+        if rc == 0:
+            break
+        assert rc == UNC_ERR_HIP, (k, rc, sim_lib.unc_last_error())
+        failed += 1
+        assert _same(m.map_batch(raw1, off1, cal1), first), k
+    assert failed >= 3
+    assert _same(hits2[0], first[0]) and _same(hits2[1], first[0])
+
+    rt = capi.Realtime(ix, n_channels=1)
+    sig = np.ascontiguousarray(example["signal"], dtype=np.int16)
+    assert sig.size >= 3000
+    res = np.zeros(1, dtype=capi.RT_RESULT)
+    short = rt.process_chunks(_chunk(example, 1, 1000), raw_i16=sig)
+    assert short[0]["state"] == capi.RT_MAPPING
+    failed = 0
+    for k in itertools.count(1):
+        assert k < 100
+        long_chunk = _chunk(example, 2 * k, 3000)
+        _arm(sim_lib, k)
+        rc = sim_lib.unc_rt_process_chunks(rt.h, 1, long_chunk.ctypes.data, sig.ctypes.data, 0, None, res.ctypes.data)
+        _arm(sim_lib, 0)
+        if rc == 0:
+            break
+        assert rc == UNC_ERR_HIP, (k, rc, sim_lib.unc_last_error())
+        failed += 1
+        again = rt.process_chunks(_chunk(example, 2 * k + 1, 1000), raw_i16=sig)
+        assert again[0]["state"] == short[0]["state"] and _same(again[0]["hit"], short[0]["hit"]), k
+    assert failed >= 1
+    assert res[0]["state"] in (capi.RT_MAPPING, capi.RT_MAPPED)
+
+    rt.close()
+    m.close()
+    ix.close()
+    assert _live(sim_lib) == start

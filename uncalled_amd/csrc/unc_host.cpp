@@ -16,6 +16,7 @@
 #include <array>
 #include <map>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "r94_model_table.h"
@@ -68,6 +69,38 @@ extern "C" void unc_params_default(unc_params_t *p) {
     p->bp_per_sec = 450.0f; p->sample_rate = 4000.0f; p->chunk_time = 1.0f; p->max_chunks = 1000000;
 }
 
+// ------------------------------------------------------------------ device memory
+// The one owner of device memory in this file (PlacementSpacer apart, which holds untyped memory for a moment).  Pointer and capacity
+// travel together: p == nullptr exactly when cap == 0; the destructor frees; a move leaves the source empty.  `cap` counts the elements
+// the holder may use; `slack` more elements may lie behind them that belong to the allocation and not to the capacity (the raw signal's
+// 64 samples past the end).
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // a fresh allocation of (n + slack) * sizeof(T) bytes (n == 0: one element); whatever was held is freed first
+    hipError_t alloc(size_t n, size_t slack = 0) {
+        release();
+        if (!n) n = 1;
+        const hipError_t e = hipMalloc((void **)&p, (n + slack) * sizeof(T));
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = n;
+        return hipSuccess;
+    }
+    // grows only.  A growth that fails leaves the buffer EMPTY (cap 0), never a capacity without memory behind it: the next call
+    // allocates again
+    hipError_t reserve(size_t n, size_t slack = 0) { return n <= cap ? hipSuccess : alloc(n, slack); }
+};
+
 // ------------------------------------------------------------------ index
 struct SeqAnn { std::string name; uint64_t offset, len; };
 
@@ -81,14 +114,14 @@ struct unc_index {
     std::vector<float> model;                // [3][1024] host copy
     float model_mean = 0, model_stdv = 0;
     // device
-    uint32_t *d_bwt = nullptr;
-    uint64_t *d_sa = nullptr;
-    uint64_t *d_kmer_ranges = nullptr;
-    float *d_model = nullptr;
-    uint16_t *d_kmer_valid = nullptr;
-    uint64_t *d_sa_dense = nullptr;
-    uint32_t *d_fm32 = nullptr;
-    float *d_model4 = nullptr;
+    DevBuf<uint32_t> d_bwt;
+    DevBuf<uint64_t> d_sa;
+    DevBuf<uint64_t> d_kmer_ranges;
+    DevBuf<float> d_model;
+    DevBuf<uint16_t> d_kmer_valid;
+    DevBuf<char> d_sa_dense;                 // 6-byte entries in pairs (fm_dev.h); the kernels take it as uint64_t *
+    DevBuf<uint32_t> d_fm32;
+    DevBuf<float> d_model4;
     uint64_t device_bytes = 0;
     DevIndex dev;
 };
@@ -181,14 +214,6 @@ static int parse_ann(const std::string &fn, unc_index *ix) {
 extern "C" void unc_index_free(unc_index_t *ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
-    if (ix->d_bwt) (void)hipFree(ix->d_bwt);
-    if (ix->d_sa) (void)hipFree(ix->d_sa);
-    if (ix->d_kmer_ranges) (void)hipFree(ix->d_kmer_ranges);
-    if (ix->d_model) (void)hipFree(ix->d_model);
-    if (ix->d_kmer_valid) (void)hipFree(ix->d_kmer_valid);
-    if (ix->d_sa_dense) (void)hipFree(ix->d_sa_dense);
-    if (ix->d_fm32) (void)hipFree(ix->d_fm32);
-    if (ix->d_model4) (void)hipFree(ix->d_model4);
     delete ix;
 }
 
@@ -265,29 +290,29 @@ extern "C" int unc_index_load(const char *bwa_prefix, const char *idx_preset, in
     const size_t bwt_bytes = ((n_words * 4 + 63) / 64 + 1) * 64;
     // (the index's tables are read at random by every FM step: allocated behind a spacer like the mapper's slots -- PlacementSpacer)
     PlacementSpacer spacer(bwt_bytes + n_sa * 8 + ((size_t)n_words * 16 + 2) / 2 * 12 + (size_t)n_words * 2 + (64u << 20));
-    HIPCHK(hipMalloc((void **)&ix->d_bwt, bwt_bytes));
-    HIPCHK(hipMemset(ix->d_bwt, 0, bwt_bytes));
-    HIPCHK(hipMemcpy(ix->d_bwt, bwt.data() + 40, n_words * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&ix->d_sa, n_sa * 8));
+    HIPCHK(ix->d_bwt.alloc(bwt_bytes / 4));
+    HIPCHK(hipMemset(ix->d_bwt.p, 0, bwt_bytes));
+    HIPCHK(hipMemcpy(ix->d_bwt.p, bwt.data() + 40, n_words * 4, hipMemcpyHostToDevice));
+    HIPCHK(ix->d_sa.alloc(n_sa));
     {
         std::vector<uint64_t> h(n_sa);
         h[0] = ~0ull;   // bwt_restore_sa: sa[0] = -1
         memcpy(h.data() + 1, sa.data() + 56, (n_sa - 1) * 8);
-        HIPCHK(hipMemcpy(ix->d_sa, h.data(), n_sa * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ix->d_sa.p, h.data(), n_sa * 8, hipMemcpyHostToDevice));
     }
-    HIPCHK(hipMalloc((void **)&ix->d_kmer_ranges, 2 * NKMER * 8));
-    HIPCHK(hipMalloc((void **)&ix->d_model, 3 * NKMER * 4));
-    HIPCHK(hipMemcpy(ix->d_model, ix->model.data(), 3 * NKMER * 4, hipMemcpyHostToDevice));
+    HIPCHK(ix->d_kmer_ranges.alloc(2 * NKMER));
+    HIPCHK(ix->d_model.alloc(3 * NKMER));
+    HIPCHK(hipMemcpy(ix->d_model.p, ix->model.data(), 3 * NKMER * 4, hipMemcpyHostToDevice));
     {
         std::vector<float> m4(4 * NKMER, 0.0f);
         for (int k = 0; k < NKMER; ++k) { m4[4 * k] = ix->model[k]; m4[4 * k + 1] = ix->model[NKMER + k]; m4[4 * k + 2] = ix->model[2 * NKMER + k]; }
-        HIPCHK(hipMalloc((void **)&ix->d_model4, 4 * NKMER * 4));
-        HIPCHK(hipMemcpy(ix->d_model4, m4.data(), 4 * NKMER * 4, hipMemcpyHostToDevice));
+        HIPCHK(ix->d_model4.alloc(4 * NKMER));
+        HIPCHK(hipMemcpy(ix->d_model4.p, m4.data(), 4 * NKMER * 4, hipMemcpyHostToDevice));
     }
     ix->device_bytes = bwt_bytes + n_sa * 8 + 2 * NKMER * 8 + 3 * NKMER * 4;
 
     DevIndex &d = ix->dev;
-    d.bwt = ix->d_bwt; d.sa = ix->d_sa; d.kmer_ranges = ix->d_kmer_ranges; d.model = ix->d_model; d.model4 = ix->d_model4;
+    d.bwt = ix->d_bwt.p; d.sa = ix->d_sa.p; d.kmer_ranges = ix->d_kmer_ranges.p; d.model = ix->d_model.p; d.model4 = ix->d_model4.p;
     d.primary = ix->primary; d.seq_len = n;
     for (int i = 0; i < 5; ++i) d.L2[i] = ix->L2[i];
     memcpy(d.thresholds, ix->thresholds, sizeof d.thresholds);
@@ -302,21 +327,22 @@ extern "C" int unc_index_load(const char *bwa_prefix, const char *idx_preset, in
         free_b += spacer.bytes;
         const size_t need = ((n + 2) / 2) * 12 + 16;      // rows 0 .. n in pairs (12 bytes) + the word a load reads past the last entry
         if (!(env && env[0] == '0') && need < free_b / 2) {
-            HIPCHK(hipMalloc((void **)&ix->d_sa_dense, need));
-            launch_dense_sa(d, ix->d_sa_dense, nullptr);
+            HIPCHK(ix->d_sa_dense.alloc(need));
+            uint64_t *const dense = reinterpret_cast<uint64_t *>(ix->d_sa_dense.p);
+            launch_dense_sa(d, dense, nullptr);
             HIPCHK(hipGetLastError());
             HIPCHK(hipDeviceSynchronize());
             {   // self-check: 16 384 rows spread over the whole table (the last row included) against the BWA-format walk
-                uint32_t *d_bad = nullptr, bad = 0;
-                HIPCHK(hipMalloc((void **)&d_bad, 4));
-                HIPCHK(hipMemset(d_bad, 0, 4));
-                launch_dense_sa_check(d, ix->d_sa_dense, 16384, d_bad, nullptr);
+                DevBuf<uint32_t> d_bad;
+                uint32_t bad = 0;
+                HIPCHK(d_bad.alloc(1));
+                HIPCHK(hipMemset(d_bad.p, 0, 4));
+                launch_dense_sa_check(d, dense, 16384, d_bad.p, nullptr);
                 HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
-                (void)hipFree(d_bad);
+                HIPCHK(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
                 if (bad) return fail(UNC_ERR_HIP, "dense SA self-check failed on %u of 16384 probe rows", bad);
             }
-            d.sa_dense = ix->d_sa_dense;
+            d.sa_dense = dense;
             ix->device_bytes += need;
         }
     }
@@ -326,27 +352,27 @@ extern "C" int unc_index_load(const char *bwa_prefix, const char *idx_preset, in
     d.fm32 = nullptr;
     if (n < 0xFFFFFF00ull) {
         const uint32_t n_blk = (uint32_t)((n + 63) / 64 + 1);
-        HIPCHK(hipMalloc((void **)&ix->d_fm32, (size_t)n_blk * 32));
-        launch_build_fm32(d, ix->d_fm32, n_blk, nullptr);
+        HIPCHK(ix->d_fm32.alloc((size_t)n_blk * 8));
+        launch_build_fm32(d, ix->d_fm32.p, n_blk, nullptr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipDeviceSynchronize());
-        d.fm32 = ix->d_fm32;
-        uint32_t *d_bad = nullptr, bad = 0;
-        HIPCHK(hipMalloc((void **)&d_bad, 4));
-        HIPCHK(hipMemset(d_bad, 0, 4));
-        launch_fm32_check(d, 16384, d_bad, nullptr);
-        const hipError_t e1 = hipGetLastError(), e2 = hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost);
-        (void)hipFree(d_bad);
-        HIPCHK(e1); HIPCHK(e2);
+        d.fm32 = ix->d_fm32.p;
+        DevBuf<uint32_t> d_bad;
+        uint32_t bad = 0;
+        HIPCHK(d_bad.alloc(1));
+        HIPCHK(hipMemset(d_bad.p, 0, 4));
+        launch_fm32_check(d, 16384, d_bad.p, nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
         if (bad) return fail(UNC_ERR_HIP, "32-bit rank table self-check failed on %u of 16384 probe steps", bad);
         ix->device_bytes += (size_t)n_blk * 32;
     }
     // the 1024 k-mer ranges, derived on the device exactly as BwaIndex::load_index does (bwa_index.hpp:124-132)
-    launch_kmer_ranges(d, ix->d_kmer_ranges, nullptr);
+    launch_kmer_ranges(d, ix->d_kmer_ranges.p, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     ix->kmer_ranges.resize(2 * NKMER);
-    HIPCHK(hipMemcpy(ix->kmer_ranges.data(), ix->d_kmer_ranges, 2 * NKMER * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ix->kmer_ranges.data(), ix->d_kmer_ranges.p, 2 * NKMER * 8, hipMemcpyDeviceToHost));
     for (int k = 0; k < NKMER; ++k) {
         uint64_t s = ix->kmer_ranges[2 * k], e = ix->kmer_ranges[2 * k + 1];
         if (s <= e && e - s + 1 >= (1ull << KEY_LEN_BITS)) return fail(UNC_ERR_ARG, "k-mer %d occurs more than 2^30 times: unsupported", k);
@@ -387,9 +413,9 @@ extern "C" int unc_index_load(const char *bwa_prefix, const char *idx_preset, in
                 if (ix->kmer_ranges[2 * k] <= ix->kmer_ranges[2 * k + 1]) valid[l] |= (uint16_t)(1u << j);
             }
         }
-        HIPCHK(hipMalloc((void **)&ix->d_kmer_valid, sizeof valid));
-        HIPCHK(hipMemcpy(ix->d_kmer_valid, valid, sizeof valid, hipMemcpyHostToDevice));
-        ix->dev.kmer_valid = ix->d_kmer_valid;
+        HIPCHK(ix->d_kmer_valid.alloc(WAVE));
+        HIPCHK(hipMemcpy(ix->d_kmer_valid.p, valid, sizeof valid, hipMemcpyHostToDevice));
+        ix->dev.kmer_valid = ix->d_kmer_valid.p;
     }
     guard.p = nullptr;
     *out = ix;
@@ -436,16 +462,6 @@ extern "C" void unc_index_model_tables(const unc_index_t *ix, float *mu, float *
     *ms = ix->model_stdv;
 }
 
-template <class T> struct DevBuf;
-extern "C" int unc_self_align(const unc_index_t *ix, const char *bwa_prefix, uint32_t sample_dist, uint32_t cap, uint64_t *lens,
-                              uint32_t *full_len, uint64_t max_paths, uint64_t *n_paths);
-
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)); }
-};
-
 extern "C" int unc_fm_get_neighbor(const unc_index_t *ix, uint32_t n, const uint64_t *starts, const uint64_t *ends,
                                    const uint8_t *bases, uint64_t *out_s, uint64_t *out_e) {
     HIPCHK(hipSetDevice(ix->device));
@@ -488,12 +504,19 @@ extern "C" int unc_match_probs(const unc_index_t *ix, uint32_t n, const float *l
 }
 
 // ------------------------------------------------------------------ mapper
+// DevScratch, DevPool and DevSched are the plain views the kernels take by value (unc_dev_types.h); the host keeps each beside the
+// buffers it points into.  Moving an owner moves its buffers (the source is then good for nothing but its destructor); assigning an
+// empty one frees them and clears the view.
+struct Scratch { DevBuf<char> mem; DevScratch v{}; };
+struct Pool { DevBuf<char> nodes; DevBuf<PoolQueue> q; DevBuf<SchedCell> cells; DevPool v{}; };
+struct Sched { DevBuf<SchedCtl> ctl; DevBuf<SchedCell> free_cells, park_cells; DevSched v{}; };
+
 struct unc_mapper {
     const unc_index *ix = nullptr;
     unc_params_t P;
     uint32_t n_slots = 0, n_waves = 0, slice_events = 1024, ev_rpw = 64;
-    DevSched sched{};             // ctl != null: sliced batch scheduler (n_slots > n_waves)
-    DevScratch sc;
+    Sched sched;                  // ctl != null: sliced batch scheduler (n_slots > n_waves)
+    Scratch sc;
     uint64_t device_bytes = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -502,7 +525,7 @@ struct unc_mapper {
     double wave_busy = 0;          // mean wave lifetime / k_map duration of the last batch (1 = no queue tail)
     float wall_khz = 0;            // device wall clock rate (ticks per ms)
     bool profile = false;          // launch the instantiation of k_map that counts cycles per phase
-    DevPool pool{};                // nodes of the seed-cluster grids, shared by every read in flight
+    Pool pool;                     // nodes of the seed-cluster grids, shared by every read in flight
     // the pool is sized by NEED: created by a rule of thumb, cut to four times the most chunks that were ever out at once when it
     // holds more than eight times that, doubled when found dry (pool_fit, unc_mapper_pool_usage); a caller who named pool_chunks
     // keeps that number
@@ -517,25 +540,24 @@ struct unc_mapper {
         bool t1 = false;
         std::vector<uint64_t> lens;      // samples per read (fill_hit)
     } pend;
-    DevScratch big{};              // scratch with a larger node allowance for the reads that outgrew a slot's (kept between batches)
-    uint64_t big_cap = 0;
+    Scratch big;                   // scratch with a larger node allowance for the reads that outgrew a slot's (kept between batches)
     size_t big_slots = 0;
     bool big_at_limit = false;     // big_slots is all the free HBM allowed
-    uint32_t *d_list = nullptr; size_t list_cap = 0;     // read ids of a re-map round
+    DevBuf<uint32_t> d_list;       // read ids of a re-map round
     uint32_t remap_reads = 0;      // reads of the last batch that were mapped again with more room, and what that cost
     float remap_ms = 0;
     // read order UNC_ORDER_T1 (unc_mapper_set_read_order): sources_added_ travels from a read to the next one, across batches
     int read_order = 0;
-    uint32_t *d_flags_in = nullptr, *d_flags_out = nullptr; size_t flags_cap = 0;
+    DevBuf<uint32_t> d_flags_in, d_flags_out;
     uint32_t carry_flags[NKMER / 32] = {0};     // what the last read of the previous batch left set
     uint32_t carry_reads = 0, carry_rounds = 0; // reads of the last batch mapped again because their predecessor left flags set
     float carry_ms = 0;
-    uint32_t *d_next = nullptr;
+    DevBuf<uint32_t> d_next;
     // per-batch buffers (grown on demand)
-    int16_t *d_raw = nullptr; size_t raw_cap = 0;
-    uint64_t *d_offsets = nullptr; uint64_t *d_moff = nullptr; unc_calib_t *d_calib = nullptr;
-    unc_evt_info_t *d_info = nullptr; DevResult *d_results = nullptr; size_t reads_cap = 0;
-    float *d_means = nullptr; size_t means_cap = 0;
+    DevBuf<int16_t> d_raw;         // capacity in samples; 64 more lie behind them
+    DevBuf<uint64_t> d_offsets, d_moff; DevBuf<unc_calib_t> d_calib;      // the five per-read arrays grow together (ensure_batch)
+    DevBuf<unc_evt_info_t> d_info; DevBuf<DevResult> d_results;
+    DevBuf<float> d_means;
     std::vector<uint64_t> h_moff;
     std::vector<uint64_t> h_offsets;        // the caller's offsets and calibrations, copied by stage_batch: the copies to the device
     std::vector<unc_calib_t> h_calib;       // read these, so the caller may reuse its arrays as soon as the call returns
@@ -545,11 +567,6 @@ struct unc_mapper {
     uint32_t trace_n = 0;
     bool trace_active = false;
 };
-
-static void free_scratch(DevScratch &sc) {
-    if (sc.base) (void)hipFree(sc.base);
-    memset(&sc, 0, sizeof sc);
-}
 
 // Regions of one slot (DevScratch), each 256-byte aligned; everything below 4 GB so that kernels address a slot as
 // uniform base + 32-bit offset.
@@ -592,22 +609,18 @@ static uint64_t scratch_slot_bytes(const unc_params_t &P, uint32_t max_clusters,
     return scratch_layout(t, P, max_clusters, max_seed_paths, dix) == UNC_OK ? t.slot_bytes : ~0ull;
 }
 
-static int alloc_scratch(DevScratch &sc, const unc_params_t &P, size_t n_slots, uint32_t max_clusters, uint32_t max_seed_paths,
+static int alloc_scratch(Scratch &s, const unc_params_t &P, size_t n_slots, uint32_t max_clusters, uint32_t max_seed_paths,
                          size_t *bytes_out, const DevIndex &dix) {
+    DevScratch &sc = s.v;
     int rc = scratch_layout(sc, P, max_clusters, max_seed_paths, dix);
     if (rc) return rc;
     const size_t bytes = (size_t)n_slots * sc.slot_bytes;
-    HIPCHK(hipMalloc((void **)&sc.base, bytes));
+    HIPCHK(s.mem.alloc(bytes));
+    sc.base = s.mem.p;
     // SlotState of every slot starts zeroed (done = 0, nothing parked)
     HIPCHK(hipMemset2D(sc.base + sc.off_state, sc.slot_bytes, 0, sizeof(SlotState), n_slots));
     if (bytes_out) *bytes_out = bytes;
     return UNC_OK;
-}
-
-static void free_pool(DevPool &p) {
-    void *ptrs[] = {p.nodes, p.q, p.cells};
-    for (void *x : ptrs) if (x) (void)hipFree(x);
-    memset(&p, 0, sizeof p);
 }
 
 // XCDs of a device: workgroups of a small grid report the XCD they run on (hardware register), the distinct answers are counted; once
@@ -619,34 +632,34 @@ static uint32_t xcd_count(int device) {
     auto it = known.find(device);
     if (it != known.end()) return it->second;
     uint32_t n = 1;
-    uint32_t *d = nullptr;
+    DevBuf<uint32_t> d;
     constexpr uint32_t NB = 256;
-    if (hipMalloc((void **)&d, NB * sizeof(uint32_t)) == hipSuccess) {
+    if (d.alloc(NB) == hipSuccess) {
         uint32_t h[NB];
-        launch_xcd_probe(d, NB, nullptr);
-        if (hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
+        launch_xcd_probe(d.p, NB, nullptr);
+        if (hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
             uint32_t seen = 0;
             for (uint32_t i = 0; i < NB; ++i) seen |= 1u << (h[i] & 15u);
             n = (uint32_t)__builtin_popcount(seen);
             // the ids must be 0 .. n - 1 (sched_part takes the id modulo n_parts)
             if (seen != (n >= 32 ? ~0u : (1u << n) - 1u)) n = 1;
         }
-        (void)hipFree(d);
     }
     (void)hipGetLastError();
     known[device] = n;
     return n;
 }
 
-static int alloc_pool(DevPool &p, uint32_t n_chunks, size_t *bytes_out) {
-    memset(&p, 0, sizeof p);
+static int alloc_pool(Pool &p, uint32_t n_chunks, size_t *bytes_out) {
+    p = Pool{};
     uint32_t cap = 64;
     while (cap < n_chunks) cap <<= 1;
-    p.cap_mask = cap - 1; p.n_chunks = n_chunks;
-    HIPCHK(hipMalloc((void **)&p.nodes, (size_t)n_chunks * POOL_CHUNK_BYTES));
-    HIPCHK(hipMalloc((void **)&p.q, sizeof(PoolQueue)));
-    HIPCHK(hipMalloc((void **)&p.cells, (size_t)cap * sizeof(SchedCell)));
-    launch_pool_init(p, nullptr);
+    p.v.cap_mask = cap - 1; p.v.n_chunks = n_chunks;
+    HIPCHK(p.nodes.alloc((size_t)n_chunks * POOL_CHUNK_BYTES));
+    HIPCHK(p.q.alloc(1));
+    HIPCHK(p.cells.alloc(cap));
+    p.v.nodes = p.nodes.p; p.v.q = p.q.p; p.v.cells = p.cells.p;
+    launch_pool_init(p.v, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     if (bytes_out) *bytes_out += (size_t)n_chunks * POOL_CHUNK_BYTES + (size_t)cap * sizeof(SchedCell);
@@ -658,12 +671,6 @@ static SlotState *slot_state(const DevScratch &sc, size_t slot) { return reinter
 extern "C" void unc_mapper_free(unc_mapper_t *m) {
     if (!m) return;
     (void)hipSetDevice(m->ix->device);
-    free_scratch(m->sc);
-    free_scratch(m->big);
-    void *ptrs[] = {m->d_next, m->d_raw, m->d_offsets, m->d_moff, m->d_calib, m->d_info, m->d_results, m->d_means,
-                    m->sched.ctl, m->sched.free_cells, m->sched.park_cells, m->d_list, m->d_flags_in, m->d_flags_out};
-    free_pool(m->pool);
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &e : m->ev) if (e) (void)hipEventDestroy(e);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
@@ -696,7 +703,6 @@ extern "C" int unc_mapper_create(const unc_index_t *ix, const unc_params_t *p, c
     struct Guard { unc_mapper *p; ~Guard() { if (p) unc_mapper_free(p); } } guard{m};
     m->ix = ix;
     m->P = *p;
-    memset(&m->sc, 0, sizeof m->sc);
     uint32_t n_slots = opts ? opts->n_slots : 0, n_waves = opts ? opts->n_waves : 0;
     if (n_waves == 0) {
         hipDeviceProp_t prop;
@@ -737,7 +743,7 @@ extern "C" int unc_mapper_create(const unc_index_t *ix, const unc_params_t *p, c
     PlacementSpacer spacer((size_t)n_slots * scratch_slot_bytes(*p, mcl, msp, ix->dev) + pool_want);
     int rc_ = alloc_scratch(m->sc, *p, n_slots, mcl, msp, &bytes, ix->dev);
     if (rc_) return rc_;
-    HIPCHK(hipMalloc((void **)&m->d_next, 64));
+    HIPCHK(m->d_next.alloc(16));
     {
         // the pool of cluster nodes: 8 chunks (1.5 MB, 6144 nodes) per read in flight on average, 64 on references of 2^26
         // index rows and more, where a read touches thousands of buckets and off-target reads collect hundreds of thousands
@@ -778,10 +784,11 @@ extern "C" int unc_mapper_create(const unc_index_t *ix, const unc_params_t *p, c
         const uint32_t spp = n_slots / parts;
         uint32_t cap = 64;
         while (cap < spp) cap <<= 1;
-        m->sched.cap_mask = cap - 1; m->sched.n_slots = n_slots; m->sched.n_parts = parts;
-        HIPCHK(hipMalloc((void **)&m->sched.ctl, sizeof(SchedCtl)));
-        HIPCHK(hipMalloc((void **)&m->sched.free_cells, (size_t)parts * cap * sizeof(SchedCell)));
-        HIPCHK(hipMalloc((void **)&m->sched.park_cells, (size_t)parts * cap * sizeof(SchedCell)));
+        m->sched.v.cap_mask = cap - 1; m->sched.v.n_slots = n_slots; m->sched.v.n_parts = parts;
+        HIPCHK(m->sched.ctl.alloc(1));
+        HIPCHK(m->sched.free_cells.alloc((size_t)parts * cap));
+        HIPCHK(m->sched.park_cells.alloc((size_t)parts * cap));
+        m->sched.v.ctl = m->sched.ctl.p; m->sched.v.free_cells = m->sched.free_cells.p; m->sched.v.park_cells = m->sched.park_cells.p;
         bytes += sizeof(SchedCtl) + 2 * (size_t)parts * cap * sizeof(SchedCell);
     }
     m->device_bytes = bytes;
@@ -801,30 +808,19 @@ extern "C" int unc_mapper_create(const unc_index_t *ix, const unc_params_t *p, c
 extern "C" uint64_t unc_mapper_device_bytes(const unc_mapper_t *m) { return m->device_bytes; }
 
 static int ensure_batch(unc_mapper *m, uint32_t n_reads, uint64_t total_samples, bool need_raw) {
-    if (need_raw && total_samples > m->raw_cap) {
-        if (m->d_raw) (void)hipFree(m->d_raw);
-        m->d_raw = nullptr;
-        HIPCHK(hipMalloc((void **)&m->d_raw, (total_samples + 64) * 2));
-        m->raw_cap = total_samples;
-    }
-    if (n_reads > m->reads_cap) {
-        void *ptrs[] = {m->d_offsets, m->d_moff, m->d_calib, m->d_info, m->d_results};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-        m->d_offsets = m->d_moff = nullptr; m->d_calib = nullptr; m->d_info = nullptr; m->d_results = nullptr;
-        HIPCHK(hipMalloc((void **)&m->d_offsets, ((size_t)n_reads + 1) * 8));
-        HIPCHK(hipMalloc((void **)&m->d_moff, ((size_t)n_reads + 1) * 8));
-        HIPCHK(hipMalloc((void **)&m->d_calib, (size_t)n_reads * sizeof(unc_calib_t)));
-        HIPCHK(hipMalloc((void **)&m->d_info, (size_t)n_reads * sizeof(unc_evt_info_t)));
-        HIPCHK(hipMalloc((void **)&m->d_results, (size_t)n_reads * sizeof(DevResult)));
-        m->reads_cap = n_reads;
+    if (need_raw) HIPCHK(m->d_raw.reserve(total_samples, 64));
+    // the five per-read arrays: all freed, then all allocated (the order the runtime has always seen).  d_results comes last, so
+    // its capacity is that of all five: after a growth that failed half way it is 0 and the next batch allocates again
+    if (n_reads > m->d_results.cap) {
+        m->d_offsets.release(); m->d_moff.release(); m->d_calib.release(); m->d_info.release(); m->d_results.release();
+        HIPCHK(m->d_offsets.alloc((size_t)n_reads + 1));
+        HIPCHK(m->d_moff.alloc((size_t)n_reads + 1));
+        HIPCHK(m->d_calib.alloc(n_reads));
+        HIPCHK(m->d_info.alloc(n_reads));
+        HIPCHK(m->d_results.alloc(n_reads));
     }
     const uint64_t means_need = total_samples / 8 * 5 + 24ull * n_reads + 16;      // (>= the sum of the reads' rooms, stage_batch)
-    if (means_need > m->means_cap) {
-        if (m->d_means) (void)hipFree(m->d_means);
-        m->d_means = nullptr;
-        HIPCHK(hipMalloc((void **)&m->d_means, means_need * 4));
-        m->means_cap = means_need;
-    }
+    HIPCHK(m->d_means.reserve(means_need));
     return UNC_OK;
 }
 
@@ -855,16 +851,16 @@ static int stage_batch(unc_mapper *m, uint32_t n_reads, const int16_t *raw, cons
         for (uint32_t i = 0; i < n_reads; ++i) { m->h_moff[i] = acc; acc += (offsets[i + 1] - offsets[i]) / 8 * 5 + 16; }
         m->h_moff[n_reads] = acc;
     }
-    HIPCHK(hipMemcpyAsync(m->d_offsets, offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(m->d_moff, m->h_moff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(m->d_calib, calib, (size_t)n_reads * sizeof(unc_calib_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(m->d_offsets.p, offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(m->d_moff.p, m->h_moff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(m->d_calib.p, calib, (size_t)n_reads * sizeof(unc_calib_t), hipMemcpyHostToDevice, st));
     const int16_t *d_raw = raw;
     if (!on_device) {
-        HIPCHK(hipMemcpyAsync(m->d_raw, raw + base, total * 2, hipMemcpyHostToDevice, st));
-        d_raw = m->d_raw - base;   // kernels index raw[offsets[i]..]
+        HIPCHK(hipMemcpyAsync(m->d_raw.p, raw + base, total * 2, hipMemcpyHostToDevice, st));
+        d_raw = m->d_raw.p - base;   // kernels index raw[offsets[i]..]
     }
-    rd->raw = d_raw; rd->offsets = m->d_offsets; rd->calib = m->d_calib; rd->means = m->d_means; rd->moff = m->d_moff;
-    rd->info = m->d_info; rd->n_reads = n_reads;
+    rd->raw = d_raw; rd->offsets = m->d_offsets.p; rd->calib = m->d_calib.p; rd->means = m->d_means.p; rd->moff = m->d_moff.p;
+    rd->info = m->d_info.p; rd->n_reads = n_reads;
     rd->tgt_mean = m->ix->model_mean; rd->tgt_stdv = m->ix->model_stdv;
     rd->ring0 = nullptr; rd->new_read = nullptr; rd->ring_mod = 0;
     return UNC_OK;
@@ -921,10 +917,10 @@ static void fill_hit(const unc_index *ix, const unc_params_t &P, const DevResult
 
 // chunks that were out at once in the launches since the pool was last initialised (PoolQueue::low_water)
 static int pool_note_high_water(unc_mapper *m, hipStream_t st) {
-    uint32_t lw = m->pool.n_chunks;
-    HIPCHK(hipMemcpyAsync(&lw, &m->pool.q->low_water, 4, hipMemcpyDeviceToHost, st));
+    uint32_t lw = m->pool.v.n_chunks;
+    HIPCHK(hipMemcpyAsync(&lw, &m->pool.v.q->low_water, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const uint32_t hw = m->pool.n_chunks - std::min(lw, m->pool.n_chunks);
+    const uint32_t hw = m->pool.v.n_chunks - std::min(lw, m->pool.v.n_chunks);
     m->pool_hw_last = std::max(m->pool_hw_last, hw);
     m->pool_hw_max = std::max(m->pool_hw_max, hw);
     return UNC_OK;
@@ -934,7 +930,7 @@ static int pool_note_high_water(unc_mapper *m, hipStream_t st) {
 // that holds more than eight times the most chunks that were ever out at once shrinks to four times that.
 static int pool_fit(unc_mapper *m, bool went_dry, uint32_t n_reads) {
     if (!m->pool_auto) return UNC_OK;
-    const uint64_t cur = m->pool.n_chunks;
+    const uint64_t cur = m->pool.v.n_chunks;
     uint64_t target = cur;
     if (went_dry) {
         // found dry: not one doubling per batch (a pool cut after a small first call took several full batches to recover, each with
@@ -961,21 +957,20 @@ static int pool_fit(unc_mapper *m, bool went_dry, uint32_t n_reads) {
     // the batch's hits are already filled: a resize that fails must neither fail the call nor leave the mapper without a pool.  A
     // smaller pool is allocated BEFORE the old one is freed (both fit); a larger one may need the old one's memory, and if it cannot
     // be had the old size is allocated again.
-    DevPool fresh;
+    Pool fresh;
     size_t bytes = 0;
     if (target < cur) {
-        if (alloc_pool(fresh, (uint32_t)target, &bytes) != UNC_OK) { free_pool(fresh); (void)hipGetLastError(); return UNC_OK; }
-        free_pool(m->pool);
+        if (alloc_pool(fresh, (uint32_t)target, &bytes) != UNC_OK) { (void)hipGetLastError(); return UNC_OK; }
     } else {
-        free_pool(m->pool);
+        m->pool = Pool{};
         if (alloc_pool(fresh, (uint32_t)target, &bytes) != UNC_OK) {
-            free_pool(fresh); (void)hipGetLastError();
+            (void)hipGetLastError();
             target = cur;
             int rc = alloc_pool(fresh, (uint32_t)cur, &bytes);
-            if (rc) { free_pool(fresh); memset(&m->pool, 0, sizeof m->pool); return rc; }      // (the memory was there a moment ago)
+            if (rc) return rc;      // (the memory was there a moment ago)
         }
     }
-    m->pool = fresh;
+    m->pool = std::move(fresh);
     m->device_bytes += (uint64_t)target * POOL_CHUNK_BYTES;
     m->device_bytes -= (uint64_t)cur * POOL_CHUNK_BYTES;
     if (target != cur) m->pool_resizes++;
@@ -984,7 +979,7 @@ static int pool_fit(unc_mapper *m, bool went_dry, uint32_t n_reads) {
 
 extern "C" int unc_mapper_pool_usage(const unc_mapper_t *m, uint32_t *out4) {
     if (!m || !out4) return fail(UNC_ERR_ARG, "null argument");
-    out4[0] = m->pool.n_chunks; out4[1] = m->pool_hw_last; out4[2] = m->pool_hw_max; out4[3] = m->pool_resizes;
+    out4[0] = m->pool.v.n_chunks; out4[1] = m->pool_hw_last; out4[2] = m->pool_hw_max; out4[3] = m->pool_resizes;
     return UNC_OK;
 }
 
@@ -1001,32 +996,29 @@ extern "C" int unc_map_batch_begin(unc_mapper_t *m, uint32_t n_reads, const int1
     DevReads rd;
     int rc = stage_batch(m, n_reads, raw, offsets, calib, on_device, st, &rd);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(m->d_next, 0, 16, st));   // [0] queue head, [2..3] wave-lifetime ticks
+    HIPCHK(hipMemsetAsync(m->d_next.p, 0, 16, st));   // [0] queue head, [2..3] wave-lifetime ticks
     HIPCHK(hipEventRecord(m->ev[0], st));
     launch_events(rd, m->P, st, m->ev_rpw);
     HIPCHK(hipEventRecord(m->ev[1], st));
     const uint32_t grid = n_reads < m->n_waves ? n_reads : m->n_waves;
-    const bool sliced = m->sched.ctl != nullptr && n_reads > m->n_waves;
-    if (sliced) launch_sched_init(m->sched, st);
-    launch_pool_init(m->pool, st);       // every chunk free: nothing outlives a batch
+    const bool sliced = m->sched.v.ctl != nullptr && n_reads > m->n_waves;
+    if (sliced) launch_sched_init(m->sched.v, st);
+    launch_pool_init(m->pool.v, st);       // every chunk free: nothing outlives a batch
     constexpr size_t FW = NKMER / 32;      // words of one read's sources_added_ bitmap
     const bool t1 = m->read_order == UNC_ORDER_T1;
     if (t1) {
-        if (n_reads > m->flags_cap) {
-            if (m->d_flags_in) (void)hipFree(m->d_flags_in);
-            if (m->d_flags_out) (void)hipFree(m->d_flags_out);
-            m->d_flags_in = m->d_flags_out = nullptr; m->flags_cap = 0;
-            HIPCHK(hipMalloc((void **)&m->d_flags_in, (size_t)n_reads * FW * 4));
-            HIPCHK(hipMalloc((void **)&m->d_flags_out, (size_t)n_reads * FW * 4));
-            m->flags_cap = n_reads;
+        if ((size_t)n_reads * FW > m->d_flags_out.cap) {      // (both freed, then both allocated; d_flags_out last: its capacity is that of the two)
+            m->d_flags_in.release(); m->d_flags_out.release();
+            HIPCHK(m->d_flags_in.alloc((size_t)n_reads * FW));
+            HIPCHK(m->d_flags_out.alloc((size_t)n_reads * FW));
         }
-        HIPCHK(hipMemsetAsync(m->d_flags_in, 0, (size_t)n_reads * FW * 4, st));
-        HIPCHK(hipMemcpyAsync(m->d_flags_in, m->carry_flags, FW * 4, hipMemcpyHostToDevice, st));    // read 0 follows the previous batch's last read
+        HIPCHK(hipMemsetAsync(m->d_flags_in.p, 0, (size_t)n_reads * FW * 4, st));
+        HIPCHK(hipMemcpyAsync(m->d_flags_in.p, m->carry_flags, FW * 4, hipMemcpyHostToDevice, st));    // read 0 follows the previous batch's last read
     }
-    const uint32_t *const fl_in = t1 ? m->d_flags_in : nullptr;
-    uint32_t *const fl_out = t1 ? m->d_flags_out : nullptr;
-    launch_map(m->ix->dev, m->sc, rd, m->P, m->d_results, m->d_next, sliced ? m->slice_events : 0xFFFFFFFFu, 0, nullptr, grid, st, m->pool,
-               nullptr, reinterpret_cast<unsigned long long *>(m->d_next + 2), sliced ? &m->sched : nullptr, m->profile, fl_in, fl_out);
+    const uint32_t *const fl_in = t1 ? m->d_flags_in.p : nullptr;
+    uint32_t *const fl_out = t1 ? m->d_flags_out.p : nullptr;
+    launch_map(m->ix->dev, m->sc.v, rd, m->P, m->d_results.p, m->d_next.p, sliced ? m->slice_events : 0xFFFFFFFFu, 0, nullptr, grid, st, m->pool.v,
+               nullptr, reinterpret_cast<unsigned long long *>(m->d_next.p + 2), sliced ? &m->sched.v : nullptr, m->profile, fl_in, fl_out);
     HIPCHK(hipEventRecord(m->ev[2], st));
     HIPCHK(hipGetLastError());
     m->pend.active = true; m->pend.n_reads = n_reads; m->pend.grid = grid; m->pend.st = st; m->pend.rd = rd; m->pend.t1 = t1;
@@ -1045,14 +1037,14 @@ extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
     const DevReads rd = m->pend.rd;
     const bool t1 = m->pend.t1;
     constexpr size_t FW = NKMER / 32;
-    const uint32_t *const fl_in = t1 ? m->d_flags_in : nullptr;
-    uint32_t *const fl_out = t1 ? m->d_flags_out : nullptr;
+    const uint32_t *const fl_in = t1 ? m->d_flags_in.p : nullptr;
+    uint32_t *const fl_out = t1 ? m->d_flags_out.p : nullptr;
     int rc = UNC_OK;
     m->h_info.resize(n_reads);
     m->h_results.resize(n_reads);
     // (the copies into pageable host memory would hold the host until the kernels are done: they are issued here, not in _begin)
-    HIPCHK(hipMemcpyAsync(m->h_info.data(), m->d_info, (size_t)n_reads * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(m->h_results.data(), m->d_results, (size_t)n_reads * sizeof(DevResult), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(m->h_info.data(), m->d_info.p, (size_t)n_reads * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(m->h_results.data(), m->d_results.p, (size_t)n_reads * sizeof(DevResult), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&m->ms_events, m->ev[0], m->ev[1]));
     HIPCHK(hipEventElapsedTime(&m->ms_map, m->ev[1], m->ev[2]));
@@ -1072,7 +1064,7 @@ extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
     {
         unsigned long long ticks = 0;
         int khz = 0;
-        HIPCHK(hipMemcpy(&ticks, m->d_next + 2, 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&ticks, m->d_next.p + 2, 8, hipMemcpyDeviceToHost));
         HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, m->ix->device));
         m->wave_busy = (grid && m->ms_map > 0 && khz > 0) ? (double)ticks / ((double)grid * (double)m->ms_map * (double)khz) : 0.0;
     }
@@ -1095,37 +1087,32 @@ extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
         m->remap_reads += (uint32_t)(dry.size() + full.size());
         if (!dry.empty()) pool_went_dry = true;
         const auto t_redo = std::chrono::steady_clock::now();
-        uint64_t cap = m->sc.max_clusters;
+        uint64_t cap = m->sc.v.max_clusters;
         size_t limit = m->n_waves;
         // one pass over `work` with at most `slots` reads in flight; the reads that overflowed again are sorted by cause
         auto run_round = [&](const DevScratch &sc, size_t slots) -> int {
-            if (work.size() > m->list_cap) {
-                if (m->d_list) (void)hipFree(m->d_list);
-                m->d_list = nullptr; m->list_cap = 0;
-                HIPCHK(hipMalloc((void **)&m->d_list, work.size() * 4));
-                m->list_cap = work.size();
-            }
-            HIPCHK(hipMemcpyAsync(m->d_list, work.data(), work.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemsetAsync(m->d_next, 0, 4, st));
-            launch_pool_init(m->pool, st);
+            HIPCHK(m->d_list.reserve(work.size()));
+            HIPCHK(hipMemcpyAsync(m->d_list.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(m->d_next.p, 0, 4, st));
+            launch_pool_init(m->pool.v, st);
             DevReads rd2 = rd;
             rd2.n_reads = (uint32_t)work.size();
-            launch_map(m->ix->dev, sc, rd2, m->P, m->d_results, m->d_next, 0xFFFFFFFFu, 0, nullptr, (uint32_t)slots, st, m->pool, m->d_list,
+            launch_map(m->ix->dev, sc, rd2, m->P, m->d_results.p, m->d_next.p, 0xFFFFFFFFu, 0, nullptr, (uint32_t)slots, st, m->pool.v, m->d_list.p,
                        nullptr, nullptr, false, fl_in, fl_out);
             HIPCHK(hipGetLastError());
             const uint32_t lo = *std::min_element(work.begin(), work.end()), hi = *std::max_element(work.begin(), work.end());
-            HIPCHK(hipMemcpyAsync(m->h_results.data() + lo, m->d_results + lo, (size_t)(hi - lo + 1) * sizeof(DevResult), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(m->h_results.data() + lo, m->d_results.p + lo, (size_t)(hi - lo + 1) * sizeof(DevResult), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             if (int rc3 = pool_note_high_water(m, st)) return rc3;
             for (uint32_t i : work) classify(i);
             work.clear();
             return UNC_OK;
         };
-        auto scratch_now = [&]() -> const DevScratch & { return cap == m->sc.max_clusters ? m->sc : m->big; };
+        auto scratch_now = [&]() -> const DevScratch & { return cap == m->sc.v.max_clusters ? m->sc.v : m->big.v; };
         while (!dry.empty() || !full.empty()) {
             if (!dry.empty()) {
                 const DevScratch &sc = scratch_now();
-                const size_t have = cap == m->sc.max_clusters ? m->n_slots : m->big_slots;
+                const size_t have = cap == m->sc.v.max_clusters ? m->n_slots : m->big_slots;
                 const size_t slots = std::min({dry.size(), have, limit});
                 work.swap(dry);
                 // (reads that ran out of allowance wait in `full` meanwhile: at this allowance they would only overflow again)
@@ -1145,21 +1132,21 @@ extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
             cap *= 16;
             if (cap > (1ull << 26)) break;
             const size_t want = std::min<size_t>(std::max<size_t>(full.size(), 64), m->n_waves);
-            if (m->big_cap != cap || (m->big_slots < want && !m->big_at_limit)) {
-                free_scratch(m->big);
-                m->big_cap = 0; m->big_slots = 0;
+            if (m->big.v.max_clusters != cap || (m->big_slots < want && !m->big_at_limit)) {      // (the big scratch's allowance: 0 while there is none)
+                m->big = Scratch{};
+                m->big_slots = 0;
                 size_t free_b = 0, total_b = 0;
                 HIPCHK(hipMemGetInfo(&free_b, &total_b));
-                const size_t per_slot = scratch_slot_bytes(m->P, (uint32_t)cap, m->sc.max_seed_paths, m->ix->dev);
+                const size_t per_slot = scratch_slot_bytes(m->P, (uint32_t)cap, m->sc.v.max_seed_paths, m->ix->dev);
                 const size_t fit = std::max<size_t>(1, free_b / 4 / per_slot);
                 const size_t n = std::min(want, fit);
-                int rc2 = alloc_scratch(m->big, m->P, n, (uint32_t)cap, m->sc.max_seed_paths, nullptr, m->ix->dev);
-                if (rc2) { free_scratch(m->big); return rc2; }
-                m->big_cap = cap; m->big_slots = n; m->big_at_limit = n == fit;
+                int rc2 = alloc_scratch(m->big, m->P, n, (uint32_t)cap, m->sc.v.max_seed_paths, nullptr, m->ix->dev);
+                if (rc2) { m->big = Scratch{}; return rc2; }
+                m->big_slots = n; m->big_at_limit = n == fit;
             }
             const size_t slots = std::min({full.size(), m->big_slots, limit});
             work.swap(full);
-            int rc2 = run_round(m->big, slots);
+            int rc2 = run_round(m->big.v, slots);
             if (rc2) return rc2;
         }
         m->remap_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_redo).count();
@@ -1191,7 +1178,7 @@ extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
             }
             std::vector<Flags> got(rows.size());
             for (size_t k = 0; k < rows.size(); ++k)
-                HIPCHK(hipMemcpyAsync(got[k].data(), m->d_flags_out + (size_t)rows[k] * FW, sizeof(Flags), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(got[k].data(), m->d_flags_out.p + (size_t)rows[k] * FW, sizeof(Flags), hipMemcpyDeviceToHost, st));
             if (!rows.empty()) HIPCHK(hipStreamSynchronize(st));
             for (size_t k = 0; k < rows.size(); ++k) left[rows[k]] = got[k];
             return UNC_OK;
@@ -1212,24 +1199,19 @@ extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
             for (uint32_t j : work) {
                 const Flags &f = get(left, j - 1);
                 if (f == zero) assumed.erase(j); else assumed[j] = f;
-                HIPCHK(hipMemcpyAsync(m->d_flags_in + (size_t)j * FW, f.data(), sizeof f, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(m->d_flags_in.p + (size_t)j * FW, f.data(), sizeof f, hipMemcpyHostToDevice, st));
             }
-            if (work.size() > m->list_cap) {
-                if (m->d_list) (void)hipFree(m->d_list);
-                m->d_list = nullptr; m->list_cap = 0;
-                HIPCHK(hipMalloc((void **)&m->d_list, work.size() * 4));
-                m->list_cap = work.size();
-            }
-            HIPCHK(hipMemcpyAsync(m->d_list, work.data(), work.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemsetAsync(m->d_next, 0, 4, st));
-            launch_pool_init(m->pool, st);
+            HIPCHK(m->d_list.reserve(work.size()));
+            HIPCHK(hipMemcpyAsync(m->d_list.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(m->d_next.p, 0, 4, st));
+            launch_pool_init(m->pool.v, st);
             DevReads rd2 = rd;
             rd2.n_reads = (uint32_t)work.size();
-            launch_map(m->ix->dev, m->sc, rd2, m->P, m->d_results, m->d_next, 0xFFFFFFFFu, 0, nullptr,
-                       (uint32_t)std::min<size_t>(work.size(), m->n_slots), st, m->pool, m->d_list, nullptr, nullptr, false, fl_in, fl_out);
+            launch_map(m->ix->dev, m->sc.v, rd2, m->P, m->d_results.p, m->d_next.p, 0xFFFFFFFFu, 0, nullptr,
+                       (uint32_t)std::min<size_t>(work.size(), m->n_slots), st, m->pool.v, m->d_list.p, nullptr, nullptr, false, fl_in, fl_out);
             HIPCHK(hipGetLastError());
             for (uint32_t j : work)
-                HIPCHK(hipMemcpyAsync(m->h_results.data() + j, m->d_results + j, sizeof(DevResult), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(m->h_results.data() + j, m->d_results.p + j, sizeof(DevResult), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             rc = resolve_overflows(&work);
             if (rc) return rc;
@@ -1289,12 +1271,12 @@ extern "C" int unc_mapper_last_read_cycles(const unc_mapper_t *m, uint32_t n_rea
 // [4] event means, [5] results
 extern "C" int unc_mapper_device_addresses(const unc_mapper_t *m, uint64_t *out6) {
     if (!m || !out6) return fail(UNC_ERR_ARG, "null argument");
-    out6[0] = (uint64_t)(uintptr_t)m->sc.base; out6[1] = m->sc.slot_bytes;
-    out6[2] = (uint64_t)(uintptr_t)m->pool.nodes; out6[3] = (uint64_t)m->pool.n_chunks * POOL_CHUNK_BYTES;
-    out6[4] = (uint64_t)(uintptr_t)m->d_means; out6[5] = (uint64_t)(uintptr_t)m->d_results;
+    out6[0] = (uint64_t)(uintptr_t)m->sc.v.base; out6[1] = m->sc.v.slot_bytes;
+    out6[2] = (uint64_t)(uintptr_t)m->pool.v.nodes; out6[3] = (uint64_t)m->pool.v.n_chunks * POOL_CHUNK_BYTES;
+    out6[4] = (uint64_t)(uintptr_t)m->d_means.p; out6[5] = (uint64_t)(uintptr_t)m->d_results.p;
     return UNC_OK;
 }
-extern "C" uint32_t unc_mapper_sched_parts(const unc_mapper_t *m) { return (m && m->sched.ctl) ? m->sched.n_parts : 0u; }
+extern "C" uint32_t unc_mapper_sched_parts(const unc_mapper_t *m) { return (m && m->sched.v.ctl) ? m->sched.v.n_parts : 0u; }
 extern "C" double unc_mapper_last_wave_busy(const unc_mapper_t *m) { return m ? m->wave_busy : 0.0; }
 extern "C" int unc_mapper_set_read_order(unc_mapper_t *m, int order) {
     if (!m || (order != UNC_ORDER_INDEPENDENT && order != UNC_ORDER_T1)) return fail(UNC_ERR_ARG, "unc_mapper_set_read_order: UNC_ORDER_INDEPENDENT or UNC_ORDER_T1");
@@ -1318,8 +1300,8 @@ extern "C" int unc_mapper_kernel_info(const unc_mapper_t *m, uint32_t *out6) {
     return UNC_OK;
 }
 extern "C" void unc_mapper_geometry(const unc_mapper_t *m, uint32_t *out5) {
-    out5[0] = m->n_waves; out5[1] = m->n_slots; out5[2] = m->sched.ctl ? m->slice_events : 0u;
-    out5[3] = m->pool.n_chunks; out5[4] = m->sc.max_clusters;
+    out5[0] = m->n_waves; out5[1] = m->n_slots; out5[2] = m->sched.v.ctl ? m->slice_events : 0u;
+    out5[3] = m->pool.v.n_chunks; out5[4] = m->sc.v.max_clusters;
 }
 extern "C" void unc_mapper_last_remap(const unc_mapper_t *m, uint32_t *n_reads, float *ms) {
     if (n_reads) *n_reads = m ? m->remap_reads : 0;
@@ -1352,7 +1334,7 @@ extern "C" int unc_detect_events(unc_mapper_t *m, uint32_t n_reads, const int16_
     launch_events(rd, m->P, st, m->ev_rpw);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->ev[1], st));
-    HIPCHK(hipMemcpyAsync(info, m->d_info, (size_t)n_reads * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info, m->d_info.p, (size_t)n_reads * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&m->ms_events, m->ev[0], m->ev[1]));     // unc_mapper_last_timing: k_events alone
     m->ms_map = 0;
@@ -1363,7 +1345,7 @@ extern "C" int unc_detect_events(unc_mapper_t *m, uint32_t n_reads, const int16_
     means_offsets[n_reads] = tot;
     if (tot > means_cap) return fail(UNC_ERR_ARG, "means buffer too small: need %llu", (unsigned long long)tot);
     for (uint32_t i = 0; i < n_reads; ++i)
-        HIPCHK(hipMemcpyAsync(means + means_offsets[i], m->d_means + m->h_moff[i], (size_t)info[i].n_events * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(means + means_offsets[i], m->d_means.p + m->h_moff[i], (size_t)info[i].n_events * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return UNC_OK;
 }
@@ -1378,13 +1360,13 @@ extern "C" int unc_sort_pairs_u64(int device, uint64_t n, uint64_t *keys, uint64
     HIPCHK(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     const uint64_t ntiles = (n + rsort_tile() - 1) / rsort_tile(), m = 256 * ntiles, nsums = (m + rsort_tile() - 1) / rsort_tile();
-    uint32_t *counts = nullptr, *sums = nullptr;
-    HIPCHK(hipMalloc((void **)&counts, m * 4));
-    if (hipMalloc((void **)&sums, nsums * 4) != hipSuccess) { (void)hipFree(counts); return fail(UNC_ERR_HIP, "hipMalloc failed"); }
+    DevBuf<uint32_t> counts, sums;
+    HIPCHK(counts.alloc(m));
+    if (sums.alloc(nsums) != hipSuccess) return fail(UNC_ERR_HIP, "hipMalloc failed");
     uint64_t *ki = keys, *vi = vals, *ko = tmp_keys, *vo = tmp_vals;
     const int passes = (key_bits + 7) / 8;
     for (int p = 0; p < passes; ++p) {
-        launch_rsort_pass(ki, vi, ko, vo, n, (uint32_t)(8 * p), (iota && p == 0) ? 1u : 0u, counts, sums, st);
+        launch_rsort_pass(ki, vi, ko, vo, n, (uint32_t)(8 * p), (iota && p == 0) ? 1u : 0u, counts.p, sums.p, st);
         std::swap(ki, ko); std::swap(vi, vo);
     }
     hipError_t e = hipGetLastError();
@@ -1393,7 +1375,6 @@ extern "C" int unc_sort_pairs_u64(int device, uint64_t n, uint64_t *keys, uint64
         if (e == hipSuccess) e = hipMemcpyAsync(vals, vi, n * 8, hipMemcpyDeviceToDevice, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(counts); (void)hipFree(sums);
     if (e != hipSuccess) return fail(UNC_ERR_HIP, "radix sort: %s", hipGetErrorString(e));
     return UNC_OK;
 }
@@ -1409,54 +1390,52 @@ extern "C" int unc_build_suffix_array(int device, const uint8_t *codes, uint64_t
                                                     "uncalled_amd/build_index_big.py takes the larger ones)");
     HIPCHK(hipSetDevice(device));
     hipStream_t st = nullptr;
-    struct Bufs {
-        uint8_t *text = nullptr; uint64_t *k[2] = {nullptr, nullptr}, *v[2] = {nullptr, nullptr};
-        uint32_t *rank = nullptr, *flags = nullptr, *sums = nullptr, *counts = nullptr, *ngroups = nullptr;
-        ~Bufs() { void *p[] = {text, k[0], k[1], v[0], v[1], rank, flags, sums, counts, ngroups}; for (void *x : p) if (x) (void)hipFree(x); }
-    } B;
+    DevBuf<uint8_t> text;
+    DevBuf<uint64_t> key[2], val[2];
+    DevBuf<uint32_t> rank, flags, sums, counts, ngroups;
     const uint64_t ntiles = (n + rsort_tile() - 1) / rsort_tile(), m = 256 * ntiles;
     const uint64_t nsums = (std::max<uint64_t>(m, n) + rsort_tile() - 1) / rsort_tile();
-    HIPCHK(hipMalloc((void **)&B.text, n));
-    for (int i = 0; i < 2; ++i) { HIPCHK(hipMalloc((void **)&B.k[i], n * 8)); HIPCHK(hipMalloc((void **)&B.v[i], n * 8)); }
-    HIPCHK(hipMalloc((void **)&B.rank, n * 4));
-    HIPCHK(hipMalloc((void **)&B.flags, n * 4));
-    HIPCHK(hipMalloc((void **)&B.sums, nsums * 4));
-    HIPCHK(hipMalloc((void **)&B.counts, m * 4));
-    HIPCHK(hipMalloc((void **)&B.ngroups, 4));
-    HIPCHK(hipMemcpyAsync(B.text, codes, n, hipMemcpyHostToDevice, st));
-    // keys in B.k[0], sorted with the suffix numbers as values (iota); returns which pair of buffers holds the result
+    HIPCHK(text.alloc(n));
+    for (int i = 0; i < 2; ++i) { HIPCHK(key[i].alloc(n)); HIPCHK(val[i].alloc(n)); }
+    HIPCHK(rank.alloc(n));
+    HIPCHK(flags.alloc(n));
+    HIPCHK(sums.alloc(nsums));
+    HIPCHK(counts.alloc(m));
+    HIPCHK(ngroups.alloc(1));
+    HIPCHK(hipMemcpyAsync(text.p, codes, n, hipMemcpyHostToDevice, st));
+    // keys in key[0], sorted with the suffix numbers as values (iota); returns which pair of buffers holds the result
     auto sort_keys = [&](int key_bits) -> int {
         int cur = 0;
         const int passes = (key_bits + 7) / 8;
         for (int p = 0; p < passes; ++p) {
-            launch_rsort_pass(B.k[cur], B.v[cur], B.k[cur ^ 1], B.v[cur ^ 1], n, (uint32_t)(8 * p), p == 0 ? 1u : 0u, B.counts, B.sums, st);
+            launch_rsort_pass(key[cur].p, val[cur].p, key[cur ^ 1].p, val[cur ^ 1].p, n, (uint32_t)(8 * p), p == 0 ? 1u : 0u, counts.p, sums.p, st);
             cur ^= 1;
         }
         return cur;
     };
     auto rerank = [&](int key_bits, uint32_t *groups) -> int {
         const int cur = sort_keys(key_bits);
-        launch_sa_ranks(B.k[cur], B.v[cur], n, B.flags, B.sums, B.rank, B.ngroups, st);
+        launch_sa_ranks(key[cur].p, val[cur].p, n, flags.p, sums.p, rank.p, ngroups.p, st);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(groups, B.ngroups, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(groups, ngroups.p, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         return UNC_OK;
     };
     uint32_t groups = 0;
-    launch_sa_first_key(B.text, n, B.k[0], st);
+    launch_sa_first_key(text.p, n, key[0].p, st);
     int rc = rerank(63, &groups);
     if (rc) return rc;
     int bits = 1;
     while ((((unsigned __int128)(n + 1) * (n + 1)) >> bits) != 0) ++bits;      // bits of the largest doubled key
     for (uint64_t k = 21; groups < n; k *= 2) {
-        launch_sa_next_key(B.rank, n, k, B.k[0], st);
+        launch_sa_next_key(rank.p, n, k, key[0].p, st);
         rc = rerank(bits, &groups);
         if (rc) return rc;
         if (k > n) return fail(UNC_ERR_HIP, "unc_build_suffix_array: %u groups of %llu suffixes after comparing whole suffixes", groups, (unsigned long long)n);
     }
-    launch_sa_invert(B.rank, n, reinterpret_cast<int64_t *>(B.k[0]), st);
+    launch_sa_invert(rank.p, n, reinterpret_cast<int64_t *>(key[0].p), st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(sa, B.k[0], n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(sa, key[0].p, n * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return UNC_OK;
 }
@@ -1466,16 +1445,15 @@ extern "C" int unc_build_suffix_array(int device, const uint8_t *codes, uint64_t
 extern "C" int unc_calib_traffic(int device, uint64_t n_records, int reps) {
     HIPCHK(hipSetDevice(device));
     n_records |= 1;     // odd: the multiplicative scatter is then a permutation
-    uint4 *buf = nullptr;
-    uint32_t *sink = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, n_records * 64));
-    HIPCHK(hipMalloc((void **)&sink, 4));
-    for (int i = 0; i < reps; ++i) launch_calib(buf, n_records, 1, sink, nullptr);
+    DevBuf<uint4> buf;
+    DevBuf<uint32_t> sink;
+    HIPCHK(buf.alloc(n_records * 4));
+    HIPCHK(sink.alloc(1));
+    for (int i = 0; i < reps; ++i) launch_calib(buf.p, n_records, 1, sink.p, nullptr);
     HIPCHK(hipDeviceSynchronize());
-    for (int i = 0; i < reps; ++i) launch_calib(buf, n_records, 0, sink, nullptr);
+    for (int i = 0; i < reps; ++i) launch_calib(buf.p, n_records, 0, sink.p, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    (void)hipFree(buf); (void)hipFree(sink);
     return UNC_OK;
 }
 
@@ -1484,21 +1462,24 @@ extern "C" int unc_calib_traffic(int device, uint64_t n_records, int reps) {
 extern "C" int unc_calib_chase(int device, const void *base, uint64_t bytes, uint32_t waves, uint32_t steps, float *ms_out) {
     if (!base || bytes < 16 || !ms_out) return fail(UNC_ERR_ARG, "unc_calib_chase: a region of 16 bytes or more");
     HIPCHK(hipSetDevice(device));
-    uint32_t *sink = nullptr;
-    hipEvent_t e0, e1;
-    HIPCHK(hipMalloc((void **)&sink, 4));
+    DevBuf<uint32_t> sink;
+    struct Events {      // (destroyed on every way out)
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } evs;
+    hipEvent_t &e0 = evs.e[0], &e1 = evs.e[1];
+    HIPCHK(sink.alloc(1));
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     float best = 1e30f;
     for (int r = 0; r < 3; ++r) {
         HIPCHK(hipEventRecord(e0, nullptr));
-        launch_calib_chase((const uint4 *)base, bytes / 16, waves ? waves : 4096, steps ? steps : 2000, sink, nullptr);
+        launch_calib_chase((const uint4 *)base, bytes / 16, waves ? waves : 4096, steps ? steps : 2000, sink.p, nullptr);
         HIPCHK(hipEventRecord(e1, nullptr));
         HIPCHK(hipEventSynchronize(e1));
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, e0, e1));
         best = std::min(best, ms);
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(sink);
     *ms_out = best;
     return UNC_OK;
 }
@@ -1514,13 +1495,13 @@ extern "C" int unc_trace_begin(unc_mapper_t *m, const int16_t *raw, uint32_t n, 
     int rc = stage_batch(m, 1, raw, offsets, calib, 0, st, &rd);
     if (rc) return rc;
     launch_events(rd, m->P, st, m->ev_rpw);
-    launch_pool_init(m->pool, st);      // the traced read starts with every chunk free
+    launch_pool_init(m->pool.v, st);      // the traced read starts with every chunk free
     SlotState s0;
     memset(&s0, 0, sizeof s0);
     s0.max_map.rstart = 1; s0.max_map.evt_st = 1;   // NULL_ALN
-    HIPCHK(hipMemcpyAsync(slot_state(m->sc, 0), &s0, sizeof s0, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(slot_state(m->sc.v, 0), &s0, sizeof s0, hipMemcpyHostToDevice, st));
     unc_evt_info_t info0;
-    HIPCHK(hipMemcpyAsync(&info0, m->d_info, sizeof info0, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&info0, m->d_info.p, sizeof info0, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     // (as the batch path: a read whose events overran the room for their means is reported, never traced on a truncated list)
     if (info0.pad) return fail(UNC_ERR_OVERFLOW, "traced read: more events than the room for event means holds (5/8 of its samples + 16)");
@@ -1530,8 +1511,8 @@ extern "C" int unc_trace_begin(unc_mapper_t *m, const int16_t *raw, uint32_t n, 
 }
 
 static int trace_reads(unc_mapper *m, DevReads *rd) {
-    rd->raw = m->d_raw; rd->offsets = m->d_offsets; rd->calib = m->d_calib; rd->means = m->d_means; rd->moff = m->d_moff;
-    rd->info = m->d_info; rd->n_reads = 1; rd->tgt_mean = m->ix->model_mean; rd->tgt_stdv = m->ix->model_stdv;
+    rd->raw = m->d_raw.p; rd->offsets = m->d_offsets.p; rd->calib = m->d_calib.p; rd->means = m->d_means.p; rd->moff = m->d_moff.p;
+    rd->info = m->d_info.p; rd->n_reads = 1; rd->tgt_mean = m->ix->model_mean; rd->tgt_stdv = m->ix->model_stdv;
     rd->ring0 = nullptr; rd->new_read = nullptr; rd->ring_mod = 0;
     return UNC_OK;
 }
@@ -1542,10 +1523,10 @@ extern "C" int unc_trace_step(unc_mapper_t *m, uint32_t n_events, int *done) {
     HIPCHK(hipSetDevice(m->ix->device));
     DevReads rd;
     trace_reads(m, &rd);
-    launch_map(m->ix->dev, m->sc, rd, m->P, m->d_results, m->d_next, n_events, 1, nullptr, 1, m->stream, m->pool);
+    launch_map(m->ix->dev, m->sc.v, rd, m->P, m->d_results.p, m->d_next.p, n_events, 1, nullptr, 1, m->stream, m->pool.v);
     HIPCHK(hipGetLastError());
     SlotState s;
-    HIPCHK(hipMemcpyAsync(&s, slot_state(m->sc, 0), sizeof s, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(&s, slot_state(m->sc.v, 0), sizeof s, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     if (done) *done = s.done ? 1 : 0;
     return UNC_OK;
@@ -1555,8 +1536,8 @@ extern "C" int unc_trace_paths(unc_mapper_t *m, unc_path_t *out, uint32_t cap, u
     if (!m || !m->trace_active) return fail(UNC_ERR_ARG, "no trace in progress");
     HIPCHK(hipSetDevice(m->ix->device));
     SlotState s;
-    HIPCHK(hipMemcpy(&s, slot_state(m->sc, 0), sizeof s, hipMemcpyDeviceToHost));
-    const DevScratch &sc = m->sc;
+    HIPCHK(hipMemcpy(&s, slot_state(m->sc.v, 0), sizeof s, hipMemcpyDeviceToHost));
+    const DevScratch &sc = m->sc.v;
     std::vector<uint32_t> ord(s.n_parents ? s.n_parents : 1);
     std::vector<PathRec> recs(sc.max_paths);
     // The paths belong to event `gen`.  prob_sums_ is not stored (PathRec): entry 0 is `sub`, entry j the sum after the j-th
@@ -1566,10 +1547,10 @@ extern "C" int unc_trace_paths(unc_mapper_t *m, unc_path_t *out, uint32_t cap, u
     const int64_t gen = s.done == 1 ? (int64_t)s.event_i : (int64_t)s.event_i - 1;
     unc_evt_info_t inf;
     uint64_t moff = 0;
-    HIPCHK(hipMemcpy(&inf, m->d_info, sizeof inf, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&moff, m->d_moff, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&inf, m->d_info.p, sizeof inf, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&moff, m->d_moff.p, 8, hipMemcpyDeviceToHost));
     std::vector<float> means(gen >= 0 ? (size_t)gen + 1 : 1);
-    if (gen >= 0) HIPCHK(hipMemcpy(means.data(), m->d_means + moff, ((size_t)gen + 1) * 4, hipMemcpyDeviceToHost));
+    if (gen >= 0) HIPCHK(hipMemcpy(means.data(), m->d_means.p + moff, ((size_t)gen + 1) * 4, hipMemcpyDeviceToHost));
     const bool narrow = m->ix->dev.key_len_bits != 0;
     HIPCHK(hipMemcpy(ord.data(), sc.base + sc.off_order + (size_t)s.cur * sc.max_paths * 4, (size_t)s.n_parents * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(recs.data(), sc.base + sc.off_paths + (size_t)s.cur * sc.max_paths * sizeof(PathRec),
@@ -1625,20 +1606,20 @@ extern "C" int unc_trace_clusters(unc_mapper_t *m, unc_cluster_t *out, uint32_t 
     if (!m || !m->trace_active) return fail(UNC_ERR_ARG, "no trace in progress");
     HIPCHK(hipSetDevice(m->ix->device));
     SlotState s;
-    HIPCHK(hipMemcpy(&s, slot_state(m->sc, 0), sizeof s, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&s, slot_state(m->sc.v, 0), sizeof s, hipMemcpyDeviceToHost));
     // flatten the bucket grid (k_map.hip, add_seed): heads -> chains of nodes (hot keys, then cold parts), then set order
     // (ref_en_.start descending, evt_en_ descending: seed_tracker.cpp:97-102)
     const uint32_t n_buckets = m->ix->dev.n_buckets;
     std::vector<uint32_t> heads(n_buckets);
-    HIPCHK(hipMemcpy(heads.data(), m->sc.base + m->sc.off_cl_dir, (size_t)n_buckets * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(heads.data(), m->sc.v.base + m->sc.v.off_cl_dir, (size_t)n_buckets * 4, hipMemcpyDeviceToHost));
     const uint32_t n_chunks = (s.n_alloc + CHUNK_NODES - 1) / CHUNK_NODES;
     std::vector<uint32_t> chunk_ids(n_chunks ? n_chunks : 1);
-    HIPCHK(hipMemcpy(chunk_ids.data(), m->sc.base + m->sc.off_cl_chunks, (size_t)n_chunks * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(chunk_ids.data(), m->sc.v.base + m->sc.v.off_cl_chunks, (size_t)n_chunks * 4, hipMemcpyDeviceToHost));
     std::map<uint32_t, std::vector<char>> chunks;            // pool chunk -> its bytes
     for (uint32_t c = 0; c < n_chunks; ++c) {
         std::vector<char> &buf = chunks[chunk_ids[c]];
         buf.resize((size_t)CHUNK_NODES * NODE_BYTES);
-        HIPCHK(hipMemcpy(buf.data(), m->pool.nodes + (size_t)chunk_ids[c] * POOL_CHUNK_BYTES, buf.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(buf.data(), m->pool.v.nodes + (size_t)chunk_ids[c] * POOL_CHUNK_BYTES, buf.size(), hipMemcpyDeviceToHost));
     }
     std::vector<unc_cluster_t> all;
     for (uint32_t b = 0; b < n_buckets; ++b) {
@@ -1683,9 +1664,9 @@ extern "C" int unc_trace_finish(unc_mapper_t *m, unc_hit_t *hit) {
     if (!m || !m->trace_active) return fail(UNC_ERR_ARG, "no trace in progress");
     HIPCHK(hipSetDevice(m->ix->device));
     SlotState s;
-    HIPCHK(hipMemcpy(&s, slot_state(m->sc, 0), sizeof s, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&s, slot_state(m->sc.v, 0), sizeof s, hipMemcpyDeviceToHost));
     unc_evt_info_t inf;
-    HIPCHK(hipMemcpy(&inf, m->d_info, sizeof inf, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&inf, m->d_info.p, sizeof inf, hipMemcpyDeviceToHost));
     DevResult res;
     memset(&res, 0, sizeof res);
     res.done = s.done; res.status = s.status; res.event_i = s.event_i; res.cluster = s.max_map;
@@ -1703,17 +1684,16 @@ struct unc_rt {
     unc_params_t P;
     uint32_t n_channels = 0;
     uint32_t team = 8;            // wavefronts per channel in k_map (UNC_RT_TEAM)
-    DevScratch sc;
-    DevPool pool{};               // nodes of the channels' seed-cluster grids (a channel keeps its chunks until its read is decided)
-    RtChan *d_chans = nullptr;
-    float *d_ring = nullptr;
-    RtChunkDesc *d_desc = nullptr;
-    unc_evt_info_t *d_info = nullptr;
-    uint32_t *d_ring0 = nullptr, *d_newread = nullptr, *d_slotmap = nullptr, *d_next = nullptr;
-    uint64_t *d_moff = nullptr;
-    DevResult *d_results = nullptr;
-    int16_t *d_raw = nullptr;
-    size_t raw_cap = 0;
+    Scratch sc;
+    Pool pool;                    // nodes of the channels' seed-cluster grids (a channel keeps its chunks until its read is decided)
+    DevBuf<RtChan> d_chans;
+    DevBuf<float> d_ring;
+    DevBuf<RtChunkDesc> d_desc;
+    DevBuf<unc_evt_info_t> d_info;
+    DevBuf<uint32_t> d_ring0, d_newread, d_slotmap, d_next;
+    DevBuf<uint64_t> d_moff;
+    DevBuf<DevResult> d_results;
+    DevBuf<int16_t> d_raw;        // capacity in int16 elements (floats take two each); 64 more lie behind them
     uint64_t device_bytes = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -1738,14 +1718,16 @@ extern "C" void unc_rt_free(unc_rt_t *rt) {
         fprintf(stderr, "\n");
     }
     (void)hipSetDevice(rt->ix->device);
-    free_pool(rt->pool);
-    void *ptrs[] = {rt->sc.base,
-                    rt->d_chans, rt->d_ring, rt->d_desc, rt->d_info, rt->d_ring0, rt->d_newread, rt->d_slotmap, rt->d_next, rt->d_moff,
-                    rt->d_results, rt->d_raw};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &e : rt->ev) if (e) (void)hipEventDestroy(e);
     if (rt->stream) (void)hipStreamDestroy(rt->stream);
     delete rt;
+}
+
+template <class T> static int alloc_zeroed(DevBuf<T> &buf, size_t count, size_t *bytes) {
+    HIPCHK(buf.alloc(count));
+    HIPCHK(hipMemset(buf.p, 0, count * sizeof(T)));
+    *bytes += count * sizeof(T);
+    return UNC_OK;
 }
 
 extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint32_t n_channels, unc_rt_t **out) {
@@ -1788,7 +1770,7 @@ extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint3
         PlacementSpacer spacer(S * scratch_slot_bytes(*p, 1u << 20, 2 * p->max_paths, ix->dev) + S * 64 * (size_t)POOL_CHUNK_BYTES);
         int rc = alloc_scratch(rt->sc, *p, S, 1u << 20, 2 * p->max_paths, &bytes, ix->dev);
         if (rc) return rc;
-        HIPCHK(hipMemset(rt->sc.base, 0, bytes));
+        HIPCHK(hipMemset(rt->sc.v.base, 0, bytes));
         // the channels' node pool: 16 chunks (12 288 nodes) per channel on average, 64 on references of 2^26 rows and more (a read
         // there touches tens of thousands of buckets); UNC_RT_POOL_CHUNKS overrides.  A channel's chunks go back when its read is
         // decided; a read that finds the pool dry fails with its status set (there is no second pass in chunked mode).
@@ -1815,24 +1797,21 @@ extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint3
         rc = alloc_pool(rt->pool, (uint32_t)n_chunks, &bytes);
         if (rc) return rc;
     }
-#define RALLOC(ptr, type, count)                                   \
-    do {                                                           \
-        size_t b_ = (size_t)(count) * sizeof(type);                \
-        HIPCHK(hipMalloc((void **)&(ptr), b_));                    \
-        HIPCHK(hipMemset((ptr), 0, b_));                           \
-        bytes += b_;                                               \
-    } while (0)
-    RALLOC(rt->d_chans, RtChan, S);
-    RALLOC(rt->d_ring, float, S * NORM_LEN);
-    RALLOC(rt->d_desc, RtChunkDesc, S);
-    RALLOC(rt->d_info, unc_evt_info_t, S);
-    RALLOC(rt->d_ring0, uint32_t, S);
-    RALLOC(rt->d_newread, uint32_t, S);
-    RALLOC(rt->d_slotmap, uint32_t, S);
-    RALLOC(rt->d_next, uint32_t, 16);
-    RALLOC(rt->d_moff, uint64_t, S + 1);
-    RALLOC(rt->d_results, DevResult, S);
-#undef RALLOC
+    {
+        int rc = UNC_OK;
+        auto zeroed = [&](auto &buf, size_t count) { if (rc == UNC_OK) rc = alloc_zeroed(buf, count, &bytes); };
+        zeroed(rt->d_chans, S);
+        zeroed(rt->d_ring, S * NORM_LEN);
+        zeroed(rt->d_desc, S);
+        zeroed(rt->d_info, S);
+        zeroed(rt->d_ring0, S);
+        zeroed(rt->d_newread, S);
+        zeroed(rt->d_slotmap, S);
+        zeroed(rt->d_next, 16);
+        zeroed(rt->d_moff, S + 1);
+        zeroed(rt->d_results, S);
+        if (rc) return rc;
+    }
     rt->device_bytes = bytes;
     rt->chans.resize(n_channels);
     HIPCHK(hipStreamCreate(&rt->stream));
@@ -1853,8 +1832,8 @@ extern "C" int unc_rt_tap_channel(unc_rt_t *rt, uint32_t channel, unc_rt_tap_t *
     if (!rt || !out || !ring || channel >= rt->n_channels) return fail(UNC_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(rt->ix->device));
     RtChan c;
-    HIPCHK(hipMemcpy(&c, rt->d_chans + channel, sizeof c, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ring, rt->d_ring + (size_t)channel * NORM_LEN, (size_t)NORM_LEN * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&c, rt->d_chans.p + channel, sizeof c, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ring, rt->d_ring.p + (size_t)channel * NORM_LEN, (size_t)NORM_LEN * 4, hipMemcpyDeviceToHost));
     memset(out, 0, sizeof *out);
     out->det_t = c.t; out->det_total_events = c.total_events; out->det_len_sum = c.len_sum;
     out->norm_n = c.n_n; out->norm_wr = c.n_wr; out->norm_mean = c.n_mean; out->norm_varsum = c.n_varsum;
@@ -1939,40 +1918,35 @@ static int rt_process(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chu
         const char *d_base = raw_pa ? reinterpret_cast<const char *>(raw_pa) : reinterpret_cast<const char *>(raw);
         if (!on_device) {
             const uint64_t span = hi > lo ? hi - lo : 0;
-            if (span * 2 > rt->raw_cap) {              // raw_cap counts int16 elements; floats take two each
-                if (rt->d_raw) (void)hipFree(rt->d_raw);
-                rt->d_raw = nullptr;
-                HIPCHK(hipMalloc((void **)&rt->d_raw, (span * 2 + 64) * 2));
-                rt->raw_cap = span * 2;
-            }
-            if (span) HIPCHK(hipMemcpyAsync(rt->d_raw, d_base + lo * esz, span * esz, hipMemcpyHostToDevice, st));
-            d_base = reinterpret_cast<const char *>(rt->d_raw) - lo * esz;
+            HIPCHK(rt->d_raw.reserve(span * 2, 64));
+            if (span) HIPCHK(hipMemcpyAsync(rt->d_raw.p, d_base + lo * esz, span * esz, hipMemcpyHostToDevice, st));
+            d_base = reinterpret_cast<const char *>(rt->d_raw.p) - lo * esz;
         }
         const int16_t *d_raw = raw_pa ? nullptr : reinterpret_cast<const int16_t *>(d_base);
         const float *d_pa = raw_pa ? reinterpret_cast<const float *>(d_base) : nullptr;
         moff.push_back(0);
-        HIPCHK(hipMemcpyAsync(rt->d_desc, desc.data(), n_act * sizeof(RtChunkDesc), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(rt->d_slotmap, slotmap.data(), n_act * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(rt->d_newread, newread.data(), n_act * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(rt->d_moff, moff.data(), (n_act + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(rt->d_desc.p, desc.data(), n_act * sizeof(RtChunkDesc), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(rt->d_slotmap.p, slotmap.data(), n_act * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(rt->d_newread.p, newread.data(), n_act * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(rt->d_moff.p, moff.data(), (n_act + 1) * 8, hipMemcpyHostToDevice, st));
         HIPCHK(hipEventRecord(rt->ev[0], st));
-        launch_rt_events(d_raw, d_pa, rt->d_desc, n_act, rt->d_chans, rt->d_ring, rt->P, rt->ix->model_mean, rt->ix->model_stdv, rt->d_info,
-                         rt->d_ring0, st);
+        launch_rt_events(d_raw, d_pa, rt->d_desc.p, n_act, rt->d_chans.p, rt->d_ring.p, rt->P, rt->ix->model_mean, rt->ix->model_stdv, rt->d_info.p,
+                         rt->d_ring0.p, st);
         HIPCHK(hipEventRecord(rt->ev[1], st));
         DevReads rd;
         memset(&rd, 0, sizeof rd);
-        rd.means = rt->d_ring; rd.moff = rt->d_moff; rd.info = rt->d_info; rd.n_reads = n_act;
+        rd.means = rt->d_ring.p; rd.moff = rt->d_moff.p; rd.info = rt->d_info.p; rd.n_reads = n_act;
         rd.tgt_mean = rt->ix->model_mean; rd.tgt_stdv = rt->ix->model_stdv;
-        rd.ring0 = rt->d_ring0; rd.new_read = rt->d_newread; rd.ring_mod = NORM_LEN;
-        launch_map(rt->ix->dev, rt->sc, rd, rt->P, rt->d_results, rt->d_next, 0xFFFFFFFFu, 1, rt->d_slotmap, n_act, st, rt->pool, nullptr, nullptr, nullptr,
+        rd.ring0 = rt->d_ring0.p; rd.new_read = rt->d_newread.p; rd.ring_mod = NORM_LEN;
+        launch_map(rt->ix->dev, rt->sc.v, rd, rt->P, rt->d_results.p, rt->d_next.p, 0xFFFFFFFFu, 1, rt->d_slotmap.p, n_act, st, rt->pool.v, nullptr, nullptr, nullptr,
                    rt->profile, nullptr, nullptr, rt->team);
         HIPCHK(hipEventRecord(rt->ev[2], st));
         HIPCHK(hipGetLastError());
         rt->h_info.resize(n_act);
-        HIPCHK(hipMemcpyAsync(rt->h_info.data(), rt->d_info, n_act * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(rt->h_info.data(), rt->d_info.p, n_act * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
     }
     rt->h_state.resize(rt->n_channels);
-    HIPCHK(hipMemcpy2DAsync(rt->h_state.data(), sizeof(SlotState), rt->sc.base + rt->sc.off_state, rt->sc.slot_bytes, sizeof(SlotState), rt->n_channels,
+    HIPCHK(hipMemcpy2DAsync(rt->h_state.data(), sizeof(SlotState), rt->sc.v.base + rt->sc.v.off_state, rt->sc.v.slot_bytes, sizeof(SlotState), rt->n_channels,
                              hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (n_act) {
