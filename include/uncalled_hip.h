@@ -336,6 +336,58 @@ int unc_sort_pairs_u64(int device, uint64_t n, uint64_t *keys, uint64_t *vals, u
  * HIP kernels (k_sort.hip), no torch.  uncalled_amd/build_index.py writes the five BWA-format index files around it. */
 int unc_build_suffix_array(int device, const uint8_t *codes, uint64_t n, int64_t *sa);
 
+/* ---- signal-to-reference alignment: replaces DTW<float, u16, Func> (src/dtw.hpp:31-186) with the two cost functions the
+ * reference ships, DTWr94p (dtw.hpp:188-210: -PoreModel::match_prob of the r9.4 TEMPLATE model, pore_model.hpp:163-165) and DTWr94d
+ * (dtw.hpp:212-233: |event - model mean|), for a whole batch of alignments.  Rows are the reference k-mers, columns the event
+ * means.  Full matrix, no band: every cell is the reference's float arithmetic (dtw.hpp:51-74), so scores and paths are the
+ * reference's bit for bit.  Only 2 bits per cell (the back-pointer) reach HBM; the scores live in registers. */
+#define UNC_DTW_NONE 0u   /* DTWSubSeq::NONE: global alignment */
+#define UNC_DTW_ROW 1u    /* DTWSubSeq::ROW: the events may align to a sub-range of the k-mers */
+#define UNC_DTW_COL 2u    /* DTWSubSeq::COL: the k-mers may align to a sub-range of the events */
+#define UNC_DTW_R94P 0u   /* dtwcost_r94p, dtw.hpp:188-190 */
+#define UNC_DTW_R94D 1u   /* dtwcost_r94d, dtw.hpp:212-214 */
+typedef struct {
+    uint32_t subseq;      /* UNC_DTW_NONE | ROW | COL */
+    uint32_t cost;        /* UNC_DTW_R94P | R94D */
+    float dw, hw, vw;     /* DTWParams, dtw.hpp:10-13 */
+} unc_dtw_params_t;
+/* the presets of dtw.hpp:15-28 as initialisers, the cost left to the caller: unc_dtw_params_t p = UNC_DTW_EVENT_QSUB(UNC_DTW_R94P); */
+#define UNC_DTW_EVENT_GLOB(cost) { UNC_DTW_NONE, (cost), 2.0f, 1.0f, 100.0f }
+#define UNC_DTW_EVENT_QSUB(cost) { UNC_DTW_COL, (cost), 2.0f, 1.0f, 100.0f }
+#define UNC_DTW_EVENT_RSUB(cost) { UNC_DTW_ROW, (cost), 2.0f, 1.0f, 100.0f }
+#define UNC_DTW_RAW_QSUB(cost) { UNC_DTW_COL, (cost), 10.0f, 1.0f, 1000.0f }
+#define UNC_DTW_RAW_RSUB(cost) { UNC_DTW_ROW, (cost), 10.0f, 1.0f, 1000.0f }
+#define UNC_DTW_RAW_GLOB(cost) { UNC_DTW_NONE, (cost), 10.0f, 1.0f, 1000.0f }
+/* per-alignment status */
+#define UNC_DTW_OK 0u
+#define UNC_DTW_TOO_LARGE 1u        /* the alignment's back-pointers alone exceed the workspace: not computed, score and path_len are 0 */
+#define UNC_DTW_PATH_TRUNCATED 2u   /* path_len exceeds the room the caller gave: score and path_len are right, the first pairs are written */
+typedef struct {
+    float score, mean_score;        /* DTW::score / DTW::mean_score, dtw.hpp:126-132 */
+    uint64_t path_len;              /* DTW::get_path().size() */
+    uint32_t status, pad;
+} unc_dtw_result_t;
+/* n alignments in one call: alignment a takes events[ev_off[a] .. ev_off[a+1]) as columns and kmers[km_off[a] .. km_off[a+1]) as rows
+ * (all host arrays; offsets ascending).  path (host, may be NULL: scores and lengths only) receives DTW::get_path() of alignment a as
+ * pairs of uint32 (event j, k-mer i), end cell first, from pair index path_off[a] on, at most path_off[a+1] - path_off[a] pairs;
+ * rows + cols - 1 pairs always suffice.  workspace_bytes bounds the device memory for back-pointers (0: half of the free HBM): a batch
+ * that needs more runs in several rounds with the same results; an alignment that alone needs more gets UNC_DTW_TOO_LARGE and the
+ * others are computed as usual.  Empty events or k-mers, a k-mer >= 1024, 2^31 or more rows or columns, or an unknown subseq / cost:
+ * UNC_ERR_ARG before anything touches the device (the reference has undefined behaviour there).  stream: a hipStream_t or NULL. */
+int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
+                  const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
+                  const uint64_t *path_off, void *stream);
+/* milliseconds the DTW kernel of the calling thread's last unc_dtw_batch ran (HIP events on the stream, summed over its rounds), the
+ * rounds it took and the bytes of back-pointers it held at most */
+int unc_dtw_last_timing(float *ms_kernel, uint32_t *rounds, uint64_t *crumb_bytes);
+/* host copies of the three tables of the r9.4 template model the DTW costs read (PoreModel(vector, cmpl=false), pore_model.hpp:77-103) */
+void unc_dtw_model_tables(float *means1024, float *vars_x2_1024, float *lognorm1024);
+/* BwaIndex::get_kmers (bwa_index.hpp:247-255): the 5-mers of bases [st, en) of sequence rid = seq_to_kmers (bp.hpp:125-146) over the
+ * packed sequence <prefix>.pac, followed for fwd == 0 by kmers_revcomp (bp.hpp:82-99).  Host only.  *n receives the count
+ * (en - st - 4, or 0 below five bases); out (may be NULL to ask for the count) holds up to cap k-mers. */
+int unc_ref_kmers(const unc_index_t *ix, const char *bwa_prefix, int32_t rid, uint64_t st, uint64_t en, int fwd, uint16_t *out,
+                  uint64_t cap, uint64_t *n);
+
 /* ---- measurement aid: `reps` launches that write, then `reps` that read, n_records (made odd) scattered 64-byte records with
  * one lane per record and four 16-byte accesses per lane -- k_map's access shape with an exactly known byte count, for
  * calibrating the HBM traffic counters of rocprofv3 (tools/dev/pmc_calib.py, profiles/r02_pmc_k_map.json) */

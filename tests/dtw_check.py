@@ -1,0 +1,54 @@
+"""TEST INFRASTRUCTURE: the CPU checker of the DTW tests -- tests/dtw_check.c compiled on first use (gcc -O2 -ffp-contract=off)
+into a temporary directory.  It reproduces every alignment of tests/golden/dtw_goldens.npz bit for bit (tests/test_dtw_cpu.py)
+and is the yardstick for sizes the goldens cannot hold."""
+import atexit
+import ctypes as C
+import shutil
+import subprocess
+import tempfile
+from pathlib import Path
+
+import numpy as np
+
+HERE = Path(__file__).resolve().parent
+NONE, ROW, COL = 0, 1, 2
+R94P, R94D = 0, 1
+
+
+class Checker:
+    _lib = None
+
+    def __init__(self, model=None):
+        """model: (means, vars_x2, lognorm) of the r9.4 template model, 1024 float32 each (default: the library's host tables,
+        whose means and costs tests/test_dtw_cpu.py holds against the goldens)"""
+        if Checker._lib is None:
+            tmp = tempfile.mkdtemp(prefix="dtw_check_")
+            atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+            so = Path(tmp) / "libdtw_check.so"
+            subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", str(so), str(HERE / "dtw_check.c"), "-lm"], check=True)
+            L = C.CDLL(str(so))
+            L.dtw_check.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                    C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)]
+            L.dtw_check_cost.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_float]
+            L.dtw_check_cost.restype = C.c_float
+            Checker._lib = L
+        if model is None:
+            from uncalled_amd import capi
+            model = capi.dtw_model_tables()
+        self.model = np.ascontiguousarray(np.concatenate([np.asarray(m, np.float32) for m in model]))
+        assert self.model.size == 3 * 1024
+
+    def cost(self, cost, k, e):
+        return np.float32(self._lib.dtw_check_cost(cost, self.model.ctypes.data, int(k), float(np.float32(e))))
+
+    def dtw(self, events, kmers, subseq, cost, dw, hw, vw):
+        ev = np.ascontiguousarray(events, np.float32)
+        km = np.ascontiguousarray(kmers, np.uint16)
+        path = np.empty((ev.size + km.size - 1, 2), np.uint32)
+        score, n, ties = C.c_float(), C.c_uint64(), C.c_uint64()
+        rc = self._lib.dtw_check(ev.ctypes.data, ev.size, km.ctypes.data, km.size, self.model.ctypes.data, subseq, cost, dw, hw, vw,
+                                 C.byref(score), C.byref(n), path.ctypes.data, C.byref(ties))
+        assert rc == 0
+        s = np.float32(score.value)
+        return dict(score=s, score_bits=int(s.view(np.uint32)), mean=np.float32(s / np.float32(n.value)), path_len=int(n.value),
+                    path=path[:n.value].copy(), ties=int(ties.value))

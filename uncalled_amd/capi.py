@@ -111,6 +111,28 @@ RT_RESULT = np.dtype([("state", "<i4"), ("ended", "<i4"), ("hit", HIT)])
 RT_FIRST, RT_LAST = 1, 2
 RT_MAPPING, RT_MAPPED, RT_FAILED, RT_IGNORED = 0, 1, 2, 3
 
+
+
+class DTWParams(C.Structure):
+    """unc_dtw_params_t: DTWParams of the reference (dtw.hpp:10-13) plus the cost function (DTWr94p / DTWr94d)."""
+    _fields_ = [("subseq", C.c_uint32), ("cost", C.c_uint32), ("dw", C.c_float), ("hw", C.c_float), ("vw", C.c_float)]
+
+    def with_cost(self, cost):
+        return DTWParams(self.subseq, cost, self.dw, self.hw, self.vw)
+
+
+DTW_NONE, DTW_ROW, DTW_COL = 0, 1, 2                  # DTWSubSeq
+DTW_R94P, DTW_R94D = 0, 1                             # dtwcost_r94p / dtwcost_r94d
+DTW_OK, DTW_TOO_LARGE, DTW_PATH_TRUNCATED = 0, 1, 2   # unc_dtw_result_t.status
+# the presets of dtw.hpp:15-28 (cost r94p; .with_cost(DTW_R94D) for the other)
+DTW_EVENT_GLOB = DTWParams(DTW_NONE, DTW_R94P, 2, 1, 100)
+DTW_EVENT_QSUB = DTWParams(DTW_COL, DTW_R94P, 2, 1, 100)
+DTW_EVENT_RSUB = DTWParams(DTW_ROW, DTW_R94P, 2, 1, 100)
+DTW_RAW_QSUB = DTWParams(DTW_COL, DTW_R94P, 10, 1, 1000)
+DTW_RAW_RSUB = DTWParams(DTW_ROW, DTW_R94P, 10, 1, 1000)
+DTW_RAW_GLOB = DTWParams(DTW_NONE, DTW_R94P, 10, 1, 1000)
+DTW_RESULT = np.dtype([("score", "<f4"), ("mean_score", "<f4"), ("path_len", "<u8"), ("status", "<u4"), ("pad", "<u4")])
+
 _libs = {}
 
 
@@ -198,6 +220,12 @@ def load(path=None):
     L.unc_trace_paths.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.unc_trace_clusters.argtypes = [vp, vp, u32, C.POINTER(u32), vp, C.POINTER(C.c_float), C.POINTER(u32)]
     L.unc_trace_finish.argtypes = [vp, vp]
+    if hasattr(L, "unc_dtw_batch"):                   # (the emulator build of the mapper's sources does not hold the DTW entry points)
+        L.unc_dtw_batch.argtypes = [C.c_int, u32, vp, vp, vp, vp, C.POINTER(DTWParams), u64, vp, vp, vp, vp]
+        L.unc_dtw_last_timing.argtypes = [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(u64)]
+        L.unc_dtw_model_tables.argtypes = [vp, vp, vp]
+        L.unc_dtw_model_tables.restype = None
+        L.unc_ref_kmers.argtypes = [vp, C.c_char_p, i32, u64, u64, C.c_int, vp, u64, C.POINTER(u64)]
     _libs[key] = L
     return L
 
@@ -286,6 +314,70 @@ class Index:
         out = np.empty((lv.size, 1024), dtype=np.float32)
         _check(self.L, self.L.unc_match_probs(self.h, lv.size, lv.ctypes.data, out.ctypes.data))
         return out
+
+
+def dtw_model_tables(lib=None):
+    """Host copies of the r9.4 TEMPLATE model's tables the DTW costs read: (means, vars_x2, lognorm), 1024 float32 each."""
+    L = lib or load()
+    a, b, c = (np.empty(1024, dtype=np.float32) for _ in range(3))
+    L.unc_dtw_model_tables(a.ctypes.data, b.ctypes.data, c.ctypes.data)
+    return a, b, c
+
+
+def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, device=0, stream=None, lib=None, full=False):
+    """unc_dtw_batch: DTWr94p / DTWr94d (dtw.hpp) of events_list[a] (columns) against kmers_list[a] (rows) for every a, on the GPU.
+    -> (scores float32[n], mean scores float32[n], paths): paths[a] is DTW::get_path() as an (len, 2) uint32 array of (event, k-mer)
+    pairs, end cell first (None with paths=False, and for an alignment whose status is DTW_TOO_LARGE).  full=True returns the
+    DTW_RESULT records (score, mean_score, path_len, status) in place of the first two."""
+    L = lib or load()
+    n = len(events_list)
+    if n != len(kmers_list):
+        raise ValueError("as many k-mer arrays as event arrays are needed")
+    evs = [np.ascontiguousarray(e, dtype=np.float32).ravel() for e in events_list]
+    kms = [np.ascontiguousarray(k, dtype=np.uint16).ravel() for k in kmers_list]
+    ev_off = np.cumsum([0] + [e.size for e in evs]).astype(np.uint64)
+    km_off = np.cumsum([0] + [k.size for k in kms]).astype(np.uint64)
+    ev = np.concatenate(evs) if n else np.zeros(0, np.float32)
+    km = np.concatenate(kms) if n else np.zeros(0, np.uint16)
+    if ev.size == 0:
+        ev = np.zeros(1, np.float32)        # (a valid address for the library's own argument checks)
+    if km.size == 0:
+        km = np.zeros(1, np.uint16)
+    res = np.zeros(n, dtype=DTW_RESULT)
+    path = path_off = None
+    if paths:
+        path_off = np.cumsum([0] + [max(0, e.size + k.size - 1) for e, k in zip(evs, kms)]).astype(np.uint64)
+        path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
+    _check(L, L.unc_dtw_batch(int(device), n, ev.ctypes.data, ev_off.ctypes.data, km.ctypes.data, km_off.ctypes.data, C.byref(params),
+                              int(workspace_bytes), res.ctypes.data, path.ctypes.data if paths else None,
+                              path_off.ctypes.data if paths else None, stream))
+    out_paths = None
+    if paths:
+        out_paths = [None if res["status"][a] == DTW_TOO_LARGE else path[int(path_off[a]):int(path_off[a]) + int(res["path_len"][a])].copy()
+                     for a in range(n)]
+    if full:
+        return res, out_paths
+    return res["score"].copy(), res["mean_score"].copy(), out_paths
+
+
+def dtw_last_timing(lib=None):
+    """(kernel milliseconds, rounds, bytes of back-pointers held at most) of the calling thread's last dtw_batch."""
+    L = lib or load()
+    ms, rounds, nbytes = C.c_float(), C.c_uint32(), C.c_uint64()
+    L.unc_dtw_last_timing(C.byref(ms), C.byref(rounds), C.byref(nbytes))
+    return ms.value, rounds.value, nbytes.value
+
+
+def ref_kmers(index, prefix, rid, st, en, fwd=True):
+    """BwaIndex::get_kmers (bwa_index.hpp:247-255): the 5-mers of bases [st, en) of sequence rid, read from <prefix>.pac;
+    fwd=False: kmers_revcomp of them (bp.hpp:82-99).  Host only."""
+    L = index.L
+    n = C.c_uint64()
+    _check(L, L.unc_ref_kmers(index.h, str(prefix).encode(), int(rid), int(st), int(en), 1 if fwd else 0, None, 0, C.byref(n)))
+    out = np.empty(n.value, dtype=np.uint16)
+    if n.value:
+        _check(L, L.unc_ref_kmers(index.h, str(prefix).encode(), int(rid), int(st), int(en), 1 if fwd else 0, out.ctypes.data, out.size, C.byref(n)))
+    return out
 
 
 def make_calib(n, rng, offset, digitisation):

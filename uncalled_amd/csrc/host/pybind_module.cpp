@@ -9,6 +9,45 @@
 namespace py = pybind11;
 using namespace unc_host;
 
+// DTWr94p / DTWr94d (src/dtw.hpp:188-233, bound in src/pybinder.cpp:72-90): the reference's constructor signature and methods, each a
+// batch of one on device 0.  The entry point is bound weakly: the emulator build of the C ABI the tests link this module against a
+// second time holds the mapper only, and a DTW object made there raises.
+extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
+                             const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
+                             const uint64_t *path_off, void *stream) __attribute__((weak));
+namespace {
+template <uint32_t COST> struct DtwOne {
+    std::vector<std::pair<uint64_t, uint64_t>> path;
+    float score_sum = 0, mean = 0;
+    DtwOne(const std::vector<float> &means, const std::vector<uint16_t> &kmers, const unc_dtw_params_t &prms) {
+        if (!unc_dtw_batch) throw std::runtime_error("this build of the library has no unc_dtw_batch");
+        unc_dtw_params_t p = prms;
+        p.cost = COST;
+        const uint64_t ev_off[2] = {0, means.size()}, km_off[2] = {0, kmers.size()};
+        const uint64_t room = means.size() + kmers.size();
+        const uint64_t path_off[2] = {0, room};
+        std::vector<uint32_t> pairs(2 * room + 2);
+        unc_dtw_result_t r{};
+        const float none_f = 0;
+        const uint16_t none_k = 0;
+        if (unc_dtw_batch(0, 1, means.empty() ? &none_f : means.data(), ev_off, kmers.empty() ? &none_k : kmers.data(), km_off, &p, 0, &r,
+                          pairs.data(), path_off, nullptr) != UNC_OK)
+            throw std::runtime_error(unc_last_error());
+        if (r.status != UNC_DTW_OK) throw std::runtime_error("the alignment does not fit the device's memory");
+        score_sum = r.score; mean = r.mean_score;
+        path.reserve(r.path_len);
+        for (uint64_t k = 0; k < r.path_len; ++k) path.emplace_back(pairs[2 * k], pairs[2 * k + 1]);
+    }
+    std::vector<std::pair<uint64_t, uint64_t>> get_path() const { return path; }
+    float score() const { return score_sum; }
+    float mean_score() const { return mean; }
+};
+template <class T> void bind_dtw(py::class_<T> &c) {
+    c.def(py::init<const std::vector<float> &, const std::vector<uint16_t> &, const unc_dtw_params_t &>())
+        .def("get_path", &T::get_path).def("score", &T::score).def("mean_score", &T::mean_score);
+}
+}  // namespace
+
 // tests link these sources a second time against the lanesim build of the C ABI and load both modules into one process:
 // that copy registers its types module-locally
 #ifdef UNC_PYBIND_LOCAL
@@ -155,4 +194,26 @@ PYBIND11_MODULE(_uncalled_amd, m) {
         .def("add_fast5", &MapPool::add_fast5)
         .def("batch_reads", &MapPool::batch_reads)
         .def("stop", &MapPool::stop);
+
+    py::class_<unc_dtw_params_t>(m, "DTWParams" UNC_ML)
+        .def(py::init([](uint32_t subseq, float dw, float hw, float vw) { return unc_dtw_params_t{subseq, UNC_DTW_R94P, dw, hw, vw}; }),
+             py::arg("subseq") = UNC_DTW_NONE, py::arg("dw") = 2.0f, py::arg("hw") = 1.0f, py::arg("vw") = 100.0f)
+        .def_readwrite("subseq", &unc_dtw_params_t::subseq)      // 0 NONE, 1 ROW, 2 COL (DTWSubSeq; the reference binds no accessor)
+        .def_readwrite("dw", &unc_dtw_params_t::dw)
+        .def_readwrite("hw", &unc_dtw_params_t::hw)
+        .def_readwrite("vw", &unc_dtw_params_t::vw);
+    const unc_dtw_params_t event_glob = UNC_DTW_EVENT_GLOB(UNC_DTW_R94P), event_qsub = UNC_DTW_EVENT_QSUB(UNC_DTW_R94P),
+                           event_rsub = UNC_DTW_EVENT_RSUB(UNC_DTW_R94P), raw_glob = UNC_DTW_RAW_GLOB(UNC_DTW_R94P);
+    m.attr("DTW_EVENT_GLOB") = py::cast(event_glob);
+    m.attr("DTW_RAW_GLOB") = py::cast(raw_glob);
+    m.attr("DTW_EVENT_QSUB") = py::cast(event_qsub);
+    m.attr("DTW_EVENT_RSUB") = py::cast(event_rsub);
+    // deliberate: the reference's module binds these two RAW names to the EVENT presets (src/pybinder.cpp:89-90), and a script
+    // written against it gets the same numbers here; the true RAW presets are UNC_DTW_RAW_QSUB / _RSUB of the C ABI
+    m.attr("DTW_RAW_QSUB") = py::cast(event_qsub);
+    m.attr("DTW_RAW_RSUB") = py::cast(event_rsub);
+    py::class_<DtwOne<UNC_DTW_R94P>> dtw_p(m, "DTWr94p" UNC_ML);
+    bind_dtw(dtw_p);
+    py::class_<DtwOne<UNC_DTW_R94D>> dtw_d(m, "DTWr94d" UNC_ML);
+    bind_dtw(dtw_d);
 }

@@ -1,0 +1,255 @@
+// Host side of the DTW entry points of include/uncalled_hip.h: argument checks, the queue of alignments in descending cell count, the
+// split of a batch into rounds that fit the workspace, and BwaIndex::get_kmers on the packed reference (host only).
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "dtw_dev.h"
+#include "r94_model_table.h"
+#include "unc_host_util.h"
+
+using namespace unc;
+
+// ------------------------------------------------------------------ the template model
+// PoreModel(vector, cmpl=false), pore_model.hpp:58-62,77-103: the arithmetic of build_model (unc_host.cpp), rows not complemented --
+// row k here is row k ^ 0x3FF there.
+static const float *dtw_model_host() {
+    static std::vector<float> tab;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        tab.assign(3 * UNC_NKMER, 0.0f);
+        float *mu = tab.data(), *v2 = mu + UNC_NKMER, *ld = mu + 2 * UNC_NKMER;
+        for (uint32_t k = 0; k < (uint32_t)UNC_NKMER; ++k) {
+            float mean, stdv;
+            memcpy(&mean, &UNC_R94_MEAN_STDV_BITS[2 * k], 4);
+            memcpy(&stdv, &UNC_R94_MEAN_STDV_BITS[2 * k + 1], 4);
+            mu[k] = mean;
+            float tv = 2 * stdv;
+            tv = tv * stdv;
+            v2[k] = tv;
+            ld[k] = (float)log(sqrt(M_PI * (double)v2[k]));
+        }
+    });
+    return tab.data();
+}
+
+extern "C" void unc_dtw_model_tables(float *means1024, float *vars_x2_1024, float *lognorm1024) {
+    const float *t = dtw_model_host();
+    if (means1024) memcpy(means1024, t, UNC_NKMER * 4);
+    if (vars_x2_1024) memcpy(vars_x2_1024, t + UNC_NKMER, UNC_NKMER * 4);
+    if (lognorm1024) memcpy(lognorm1024, t + 2 * UNC_NKMER, UNC_NKMER * 4);
+}
+
+// one copy per device, uploaded by the first batch there and kept for the life of the process
+static constexpr int DTW_MAX_DEVICES = 64;
+static std::mutex g_model_mutex;
+static DevBuf<float> *g_model[DTW_MAX_DEVICES];
+static int dtw_model_device(int device, const float **out) {
+    std::lock_guard<std::mutex> lk(g_model_mutex);
+    if (!g_model[device]) {
+        DevBuf<float> buf;
+        HIPCHK(buf.alloc(3 * UNC_NKMER));
+        HIPCHK(hipMemcpy(buf.p, dtw_model_host(), 3 * UNC_NKMER * sizeof(float), hipMemcpyHostToDevice));
+        g_model[device] = new DevBuf<float>(std::move(buf));
+    }
+    *out = g_model[device]->p;
+    return UNC_OK;
+}
+
+// ------------------------------------------------------------------ batch
+static thread_local float g_last_ms = 0;
+static thread_local uint32_t g_last_rounds = 0;
+static thread_local uint64_t g_last_crumb_bytes = 0;
+
+extern "C" int unc_dtw_last_timing(float *ms_kernel, uint32_t *rounds, uint64_t *crumb_bytes) {
+    if (ms_kernel) *ms_kernel = g_last_ms;
+    if (rounds) *rounds = g_last_rounds;
+    if (crumb_bytes) *crumb_bytes = g_last_crumb_bytes;
+    return UNC_OK;
+}
+
+namespace {
+struct HipEvent {       // (timing only)
+    hipEvent_t e = nullptr;
+    ~HipEvent() { if (e) (void)hipEventDestroy(e); }
+};
+}  // namespace
+
+extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
+                             const uint64_t *km_off, const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res,
+                             uint32_t *path, const uint64_t *path_off, void *stream) {
+    // ---- arguments: everything is checked before the device is touched
+    if (!events || !ev_off || !kmers || !km_off || !prm || !res) return fail(UNC_ERR_ARG, "unc_dtw_batch: null argument");
+    if (path && !path_off) return fail(UNC_ERR_ARG, "unc_dtw_batch: path without path_off");
+    if (device < 0 || device >= DTW_MAX_DEVICES) return fail(UNC_ERR_ARG, "unc_dtw_batch: device %d", device);
+    if (prm->subseq > UNC_DTW_COL) return fail(UNC_ERR_ARG, "unc_dtw_batch: unknown subseq %u", prm->subseq);
+    if (prm->cost > UNC_DTW_R94D) return fail(UNC_ERR_ARG, "unc_dtw_batch: unknown cost %u", prm->cost);
+    g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
+    if (n == 0) return UNC_OK;
+    std::vector<DtwJob> jobs(n);
+    std::vector<uint64_t> cells(n), words(n);
+    for (uint32_t a = 0; a < n; ++a) {
+        if (ev_off[a + 1] <= ev_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u has no events", a);
+        if (km_off[a + 1] <= km_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u has no k-mers", a);
+        if (a && (ev_off[a] < ev_off[a - 1] || km_off[a] < km_off[a - 1])) return fail(UNC_ERR_ARG, "unc_dtw_batch: offsets must ascend");
+        const uint64_t cols = ev_off[a + 1] - ev_off[a], rows = km_off[a + 1] - km_off[a];
+        if (cols >= (1ull << 31) || rows >= (1ull << 31)) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u: 2^31 or more rows or columns", a);
+        if (path && path_off[a + 1] < path_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: path_off must ascend");
+        DtwJob &j = jobs[a];
+        j.ev_off = ev_off[a] - ev_off[0];
+        j.km_off = km_off[a] - km_off[0];
+        j.rows = (uint32_t)rows; j.cols = (uint32_t)cols;
+        j.out = a;
+        const uint64_t room = path ? path_off[a + 1] - path_off[a] : 0;
+        j.path_cap = (uint32_t)std::min<uint64_t>(room, rows + cols - 1);
+        cells[a] = rows * cols;
+        words[a] = dtw_crumb_words(j.rows, j.cols);
+    }
+    const uint64_t n_ev = ev_off[n] - ev_off[0], n_km = km_off[n] - km_off[0];
+    for (uint64_t i = 0; i < n_km; ++i)
+        if (kmers[km_off[0] + i] >= UNC_NKMER) return fail(UNC_ERR_ARG, "unc_dtw_batch: k-mer %u at %llu is not below %d", kmers[km_off[0] + i],
+                                                           (unsigned long long)(km_off[0] + i), UNC_NKMER);
+
+    // ---- device
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (workspace_bytes == 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        workspace_bytes = free_b / 2;
+    }
+    // the queue: descending cell count, so that the longest alignments start first and none sits alone at the tail
+    std::vector<uint32_t> order(n);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells[x] > cells[y]; });
+    std::vector<uint32_t> todo;
+    for (uint32_t a : order) {
+        if (words[a] * 4 > workspace_bytes) {
+            res[a].score = 0; res[a].mean_score = 0; res[a].path_len = 0; res[a].status = UNC_DTW_TOO_LARGE; res[a].pad = 0;
+        } else todo.push_back(a);
+    }
+    if (todo.empty()) return UNC_OK;
+
+    const float *d_model = nullptr;
+    if (int rc = dtw_model_device(device, &d_model)) return rc;
+    DevBuf<float> d_events, d_lines;
+    DevBuf<uint16_t> d_kmers;
+    DevBuf<uint32_t> d_crumbs, d_path, d_next;
+    DevBuf<DtwJob> d_jobs;
+    DevBuf<unc_dtw_result_t> d_res;
+    HIPCHK(d_events.alloc(n_ev)); HIPCHK(d_kmers.alloc(n_km)); HIPCHK(d_res.alloc(n)); HIPCHK(d_next.alloc(1));
+    HIPCHK(hipMemcpyAsync(d_events.p, events + ev_off[0], n_ev * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_kmers.p, kmers + km_off[0], n_km * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+    HipEvent t0, t1;
+    HIPCHK(hipEventCreate(&t0.e)); HIPCHK(hipEventCreate(&t1.e));
+
+    std::vector<DtwJob> round;
+    std::vector<uint32_t> h_path;
+    std::vector<unc_dtw_result_t> h_res;
+    size_t at = 0;
+    while (at < todo.size()) {
+        // a round: the next alignments of the queue whose back-pointers fit the workspace together
+        round.clear();
+        uint64_t w = 0, lines = 0, pairs = 0;
+        while (at < todo.size() && (round.empty() || (w + words[todo[at]]) * 4 <= workspace_bytes)) {
+            DtwJob j = jobs[todo[at]];
+            j.crumb_off = w; j.line_off = lines; j.path_off = pairs;
+            w += words[todo[at]];
+            lines += 2 * dtw_line_floats(j.cols);
+            pairs += j.path_cap;
+            round.push_back(j);
+            ++at;
+        }
+        const uint32_t nr = (uint32_t)round.size();
+        HIPCHK(d_crumbs.reserve(w)); HIPCHK(d_lines.reserve(lines)); HIPCHK(d_jobs.reserve(nr));
+        if (path) HIPCHK(d_path.reserve(std::max<uint64_t>(2 * pairs, 2)));
+        HIPCHK(hipMemcpyAsync(d_jobs.p, round.data(), nr * sizeof(DtwJob), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d_next.p, 0, sizeof(uint32_t), st));
+        DtwBatch b{};
+        b.events = d_events.p; b.kmers = d_kmers.p; b.model = d_model; b.jobs = d_jobs.p; b.n_jobs = nr;
+        b.subseq = prm->subseq; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
+        b.crumbs = d_crumbs.p; b.lines = d_lines.p; b.path = path ? d_path.p : nullptr; b.res = d_res.p; b.next = d_next.p;
+        const uint32_t grid = std::min<uint32_t>(nr, (uint32_t)n_cu * 16u);
+        HIPCHK(hipEventRecord(t0.e, st));
+        launch_dtw(b, prm->cost, grid, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(t1.e, st));
+        h_res.resize(n);
+        h_path.resize(path ? 2 * pairs : 0);
+        // (the results of this round's alignments lie scattered over d_res: the whole array is small)
+        HIPCHK(hipMemcpyAsync(h_res.data(), d_res.p, (size_t)n * sizeof(unc_dtw_result_t), hipMemcpyDeviceToHost, st));
+        if (path && pairs) HIPCHK(hipMemcpyAsync(h_path.data(), d_path.p, 2 * pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, t0.e, t1.e));
+        g_last_ms += ms;
+        g_last_rounds += 1;
+        g_last_crumb_bytes = std::max<uint64_t>(g_last_crumb_bytes, w * 4);
+        for (const DtwJob &j : round) {
+            unc_dtw_result_t r = h_res[j.out];
+            r.mean_score = r.score / (float)r.path_len;          // dtw.hpp:130-132
+            res[j.out] = r;
+            if (path) {
+                const uint64_t got = std::min<uint64_t>(r.path_len, j.path_cap);
+                memcpy(path + 2 * path_off[j.out], h_path.data() + 2 * j.path_off, got * 2 * sizeof(uint32_t));
+            }
+        }
+    }
+    return UNC_OK;
+}
+
+// ------------------------------------------------------------------ BwaIndex::get_kmers
+extern "C" int unc_ref_kmers(const unc_index_t *ix, const char *bwa_prefix, int32_t rid, uint64_t st, uint64_t en, int fwd, uint16_t *out,
+                             uint64_t cap, uint64_t *n) {
+    if (!ix || !bwa_prefix || !n) return fail(UNC_ERR_ARG, "unc_ref_kmers: null argument");
+    if (rid < 0 || rid >= unc_index_n_seqs(ix)) return fail(UNC_ERR_ARG, "unc_ref_kmers: no sequence %d", rid);
+    const uint64_t len = unc_index_seq_len(ix, rid);
+    if (st > en || en > len) return fail(UNC_ERR_ARG, "unc_ref_kmers: [%llu, %llu) is not inside the sequence's %llu bases",
+                                         (unsigned long long)st, (unsigned long long)en, (unsigned long long)len);
+    const uint64_t count = en - st >= UNC_KLEN ? en - st - (UNC_KLEN - 1) : 0;
+    *n = count;
+    if (!out || count == 0) return UNC_OK;
+    if (cap < count) return fail(UNC_ERR_ARG, "unc_ref_kmers: room for %llu k-mers is needed", (unsigned long long)count);
+    uint64_t offset = 0;        // bntann1_t::offset: the sequences lie one after the other in the packed text
+    for (int32_t r = 0; r < rid; ++r) offset += unc_index_seq_len(ix, r);
+    const uint64_t a = offset + st, b = offset + en;
+    // seq_to_kmers, bp.hpp:125-146: bytes [a >> 2, (b >> 2) + 1) of the .pac, four bases a byte, the first base in the top bits; of
+    // the last byte only the b & 3 leading bases (none when b is a multiple of four: the byte is then not read here)
+    const uint64_t pst = a >> 2, pen = (b >> 2) + ((b & 3) ? 1 : 0);
+    std::vector<uint8_t> pac(pen - pst);
+    const std::string fn = std::string(bwa_prefix) + ".pac";
+    FILE *fp = fopen(fn.c_str(), "rb");
+    if (!fp) return fail(UNC_ERR_IO, "cannot read %s", fn.c_str());
+    const bool ok = fseek(fp, (long)pst, SEEK_SET) == 0 && fread(pac.data(), 1, pac.size(), fp) == pac.size();
+    fclose(fp);
+    if (!ok) return fail(UNC_ERR_IO, "%s too short", fn.c_str());
+    uint64_t got = 0, seen = 0;
+    uint16_t kmer = 0;
+    for (uint64_t pos = a; pos < b; ++pos) {
+        const uint8_t base = (pac[(pos >> 2) - pst] >> (((pos & 3) ^ 3) << 1)) & 3;
+        kmer = (uint16_t)(((kmer << 2) & (UNC_NKMER - 1)) | base);            // kmer_neighbor, bp.hpp:106-109
+        if (++seen >= UNC_KLEN) out[got++] = kmer;
+    }
+    if (!fwd) {     // kmers_revcomp, bp.hpp:82-99: reversed order, each k-mer reverse-complemented
+        std::reverse(out, out + got);
+        for (uint64_t i = 0; i < got; ++i) {
+            uint16_t r = (uint16_t)~out[i];
+            r = (uint16_t)(((r >> 2) & 0x3333) | ((r & 0x3333) << 2));
+            r = (uint16_t)(((r >> 4) & 0x0F0F) | ((r & 0x0F0F) << 4));
+            r = (uint16_t)(((r >> 8) & 0x00FF) | ((r & 0x00FF) << 8));
+            out[i] = (uint16_t)(r >> (2 * (8 - UNC_KLEN)));
+        }
+    }
+    return UNC_OK;
+}

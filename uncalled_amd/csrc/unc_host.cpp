@@ -22,24 +22,20 @@
 #include "r94_model_table.h"
 #include "unc_dev_types.h"
 #include "unc_kernels.h"
+#include "unc_host_util.h"
 
 using namespace unc;
 
 // ------------------------------------------------------------------ errors
+// (fail() / HIPCHK and the DevBuf owner of device memory are shared with unc_dtw.cpp: unc_host_util.h)
 static thread_local char g_err[1024] = "";
-static int fail(int code, const char *fmt, ...) {
+int unc::fail(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
     return code;
 }
-#define HIPCHK(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return fail(UNC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                          __FILE__, __LINE__);                                               \
-    } while (0)
 
 extern "C" const char *unc_last_error(void) { return g_err; }
 extern "C" const char *unc_version(void) { return "uncalled_hip 0.2 (gfx950)"; }
@@ -68,38 +64,6 @@ extern "C" void unc_params_default(unc_params_t *p) {
     // read_buffer.cpp:26-32
     p->bp_per_sec = 450.0f; p->sample_rate = 4000.0f; p->chunk_time = 1.0f; p->max_chunks = 1000000;
 }
-
-// ------------------------------------------------------------------ device memory
-// The one owner of device memory in this file (PlacementSpacer apart, which holds untyped memory for a moment).  Pointer and capacity
-// travel together: p == nullptr exactly when cap == 0; the destructor frees; a move leaves the source empty.  `cap` counts the elements
-// the holder may use; `slack` more elements may lie behind them that belong to the allocation and not to the capacity (the raw signal's
-// 64 samples past the end).
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    DevBuf &operator=(DevBuf &&o) noexcept {
-        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    // a fresh allocation of (n + slack) * sizeof(T) bytes (n == 0: one element); whatever was held is freed first
-    hipError_t alloc(size_t n, size_t slack = 0) {
-        release();
-        if (!n) n = 1;
-        const hipError_t e = hipMalloc((void **)&p, (n + slack) * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = n;
-        return hipSuccess;
-    }
-    // grows only.  A growth that fails leaves the buffer EMPTY (cap 0), never a capacity without memory behind it: the next call
-    // allocates again
-    hipError_t reserve(size_t n, size_t slack = 0) { return n <= cap ? hipSuccess : alloc(n, slack); }
-};
 
 // ------------------------------------------------------------------ index
 struct SeqAnn { std::string name; uint64_t offset, len; };
