@@ -16,9 +16,13 @@ float dtw_check_cost(uint32_t cost, const float *model, uint32_t k, float e) {
     return -(float)q;
 }
 
-/* path: room for rows + cols - 1 pairs (event j, k-mer i), end cell first.  Returns 0, or -1 without memory. */
+/* path: room for rows + cols - 1 pairs (event j, k-mer i), end cell first.  end_min_cells, last_is_min (either may be null): how
+ * many cells of the line the end-cell search scans (ROW: the last column, COL: the last row; NONE scans nothing: 0) equal its
+ * smallest value, and whether the matrix's last cell is one of them -- the premise of the tests of ties at the end cell.
+ * Returns 0, or -1 without memory. */
 int dtw_check(const float *ev, uint64_t cols, const uint16_t *km, uint64_t rows, const float *model, uint32_t subseq, uint32_t cost,
-              float dw, float hw, float vw, float *score, uint64_t *path_len, uint32_t *path, uint64_t *ties) {
+              float dw, float hw, float vw, float *score, uint64_t *path_len, uint32_t *path, uint64_t *ties, uint64_t *end_min_cells,
+              uint32_t *last_is_min) {
     const float MAXC = FLT_MAX / 2.0f;
     uint8_t *mv = malloc(rows * cols);
     float *prev = malloc(cols * sizeof(float)), *cur = malloc(cols * sizeof(float)), *lastcol = malloc(rows * sizeof(float));
@@ -50,6 +54,19 @@ int dtw_check(const float *ev, uint64_t cols, const uint16_t *km, uint64_t rows,
     if (subseq == SUB_ROW) { for (uint64_t k = 0; k < rows; ++k) if (lastcol[k] < lastcol[i]) i = k; *score = lastcol[i]; }
     else if (subseq == SUB_COL) { for (uint64_t k = 0; k < cols; ++k) if (prev[k] < prev[j]) j = k; *score = prev[j]; }
     else *score = prev[j];
+    {   /* (a NaN is neither the minimum nor equal to it) */
+        const float *scan = subseq == SUB_ROW ? lastcol : prev;
+        const uint64_t n_scan = subseq == SUB_ROW ? rows : subseq == SUB_COL ? cols : 0;
+        float mn = 0;
+        uint64_t n_min = 0;
+        for (uint64_t k = 0; k < n_scan; ++k) {
+            if (scan[k] != scan[k]) continue;
+            if (n_min == 0 || scan[k] < mn) { mn = scan[k]; n_min = 1; }
+            else if (scan[k] == mn) ++n_min;
+        }
+        if (end_min_cells) *end_min_cells = n_min;
+        if (last_is_min) *last_is_min = n_scan > 0 && n_min > 0 && scan[n_scan - 1] == mn;
+    }
     uint64_t n = 0;
     path[2 * n] = (uint32_t)j; path[2 * n + 1] = (uint32_t)i; ++n;
     while (!((i == 0 || subseq == SUB_ROW) && (j == 0 || subseq == SUB_COL))) {

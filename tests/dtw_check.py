@@ -28,7 +28,8 @@ class Checker:
             subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", str(so), str(HERE / "dtw_check.c"), "-lm"], check=True)
             L = C.CDLL(str(so))
             L.dtw_check.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
-                                    C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)]
+                                    C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint32)]
             L.dtw_check_cost.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_float]
             L.dtw_check_cost.restype = C.c_float
             Checker._lib = L
@@ -42,13 +43,16 @@ class Checker:
         return np.float32(self._lib.dtw_check_cost(cost, self.model.ctypes.data, int(k), float(np.float32(e))))
 
     def dtw(self, events, kmers, subseq, cost, dw, hw, vw):
+        """-> score, score_bits, mean, path_len, path (end cell first, (event, k-mer) pairs), ties (cells whose smallest move is
+        not alone), and of the line the end-cell search scans (ROW: last column, COL: last row): end_min_cells, how many of its cells
+        equal its minimum, and last_is_min, whether the matrix's last cell is one of them (NONE: 0, False)"""
         ev = np.ascontiguousarray(events, np.float32)
         km = np.ascontiguousarray(kmers, np.uint16)
         path = np.empty((ev.size + km.size - 1, 2), np.uint32)
-        score, n, ties = C.c_float(), C.c_uint64(), C.c_uint64()
+        score, n, ties, n_min, last_min = C.c_float(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
         rc = self._lib.dtw_check(ev.ctypes.data, ev.size, km.ctypes.data, km.size, self.model.ctypes.data, subseq, cost, dw, hw, vw,
-                                 C.byref(score), C.byref(n), path.ctypes.data, C.byref(ties))
+                                 C.byref(score), C.byref(n), path.ctypes.data, C.byref(ties), C.byref(n_min), C.byref(last_min))
         assert rc == 0
         s = np.float32(score.value)
         return dict(score=s, score_bits=int(s.view(np.uint32)), mean=np.float32(s / np.float32(n.value)), path_len=int(n.value),
-                    path=path[:n.value].copy(), ties=int(ties.value))
+                    path=path[:n.value].copy(), ties=int(ties.value), end_min_cells=int(n_min.value), last_is_min=bool(last_min.value))

@@ -1,6 +1,17 @@
 """CPU: the DTW feature below the GPU -- the checker (tests/dtw_check.c) against the committed reference results, the C ABI's
 declarations and exports, BwaIndex::get_kmers on the example index, and k_dtw.hip itself under the lanesim emulator (built by
-tests/lanesim/Makefile.dtw, a make file of its own: the emulator suite's library does not hold the DTW sources)."""
+tests/lanesim/Makefile.dtw, a make file of its own: the emulator suite's library does not hold the DTW sources).
+
+The emulator cases past the goldens come from tests/dtw_cases.py, in sizes the emulator can take; tests/test_gpu_dtw.py runs the
+full ones (and those only a GPU can hold: indices past 2^16, 4 GiB of back-pointers, two threads).  Measured on the build
+container, one process: test_kernel_under_the_emulator_equals_every_golden 8.7 s at the parent commit (7.6 s in the same run as
+the following); more alignments than wavefronts 5.5 s, ties at the end cell 2.1 s, ties in every cell and non-finite events 1.3 s,
+caller's offsets 0.2 s.  The tests of ties at the end cell, of the caller's offsets and of non-finite events were each seen to
+fail under the emulator with the defect they aim at put into k_dtw.hip / unc_dtw.cpp by hand and taken out again (an end cell
+chosen by lane or with <=, a base offset ignored, a NaN kept as a lane's candidate).  A row index cut to 16 bits was seen to fail
+a 66000 x 1 alignment in a run under the emulator made by hand once: no committed emulator test reaches an index of 2^16 (the GPU
+file's do), so nothing here repeats that.  For the test of more alignments than wavefronts no defect was put in: it holds the
+queue loop as it is (a wavefront's state left over from its previous alignment would show as a wrong result)."""
 import ctypes
 import re
 from pathlib import Path
@@ -8,6 +19,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import dtw_cases as dc
 from conftest import EX_PREFIX, GOLD, ROOT, locked_make
 from dtw_check import Checker
 
@@ -27,6 +39,11 @@ def sim_dtw_lib():
     from uncalled_amd import capi
     locked_make("-C", str(ROOT / "tests" / "lanesim"), "-f", "Makefile.dtw")
     return capi.load(ROOT / "tests" / "lanesim" / "_build_dtw" / "libuncalled_sim_dtw.so")
+
+
+@pytest.fixture(scope="module")
+def means(checker):
+    return checker.model[:1024]
 
 
 def case(gold, a):
@@ -144,3 +161,64 @@ def test_argument_errors_under_the_emulator(sim_dtw_lib):
                           ([ev], [km], capi.DTWParams(0, 2, 1, 1, 1))):
         with pytest.raises(capi.UncalledHipError, match="error -1"):
             capi.dtw_batch(evs, kms, prm, lib=sim_dtw_lib)
+
+
+def test_checker_counts_the_minimal_cells_of_the_line_it_scans(checker, means):
+    """one event on the mean of k-mer `a`, r94d: the last column (ROW) is |mean(k) - mean(a)| row by row"""
+    a, b, c = (int(k) for k in np.argsort(means)[[100, 500, 900]])
+    ev = means[[a]]
+    for km, n_min, last in (([a, b, a, c, a], 3, True), ([a, b, a, c], 2, False), ([b, c, b], 2, True), ([c], 1, True)):
+        r = checker.dtw(ev, np.array(km, np.uint16), dc.ROW, dc.R94D, 1, 1, 1)
+        assert (r["end_min_cells"], r["last_is_min"]) == (n_min, last), km
+        assert tuple(r["path"][0]) == (0, len(km) - 1 if last else km.index(a)), km
+        r = checker.dtw(means[km], np.array([a], np.uint16), dc.COL, dc.R94D, 1, 1, 1)      # the mirror image
+        assert (r["end_min_cells"], r["last_is_min"]) == (n_min, last), km
+        assert tuple(r["path"][0]) == (len(km) - 1 if last else km.index(a), 0), km
+        r = checker.dtw(ev, np.array(km, np.uint16), dc.NONE, dc.R94D, 1, 1, 1)
+        assert (r["end_min_cells"], r["last_is_min"]) == (0, False)
+    nan = np.array([np.nan], np.float32)        # a line of NaN has no minimum
+    r = checker.dtw(nan, np.array([a, b], np.uint16), dc.ROW, dc.R94D, 1, 1, 1)
+    assert (r["end_min_cells"], r["last_is_min"]) == (0, False) and tuple(r["path"][0]) == (0, 1)
+
+
+@pytest.mark.lanesim
+def test_more_alignments_than_wavefronts_under_the_emulator(checker, means, sim_dtw_lib):
+    """200 alignments of at most 40 x 40 on the emulator's grid of 16 x 4 wavefronts, in every subseq x cost: a wavefront goes
+    round the queue loop of k_dtw more than once"""
+    from uncalled_amd import capi
+    for b in dc.queue_batches(means, 200, 50, 40):
+        assert len(b["evs"]) > 16 * 4
+        dc.check(checker, b, lib=sim_dtw_lib)
+        assert capi.dtw_last_timing(sim_dtw_lib)[1] == 1
+
+
+@pytest.mark.lanesim
+def test_offsets_as_a_caller_may_give_them_under_the_emulator(checker, means, sim_dtw_lib):
+    dc.check_caller_offsets(sim_dtw_lib, checker, means)
+    dc.check_no_paths_with_a_too_large_member(checker, means, lib=sim_dtw_lib)
+
+
+@pytest.mark.lanesim
+def test_ties_at_the_end_cell_under_the_emulator(checker, means, sim_dtw_lib):
+    for b in dc.end_tie_batches(means):
+        res, paths, want = dc.check(checker, b, lib=sim_dtw_lib)
+        dc.assert_end_ties(b, want)
+        assert [tuple(int(x) for x in p[0]) for p in paths] == b["end"], b["name"]
+
+
+@pytest.mark.lanesim
+def test_ties_in_every_cell_and_events_that_are_no_numbers_under_the_emulator(checker, means, sim_dtw_lib):
+    rows, cols = 150, 130
+    for b in dc.zero_weight_batches(means, rows, cols):
+        _, _, want = dc.check(checker, b, lib=sim_dtw_lib)
+        # (99 % at the GPU file's 1000 x 900; at 150 x 130 the first row and column, next to the border's MAX_COST, are 1.4 % of the cells)
+        assert want[0]["ties"] > 0.95 * rows * cols, b["name"]
+    for b in dc.rounded_batches(means, rows, cols, 1.0):
+        _, _, want = dc.check(checker, b, lib=sim_dtw_lib)
+        assert want[0]["ties"] >= 0.01 * rows * cols, b["name"]
+    for b in dc.nonfinite_batches(means, rows, cols):
+        dc.check(checker, b, lib=sim_dtw_lib)
+    b = dc.nan_before_the_end_batch(means)
+    _, paths, want = dc.check(checker, b, lib=sim_dtw_lib)
+    assert want[0]["score"] == 0.0 and want[0]["end_min_cells"] == 1 and not want[0]["last_is_min"]
+    assert tuple(int(x) for x in paths[0][0]) == b["end"][0]

@@ -1,16 +1,19 @@
 """GPU: unc_dtw_batch (k_dtw.hip) against the reference's committed results (tests/golden/dtw_goldens.npz, bit for bit) and, for
 sizes the goldens cannot hold, against the CPU checker (tests/dtw_check.c), which reproduces every golden (tests/test_dtw_cpu.py).
-Measured on an MI355X box: the file takes 5 s, 3 s of it the CPU checker on the mixed batch (6 x 68 M cells)."""
+The cases past the goldens' reach come from tests/dtw_cases.py, which tests/test_dtw_cpu.py runs in small under the emulator.
+Measured on an MI355X box (profiles/dtw_tests_first_run.txt): the file takes 8.5 s, 3 s of it the CPU checker on the mixed batch
+(6 x 68 M cells), 1.3 s the indices past 2^16 and 1.0 s the 4 GiB round (their checker runs above all).  The 4 GiB round: 720
+alignments near 6000 x 4000, kernel 95.8 ms (one such alignment alone: 88 ms), 1 round, 4 413 818 880 bytes of back-pointers held:
+byte quantities past 2^32, word offsets (DtwJob::crumb_off) not."""
 import numpy as np
 import pytest
 
+import dtw_cases as dc
 from conftest import EX_PREFIX, GOLD
+from dtw_cases import COMBOS, WEIGHTS, assert_equal_to_checker, crumb_bytes
 from dtw_check import Checker
 
 pytestmark = pytest.mark.gpu
-
-COMBOS = [(s, c) for s in (0, 1, 2) for c in (0, 1)]
-WEIGHTS = {0: (2.0, 1.0, 100.0), 1: (10.0, 1.0, 1000.0), 2: (1.0, 1.0, 1.0)}      # one set of weights per mode
 
 
 @pytest.fixture(scope="module")
@@ -32,8 +35,9 @@ def gold_case(gold, a):
     return ev, km, prm, path
 
 
-def crumb_bytes(rows, cols):
-    return 4 * 64 * ((rows + 63) // 64) * ((cols + 63 + 15) // 16)
+@pytest.fixture(scope="module")
+def means(checker):
+    return checker.model[:1024]
 
 
 @pytest.fixture(scope="module")
@@ -61,22 +65,6 @@ def mixed():
 def mixed_want(mixed, checker):
     evs, kms = mixed
     return {(s, c): [checker.dtw(e, k, s, c, *WEIGHTS[s]) for e, k in zip(evs, kms)] for s, c in COMBOS}
-
-
-def assert_equal_to_checker(res, paths, want, skip=()):
-    from uncalled_amd import capi
-    compared = 0
-    for a, w in enumerate(want):
-        if a in skip:
-            continue
-        assert res["status"][a] == capi.DTW_OK, a
-        assert int(res["score"][a:a + 1].view(np.uint32)[0]) == w["score_bits"], (a, res["score"][a], w["score"])
-        assert int(res["mean_score"][a:a + 1].view(np.uint32)[0]) == int(w["mean"].view(np.uint32)), a
-        assert int(res["path_len"][a]) == w["path_len"], a
-        if paths is not None:
-            assert np.array_equal(paths[a], w["path"]), a
-        compared += 1
-    assert compared == len(want) - len(skip)
 
 
 def test_every_golden_through_the_c_abi(hip_lib, gold):
@@ -229,3 +217,111 @@ def test_argument_errors_leave_the_gpu_untouched(hip_lib):
             capi.dtw_batch(evs, kms, prm, device=63)      # (no such device: a call that reached the runtime would fail with a HIP error)
     scores, _, _ = capi.dtw_batch([ev], [km], capi.DTW_EVENT_GLOB)      # and the next good call works
     assert np.isfinite(scores[0])
+
+
+def test_more_alignments_than_wavefronts(hip_lib, checker, means):
+    """3 x (16 x CUs) + 17 alignments cycling 256 small cases, in every subseq x cost: the launch has 16 x CUs wavefronts, so each
+    goes round the queue loop of k_dtw about three times"""
+    import torch
+    from uncalled_amd import capi
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 3 * 16 * cus + 17
+    for b in dc.queue_batches(means, n, 256, 200):
+        assert len(b["evs"]) == n > 16 * cus
+        dc.check(checker, b)
+        ms, rounds, _ = capi.dtw_last_timing()
+        print(f"{b['name']}: {n} alignments on {16 * cus} wavefronts, kernel {ms:.2f} ms, {rounds} round(s)")
+        assert rounds == 1
+
+
+def test_row_and_column_indices_past_65536(hip_lib, checker, means):
+    from uncalled_amd import capi
+    for b in dc.long_index_batches(means):
+        want = dc.wanted(checker, b)
+        dc.assert_long_indices_used(b, want)
+        res, paths = dc.run(b)
+        print(f"{b['name']}: kernel {capi.dtw_last_timing()[0]:.2f} ms")
+        assert_equal_to_checker(res, paths, want)
+
+
+def test_more_than_4_gib_of_back_pointers_in_one_round(hip_lib, checker, means):
+    """720 alignments near 6000 x 4000 in a workspace of exactly their sum, 4.41 GB: the BYTE quantities of the round planner (`w * 4`
+    against the workspace, the bytes held, the size of the allocation) pass 2^32.  DtwJob::crumb_off counts 32-bit words and stays
+    near 1.1e9 here: its width is NOT held by this or any test (a round of about 2880 such alignments, 17.7 GB, would)."""
+    from uncalled_amd import capi
+    b = dc.big_round_batch(means)
+    assert len(b["evs"]) == 720 and b["workspace"] > 2**32
+    want = dc.wanted(checker, b)
+    res, paths = dc.run(b, workspace_bytes=b["workspace"])
+    ms, rounds, held = capi.dtw_last_timing()
+    print(f"big round: {len(b['evs'])} alignments, kernel {ms:.2f} ms, {rounds} round(s), {held} bytes of back-pointers held")
+    assert rounds == 1 and held == b["workspace"] and held > 2**32
+    assert_equal_to_checker(res, paths, want)
+
+
+def test_offsets_as_a_caller_may_give_them(hip_lib, checker, means):
+    from uncalled_amd import capi
+    dc.check_caller_offsets(capi.load(), checker, means)
+    dc.check_no_paths_with_a_too_large_member(checker, means)
+
+
+def test_ties_at_the_end_cell(hip_lib, checker, means):
+    for b in dc.end_tie_batches(means):
+        res, paths, want = dc.check(checker, b)
+        dc.assert_end_ties(b, want)
+        assert [tuple(int(x) for x in p[0]) for p in paths] == b["end"], b["name"]
+
+
+def test_ties_in_every_cell_and_events_that_are_no_numbers(hip_lib, checker, means):
+    for b in dc.zero_weight_batches(means, 1000, 900):
+        _, _, want = dc.check(checker, b)
+        assert want[0]["ties"] > 0.99 * 1000 * 900, b["name"]
+    for b in dc.rounded_batches(means, 1000, 900, 1.0):
+        _, _, want = dc.check(checker, b)
+        assert want[0]["ties"] >= 0.01 * 1000 * 900, b["name"]
+    for rows, cols in ((200, 200), (150, 130)):
+        for b in dc.nonfinite_batches(means, rows, cols):
+            dc.check(checker, b)
+    b = dc.nan_before_the_end_batch(means)
+    _, paths, want = dc.check(checker, b)
+    assert want[0]["score"] == 0.0 and want[0]["end_min_cells"] == 1 and not want[0]["last_is_min"]
+    assert tuple(int(x) for x in paths[0][0]) == b["end"][0]
+
+
+def test_two_threads_each_on_a_stream_of_its_own(hip_lib, mixed, mixed_want):
+    """unc_dtw_batch from two threads at once: one held to the largest alignment's workspace (3 rounds or more), one free (1 round).
+    Each gets the checker's results, and unc_dtw_last_timing tells each thread of its own call.  What this holds is the
+    thread_local timing and the buffers of each call; the model's first upload behind its mutex is NOT raced, since the tests
+    above have uploaded it long before."""
+    import threading
+    import torch
+    from uncalled_amd import capi
+    evs, kms = mixed
+    biggest = max(crumb_bytes(k.size, e.size) for e, k in zip(evs, kms))
+    prm = capi.DTWParams(1, 1, *WEIGHTS[1])
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    barrier = threading.Barrier(2, timeout=60)
+    out = [None, None]
+
+    def work(t, ws):
+        try:
+            barrier.wait()
+            res, paths = capi.dtw_batch(evs, kms, prm, workspace_bytes=ws, stream=streams[t].cuda_stream, full=True)
+            out[t] = (res, paths, capi.dtw_last_timing())
+        except BaseException as e:      # (reported by the asserts below)
+            out[t] = e
+
+    total = sum(crumb_bytes(k.size, e.size) for e, k in zip(evs, kms))
+    threads = [threading.Thread(target=work, args=(0, biggest)), threading.Thread(target=work, args=(1, 0))]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join(300)
+        assert not th.is_alive()
+    for t in (0, 1):
+        assert isinstance(out[t], tuple), out[t]
+        assert_equal_to_checker(out[t][0], out[t][1], mixed_want[(1, 1)])
+    (_, rounds0, held0), (_, rounds1, held1) = out[0][2], out[1][2]
+    print(f"two threads: rounds {rounds0} and {rounds1}, bytes held {held0} and {held1}")
+    assert rounds0 >= 3 and held0 <= biggest
+    assert rounds1 == 1 and held1 == total

@@ -64,7 +64,11 @@ template <int COST> __device__ void dtw_one(const DtwBatch &B, const DtwJob &J) 
     const uint32_t n_strips = (uint32_t)dtw_strips(rows), n_blocks = (uint32_t)dtw_step_blocks(cols);
     const uint32_t n_steps = cols + 63;
 
-    float best_v = 0.0f;                    // ROW: the first smallest score of the last column among this lane's rows
+    // ROW: the first smallest score of the last column among this lane's rows.  A candidate is a score that compared smaller, as in
+    // the reference's scan, here and in the COL scan below.  Only there can it matter: a NaN event makes its whole column NaN and
+    // no other, so the last column holds NaN in every row or in none, while the last row may hold one in a lane's first cell,
+    // where no later comparison could replace it
+    float best_v = INFINITY;
     uint32_t best_i = DTW_NONE_IDX;
     float last_score = 0.0f;                // the matrix's last cell
     const float *last_row = line0;
@@ -123,7 +127,7 @@ template <int COST> __device__ void dtw_one(const DtwBatch &B, const DtwJob &J) 
                 }
             }
         }
-        if (row_mode && row_ok && (best_i == DTW_NONE_IDX || cur < best_v)) { best_v = cur; best_i = i; }     // cur = M(i, cols - 1)
+        if (row_mode && row_ok && cur < best_v) { best_v = cur; best_i = i; }     // cur = M(i, cols - 1)
         if (s == n_strips - 1) { last_score = lane_value(cur, last_lane); last_row = lout; }
         // lanes read what other lanes wrote: the line in the next strip, the back-pointers in the traceback
         __threadfence();
@@ -136,11 +140,11 @@ template <int COST> __device__ void dtw_one(const DtwBatch &B, const DtwJob &J) 
         wave_first_min(best_v, best_i);
         if (best_i != DTW_NONE_IDX && best_v < last_score) { score = best_v; ei = best_i; }
     } else if (col_mode) {
-        float bv = 0.0f;
+        float bv = INFINITY;
         uint32_t bj = DTW_NONE_IDX;
         for (uint32_t j = lane; j < cols; j += 64) {
             const float v = last_row[j];
-            if (bj == DTW_NONE_IDX || v < bv) { bv = v; bj = j; }
+            if (v < bv) { bv = v; bj = j; }
         }
         wave_first_min(bv, bj);
         if (bj != DTW_NONE_IDX && bv < last_score) { score = bv; ej = bj; }
