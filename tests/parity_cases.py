@@ -202,6 +202,26 @@ def case_read_order_t1(lib, oracle_lib, example, goldens, max_paths, n_reads, sp
     assert_hits_equal(m.map_batch(raw, off, cal), indep, "independent order")
 
 
+def case_read_order_t1_under_pressure(lib, oracle_lib, example, goldens, n_reads=6):
+    """UNC_ORDER_T1 with a node pool of ONE chunk and an allowance of four nodes per read: reads overflow in the first pass AND when they
+    are mapped again inside a carry-over round, so the overflow handling runs on the re-mapped reads of a `-t 1` round (its `subset`
+    form, which neither case_read_order_t1 -- a roomy pool -- nor case_cluster_pool_pressure -- the independent order -- reaches).  One
+    batch, every field against the oracle with a shared mapper; both premises are checked."""
+    dev_index = _index(lib, example)
+    p = capi.default_params(dev_index.L)
+    p.max_paths = 97
+    off_all = goldens["sim_offsets"]
+    raw = goldens["sim_signal"][:int(off_all[n_reads])]
+    off = off_all[:n_reads + 1].copy()
+    cal = capi.make_calib(n_reads, CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION)
+    want = oracle_hits(oracle_lib.Index(example["prefix"]), raw, off, cal, to_oracle_params(p), fresh_mapper_per_read=False)
+    m = capi.Mapper(dev_index, params=p, n_slots=3, n_waves=3, pool_chunks=1, max_clusters=16)
+    m.set_read_order(capi.ORDER_T1)
+    hits = m.map_batch(raw, off, cal)
+    assert_hits_equal(hits, want, "-t 1 order under pool pressure")
+    assert m.last_remap()[0] > 0 and m.last_carry_over()[0] > 0, (m.last_remap(), m.last_carry_over())
+
+
 def case_trace_matches_oracle_every_event(lib, oracle_lib, example, goldens, dev_index=None, raw=None, cal=None):
     """Path buffer (order, ranges, k-mers, prob-sum windows, flags) and the seed-cluster set after every map_next."""
     dev_index = dev_index or _index(lib, example)

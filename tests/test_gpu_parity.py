@@ -48,6 +48,10 @@ def test_read_order_t1(hip_lib, oracle_lib, example, goldens, max_paths, n_reads
     pc.case_read_order_t1(hip_lib, oracle_lib, example, goldens, max_paths, n_reads, split)
 
 
+def test_read_order_t1_under_pressure(hip_lib, oracle_lib, example, goldens):
+    pc.case_read_order_t1_under_pressure(hip_lib, oracle_lib, example, goldens)
+
+
 def test_trace_matches_oracle_every_event(hip_lib, oracle_lib, example, goldens):
     pc.case_trace_matches_oracle_every_event(hip_lib, oracle_lib, example, goldens)
 

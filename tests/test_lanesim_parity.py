@@ -87,6 +87,10 @@ def test_read_order_t1(sim_lib, oracle_lib, example, goldens, max_paths, n_reads
     pc.case_read_order_t1(sim_lib, oracle_lib, example, goldens, max_paths, n_reads, split)
 
 
+def test_read_order_t1_under_pressure(sim_lib, oracle_lib, example, goldens):
+    pc.case_read_order_t1_under_pressure(sim_lib, oracle_lib, example, goldens)
+
+
 def test_trace_matches_oracle_every_event(sim_lib, oracle_lib, example, goldens):
     pc.case_trace_matches_oracle_every_event(sim_lib, oracle_lib, example, goldens)
 

@@ -2369,18 +2369,9 @@ __global__ __launch_bounds__(64 * W, UNC_LB) void k_map_team(MapArgs Aval) {
 
 #include "unc_kernels.h"
 namespace unc {
-void launch_map(const DevIndex &ix, const DevScratch &sc, const DevReads &rd, const unc_params_t &P, DevResult *results,
-                uint32_t *next_read, uint32_t max_steps, uint32_t resume, const uint32_t *slot_map, uint32_t grid, hipStream_t st,
-                const DevPool &pool, const uint32_t *read_list, unsigned long long *wave_ticks, const DevSched *sched, bool profile,
-                const uint32_t *flags_in, uint32_t *flags_out, uint32_t team) {
-    MapArgs a;
-    a.flags_in = flags_in; a.flags_out = flags_out;
-    if (sched) a.sched = *sched; else { a.sched.ctl = nullptr; a.sched.free_cells = a.sched.park_cells = nullptr; a.sched.cap_mask = a.sched.n_slots = 0; }
-    a.ix = ix; a.sc = sc; a.rd = rd; a.P = P; a.results = results; a.next_read = next_read;
-    a.max_steps = max_steps; a.resume = resume; a.slot_map = slot_map; a.read_list = read_list; a.wave_ticks = wave_ticks;
-    a.pool = pool;
-    const bool narrow = ix.key_len_bits != 0;
-    if (team > 1 && resume && rd.ring_mod) {
+void launch_map(const MapArgs &a, uint32_t grid, hipStream_t st, bool profile, uint32_t team) {
+    const bool narrow = a.ix.key_len_bits != 0;
+    if (team > 1 && a.resume && a.rd.ring_mod) {
         // the chunked path with a team of wavefronts per channel (k_map_team): 2, 4 or 8
 #define UNC_TEAM_LAUNCH(P_, N_, W_) hipLaunchKernelGGL((k_map_team<P_, N_, W_>), dim3(grid), dim3(WAVE * W_), 0, st, a)
         if (team >= 8) { if (profile) { if (narrow) UNC_TEAM_LAUNCH(true, true, 8); else UNC_TEAM_LAUNCH(true, false, 8); }

@@ -247,4 +247,23 @@ struct alignas(16) DevResult {
     uint64_t cyc[12];  // shader-clock cycles per phase: P, E(rest), S, W, F, T(sa), T(add_seed), G, E1, E2, E3, E4
 };
 
+// The argument block of k_map / k_map_team: what ONE launch is.  A caller names what its launch needs; the rest keeps its default.
+struct MapArgs {
+    DevIndex ix;
+    DevScratch sc;
+    DevReads rd;
+    unc_params_t P;
+    DevResult *results = nullptr;
+    uint32_t *next_read = nullptr;    // work-queue head
+    uint32_t max_steps = 0xFFFFFFFFu; // map_next calls per launch (0xFFFFFFFF = run to completion)
+    uint32_t resume = 0;              // 1: continue the read saved in SlotState (trace / chunked mode)
+    const uint32_t *read_list = nullptr;  // batch mode: the queue hands out read_list[t] instead of t (re-runs of selected reads)
+    const uint32_t *slot_map = nullptr;   // resume mode: block b works on scratch slot slot_map[b] (null: slot = b), descriptor b
+    unsigned long long *wave_ticks = nullptr;   // optional: sum over waves of (exit - start) in wall_clock64 ticks (queue-tail probe)
+    const uint32_t *flags_in = nullptr;   // batch mode, optional: sources_added_ a read STARTS with, [read][NKMER / 32] (null: clear)
+    uint32_t *flags_out = nullptr;        // batch mode, optional: sources_added_ as the read leaves it, same shape
+    DevSched sched{};           // batch mode with sched.ctl != null: slots are handed out per task, max_steps = slice length
+    DevPool pool;               // nodes of the seed-cluster grids
+};
+
 }  // namespace unc

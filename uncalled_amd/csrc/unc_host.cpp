@@ -500,7 +500,7 @@ struct unc_mapper {
         bool active = false;
         uint32_t n_reads = 0, grid = 0;
         hipStream_t st = nullptr;
-        DevReads rd{};
+        MapArgs args{};                  // the first pass's launch; a re-map round launches a copy of it with a read list (remap_round)
         bool t1 = false;
         std::vector<uint64_t> lens;      // samples per read (fill_hit)
     } pend;
@@ -947,6 +947,16 @@ extern "C" int unc_mapper_pool_usage(const unc_mapper_t *m, uint32_t *out4) {
     return UNC_OK;
 }
 
+constexpr size_t FW = NKMER / 32;      // words of one read's sources_added_ bitmap
+typedef std::array<uint32_t, FW> Flags;
+
+// a launch of k_map on the mapper's own index, slots, pool, result array and queue head
+static MapArgs mapper_args(const unc_mapper *m, const DevReads &rd) {
+    MapArgs a;
+    a.ix = m->ix->dev; a.sc = m->sc.v; a.rd = rd; a.P = m->P; a.pool = m->pool.v; a.results = m->d_results.p; a.next_read = m->d_next.p;
+    return a;
+}
+
 // A batch in two halves: _begin stages the reads and launches the kernels on the stream and returns; _end waits for them, maps the few
 // reads again that need it, and fills the hits.  Between the two the host is free -- and so is the GPU's tail: the persistent k_map
 // ends with a few long reads on a few wavefronts (wavefronts alive 94 % of a 50 k-read E. coli launch), and a second mapper's batch,
@@ -960,15 +970,16 @@ extern "C" int unc_map_batch_begin(unc_mapper_t *m, uint32_t n_reads, const int1
     DevReads rd;
     int rc = stage_batch(m, n_reads, raw, offsets, calib, on_device, st, &rd);
     if (rc) return rc;
+    MapArgs a = mapper_args(m, rd);
     HIPCHK(hipMemsetAsync(m->d_next.p, 0, 16, st));   // [0] queue head, [2..3] wave-lifetime ticks
+    a.wave_ticks = reinterpret_cast<unsigned long long *>(m->d_next.p + 2);
     HIPCHK(hipEventRecord(m->ev[0], st));
     launch_events(rd, m->P, st, m->ev_rpw);
     HIPCHK(hipEventRecord(m->ev[1], st));
     const uint32_t grid = n_reads < m->n_waves ? n_reads : m->n_waves;
     const bool sliced = m->sched.v.ctl != nullptr && n_reads > m->n_waves;
-    if (sliced) launch_sched_init(m->sched.v, st);
+    if (sliced) { launch_sched_init(m->sched.v, st); a.sched = m->sched.v; a.max_steps = m->slice_events; }
     launch_pool_init(m->pool.v, st);       // every chunk free: nothing outlives a batch
-    constexpr size_t FW = NKMER / 32;      // words of one read's sources_added_ bitmap
     const bool t1 = m->read_order == UNC_ORDER_T1;
     if (t1) {
         if ((size_t)n_reads * FW > m->d_flags_out.cap) {      // (both freed, then both allocated; d_flags_out last: its capacity is that of the two)
@@ -978,32 +989,21 @@ extern "C" int unc_map_batch_begin(unc_mapper_t *m, uint32_t n_reads, const int1
         }
         HIPCHK(hipMemsetAsync(m->d_flags_in.p, 0, (size_t)n_reads * FW * 4, st));
         HIPCHK(hipMemcpyAsync(m->d_flags_in.p, m->carry_flags, FW * 4, hipMemcpyHostToDevice, st));    // read 0 follows the previous batch's last read
+        a.flags_in = m->d_flags_in.p; a.flags_out = m->d_flags_out.p;
     }
-    const uint32_t *const fl_in = t1 ? m->d_flags_in.p : nullptr;
-    uint32_t *const fl_out = t1 ? m->d_flags_out.p : nullptr;
-    launch_map(m->ix->dev, m->sc.v, rd, m->P, m->d_results.p, m->d_next.p, sliced ? m->slice_events : 0xFFFFFFFFu, 0, nullptr, grid, st, m->pool.v,
-               nullptr, reinterpret_cast<unsigned long long *>(m->d_next.p + 2), sliced ? &m->sched.v : nullptr, m->profile, fl_in, fl_out);
+    launch_map(a, grid, st, m->profile);
     HIPCHK(hipEventRecord(m->ev[2], st));
     HIPCHK(hipGetLastError());
-    m->pend.active = true; m->pend.n_reads = n_reads; m->pend.grid = grid; m->pend.st = st; m->pend.rd = rd; m->pend.t1 = t1;
+    m->pend.active = true; m->pend.n_reads = n_reads; m->pend.grid = grid; m->pend.st = st; m->pend.args = a; m->pend.t1 = t1;
     m->pend.lens.resize(n_reads);
     for (uint32_t i = 0; i < n_reads; ++i) m->pend.lens[i] = m->h_offsets[i + 1] - m->h_offsets[i];
     return UNC_OK;
 }
 
-extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
-    if (!m || !hits) return fail(UNC_ERR_ARG, "null argument");
-    if (!m->pend.active) return fail(UNC_ERR_ARG, "unc_map_batch_end: no batch has been begun on this mapper");
-    m->pend.active = false;       // (whatever happens below, the batch is over)
-    HIPCHK(hipSetDevice(m->ix->device));
+// What the first pass left: results and event counts on the host, the kernels' times, how busy the wavefronts were.
+static int collect_first_pass(unc_mapper *m) {
     const uint32_t n_reads = m->pend.n_reads, grid = m->pend.grid;
     hipStream_t st = m->pend.st;
-    const DevReads rd = m->pend.rd;
-    const bool t1 = m->pend.t1;
-    constexpr size_t FW = NKMER / 32;
-    const uint32_t *const fl_in = t1 ? m->d_flags_in.p : nullptr;
-    uint32_t *const fl_out = t1 ? m->d_flags_out.p : nullptr;
-    int rc = UNC_OK;
     m->h_info.resize(n_reads);
     m->h_results.resize(n_reads);
     // (the copies into pageable host memory would hold the host until the kernels are done: they are issued here, not in _begin)
@@ -1012,190 +1012,196 @@ extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&m->ms_events, m->ev[0], m->ev[1]));
     HIPCHK(hipEventElapsedTime(&m->ms_map, m->ev[1], m->ev[2]));
-    {
-        hipEvent_t ref = nullptr;
-        float a = 0, b = 0;
-        if (ref_event(&ref) == UNC_OK && hipEventElapsedTime(&a, ref, m->ev[1]) == hipSuccess && hipEventElapsedTime(&b, ref, m->ev[2]) == hipSuccess) {
-            m->win_start_ms = a; m->win_end_ms = b;
-        } else (void)hipGetLastError();
-    }
+    hipEvent_t ref = nullptr;
+    float a = 0, b = 0;
+    if (ref_event(&ref) == UNC_OK && hipEventElapsedTime(&a, ref, m->ev[1]) == hipSuccess && hipEventElapsedTime(&b, ref, m->ev[2]) == hipSuccess) {
+        m->win_start_ms = a; m->win_end_ms = b;
+    } else (void)hipGetLastError();
     for (uint32_t i = 0; i < n_reads; ++i)
         if (m->h_info[i].pad) return fail(UNC_ERR_OVERFLOW, "read %u: more events than the room for event means holds (5/8 of its samples + 16)", i);
-    m->pool_hw_last = 0;
-    rc = pool_note_high_water(m, st);
-    if (rc) return rc;
-    bool pool_went_dry = false;
-    {
-        unsigned long long ticks = 0;
-        int khz = 0;
-        HIPCHK(hipMemcpy(&ticks, m->d_next.p + 2, 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, m->ix->device));
-        m->wave_busy = (grid && m->ms_map > 0 && khz > 0) ? (double)ticks / ((double)grid * (double)m->ms_map * (double)khz) : 0.0;
-    }
-    // The reference's SeedTracker is an unbounded std::set.  Reads whose set did not fit are mapped again after the batch, by
-    // cause: a read that found the pool of nodes DRY runs again on the same scratch with fewer and fewer reads sharing the
-    // pool (n_waves, a quarter of that, ... down to one read with the whole pool); a read that used up its own ALLOWANCE
-    // (max_clusters / 4 nodes) runs again on scratch with a 16x larger allowance, up to 2^26 clusters.
-    m->remap_reads = 0;
-    m->remap_ms = 0;
-    // (`subset`: the reads whose results are new -- all of the batch after the first pass, the re-mapped ones of a `-t 1` round)
-    auto resolve_overflows = [&](const std::vector<uint32_t> *subset) -> int {
-        std::vector<uint32_t> dry, full, work;
-        auto classify = [&](uint32_t i) {
-            const uint32_t stt = m->h_results[i].status;
-            if (stt & UNC_READ_POOL_DRY) dry.push_back(i);
-            else if (stt & UNC_READ_CLUSTER_OVERFLOW) full.push_back(i);
-        };
-        if (subset) { for (uint32_t i : *subset) classify(i); }
-        else { for (uint32_t i = 0; i < n_reads; ++i) classify(i); }
-        m->remap_reads += (uint32_t)(dry.size() + full.size());
-        if (!dry.empty()) pool_went_dry = true;
-        const auto t_redo = std::chrono::steady_clock::now();
-        uint64_t cap = m->sc.v.max_clusters;
-        size_t limit = m->n_waves;
+    unsigned long long ticks = 0;
+    int khz = 0;
+    HIPCHK(hipMemcpy(&ticks, m->d_next.p + 2, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, m->ix->device));
+    m->wave_busy = (grid && m->ms_map > 0 && khz > 0) ? (double)ticks / ((double)grid * (double)m->ms_map * (double)khz) : 0.0;
+    return UNC_OK;
+}
+
+// The one list-mode launch: the reads of `work` are mapped again from their first event on scratch `sc`, at most `slots` of them in
+// flight, with the whole pool free; their results replace the earlier ones on the host (the range lo..hi is copied: the entries of
+// d_results in between that are not in `work` still hold what h_results was last copied from).
+static int remap_round(unc_mapper *m, const DevScratch &sc, const std::vector<uint32_t> &work, size_t slots) {
+    hipStream_t st = m->pend.st;
+    HIPCHK(m->d_list.reserve(work.size()));
+    HIPCHK(hipMemcpyAsync(m->d_list.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(m->d_next.p, 0, 4, st));
+    launch_pool_init(m->pool.v, st);
+    MapArgs a = m->pend.args;      // the first pass's reads and flags, but: this list, to completion, no scheduler, no wave-lifetime probe
+    a.sc = sc; a.rd.n_reads = (uint32_t)work.size(); a.read_list = m->d_list.p;
+    a.max_steps = 0xFFFFFFFFu; a.sched = DevSched{}; a.wave_ticks = nullptr;
+    launch_map(a, (uint32_t)slots, st);
+    HIPCHK(hipGetLastError());
+    const uint32_t lo = *std::min_element(work.begin(), work.end()), hi = *std::max_element(work.begin(), work.end());
+    HIPCHK(hipMemcpyAsync(m->h_results.data() + lo, m->d_results.p + lo, (size_t)(hi - lo + 1) * sizeof(DevResult), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return UNC_OK;
+}
+
+// read i's current result by the cause of its overflow, if any
+static void classify(const unc_mapper *m, uint32_t i, std::vector<uint32_t> &dry, std::vector<uint32_t> &full) {
+    const uint32_t stt = m->h_results[i].status;
+    if (stt & UNC_READ_POOL_DRY) dry.push_back(i);
+    else if (stt & UNC_READ_CLUSTER_OVERFLOW) full.push_back(i);
+}
+
+// m->big = scratch with an allowance of `cap` clusters and, if a quarter of the free HBM allows, `want` slots
+static int ensure_big_scratch(unc_mapper *m, uint64_t cap, size_t want) {
+    if (m->big.v.max_clusters == cap && (m->big_slots >= want || m->big_at_limit)) return UNC_OK;      // (the big scratch's allowance: 0 while there is none)
+    m->big = Scratch{};
+    m->big_slots = 0;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t per_slot = scratch_slot_bytes(m->P, (uint32_t)cap, m->sc.v.max_seed_paths, m->ix->dev);
+    const size_t fit = std::max<size_t>(1, free_b / 4 / per_slot);
+    const size_t n = std::min(want, fit);
+    int rc = alloc_scratch(m->big, m->P, n, (uint32_t)cap, m->sc.v.max_seed_paths, nullptr, m->ix->dev);
+    if (rc) { m->big = Scratch{}; return rc; }
+    m->big_slots = n; m->big_at_limit = n == fit;
+    return UNC_OK;
+}
+
+// The reference's SeedTracker is an unbounded std::set.  Reads whose set did not fit are mapped again after the batch, by
+// cause: a read that found the pool of nodes DRY runs again on the same scratch with fewer and fewer reads sharing the
+// pool (n_waves, a quarter of that, ... down to one read with the whole pool); a read that used up its own ALLOWANCE
+// (max_clusters / 4 nodes) runs again on scratch with a 16x larger allowance, up to 2^26 clusters.
+// (`subset`: the reads whose results are new -- null: all of the batch, after the first pass; else the re-mapped ones of a `-t 1` round)
+static int resolve_overflows(unc_mapper *m, const std::vector<uint32_t> *subset, bool *pool_went_dry) {
+    std::vector<uint32_t> dry, full, work;
+    if (subset) { for (uint32_t i : *subset) classify(m, i, dry, full); }
+    else { for (uint32_t i = 0; i < m->pend.n_reads; ++i) classify(m, i, dry, full); }
+    m->remap_reads += (uint32_t)(dry.size() + full.size());
+    if (!dry.empty()) *pool_went_dry = true;
+    const auto t_redo = std::chrono::steady_clock::now();
+    uint64_t cap = m->sc.v.max_clusters;
+    size_t limit = m->n_waves;
+    while (!dry.empty() || !full.empty()) {
         // one pass over `work` with at most `slots` reads in flight; the reads that overflowed again are sorted by cause
-        auto run_round = [&](const DevScratch &sc, size_t slots) -> int {
-            HIPCHK(m->d_list.reserve(work.size()));
-            HIPCHK(hipMemcpyAsync(m->d_list.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemsetAsync(m->d_next.p, 0, 4, st));
-            launch_pool_init(m->pool.v, st);
-            DevReads rd2 = rd;
-            rd2.n_reads = (uint32_t)work.size();
-            launch_map(m->ix->dev, sc, rd2, m->P, m->d_results.p, m->d_next.p, 0xFFFFFFFFu, 0, nullptr, (uint32_t)slots, st, m->pool.v, m->d_list.p,
-                       nullptr, nullptr, false, fl_in, fl_out);
-            HIPCHK(hipGetLastError());
-            const uint32_t lo = *std::min_element(work.begin(), work.end()), hi = *std::max_element(work.begin(), work.end());
-            HIPCHK(hipMemcpyAsync(m->h_results.data() + lo, m->d_results.p + lo, (size_t)(hi - lo + 1) * sizeof(DevResult), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (int rc3 = pool_note_high_water(m, st)) return rc3;
-            for (uint32_t i : work) classify(i);
-            work.clear();
-            return UNC_OK;
-        };
-        auto scratch_now = [&]() -> const DevScratch & { return cap == m->sc.v.max_clusters ? m->sc.v : m->big.v; };
-        while (!dry.empty() || !full.empty()) {
-            if (!dry.empty()) {
-                const DevScratch &sc = scratch_now();
-                const size_t have = cap == m->sc.v.max_clusters ? m->n_slots : m->big_slots;
-                const size_t slots = std::min({dry.size(), have, limit});
-                work.swap(dry);
-                // (reads that ran out of allowance wait in `full` meanwhile: at this allowance they would only overflow again)
-                int rc2 = run_round(sc, slots);
-                if (rc2) return rc2;
-                if (!dry.empty()) {
-                    if (slots <= 1) {
-                        // every read of this round had the whole pool to itself and is still dry: reported with its status (raise
-                        // pool_chunks); the reads waiting in `full` for a larger allowance go on (round-3 advice: they were abandoned)
-                        dry.clear();
-                        continue;
-                    }
-                    limit = std::max<size_t>(1, slots / 4);
-                }
-                continue;
-            }
+        const bool for_dry = !dry.empty();
+        size_t slots;
+        if (for_dry) {
+            // (reads that ran out of allowance wait in `full` meanwhile: at this allowance they would only overflow again)
+            const size_t have = cap == m->sc.v.max_clusters ? m->n_slots : m->big_slots;
+            slots = std::min({dry.size(), have, limit});
+            work.swap(dry);
+        } else {
             cap *= 16;
             if (cap > (1ull << 26)) break;
-            const size_t want = std::min<size_t>(std::max<size_t>(full.size(), 64), m->n_waves);
-            if (m->big.v.max_clusters != cap || (m->big_slots < want && !m->big_at_limit)) {      // (the big scratch's allowance: 0 while there is none)
-                m->big = Scratch{};
-                m->big_slots = 0;
-                size_t free_b = 0, total_b = 0;
-                HIPCHK(hipMemGetInfo(&free_b, &total_b));
-                const size_t per_slot = scratch_slot_bytes(m->P, (uint32_t)cap, m->sc.v.max_seed_paths, m->ix->dev);
-                const size_t fit = std::max<size_t>(1, free_b / 4 / per_slot);
-                const size_t n = std::min(want, fit);
-                int rc2 = alloc_scratch(m->big, m->P, n, (uint32_t)cap, m->sc.v.max_seed_paths, nullptr, m->ix->dev);
-                if (rc2) { m->big = Scratch{}; return rc2; }
-                m->big_slots = n; m->big_at_limit = n == fit;
-            }
-            const size_t slots = std::min({full.size(), m->big_slots, limit});
+            if (int rc = ensure_big_scratch(m, cap, std::min<size_t>(std::max<size_t>(full.size(), 64), m->n_waves))) return rc;
+            slots = std::min({full.size(), m->big_slots, limit});
             work.swap(full);
-            int rc2 = run_round(m->big.v, slots);
-            if (rc2) return rc2;
         }
-        m->remap_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_redo).count();
-        return UNC_OK;
-    };
-    rc = resolve_overflows(nullptr);
+        if (int rc = remap_round(m, cap == m->sc.v.max_clusters ? m->sc.v : m->big.v, work, slots)) return rc;
+        if (int rc = pool_note_high_water(m, m->pend.st)) return rc;
+        for (uint32_t i : work) classify(m, i, dry, full);
+        work.clear();
+        if (for_dry && !dry.empty()) {
+            // still dry with the whole pool to itself: every such read is reported with its status (raise pool_chunks); the reads
+            // waiting in `full` for a larger allowance go on (round-3 advice: they were abandoned)
+            if (slots <= 1) dry.clear();
+            else limit = std::max<size_t>(1, slots / 4);
+        }
+    }
+    m->remap_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_redo).count();
+    return UNC_OK;
+}
+
+static const Flags &flags_of(const std::map<uint32_t, Flags> &mp, uint32_t i) {
+    static const Flags zero{};
+    auto it = mp.find(i);
+    return it == mp.end() ? zero : it->second;
+}
+
+// left[i] = the flags the CURRENT result of read i leaves set, for every i of `reads` (absent: none).  A read that is reported with an
+// overflow status has no valid run behind it: it hands NO flags on -- round-4 advice; the rows of all flagged reads are fetched
+// together, one synchronisation per call.
+static int fetch_left(unc_mapper *m, const std::vector<uint32_t> &reads, std::map<uint32_t, Flags> &left) {
+    std::vector<uint32_t> rows;
+    for (uint32_t i : reads) {
+        left.erase(i);
+        if (m->h_results[i].status == 0 && (m->h_results[i].notes & UNC_NOTE_FLAGS_LEFT)) rows.push_back(i);
+    }
+    std::vector<Flags> got(rows.size());
+    for (size_t k = 0; k < rows.size(); ++k)
+        HIPCHK(hipMemcpyAsync(got[k].data(), m->d_flags_out.p + (size_t)rows[k] * FW, sizeof(Flags), hipMemcpyDeviceToHost, m->pend.st));
+    if (!rows.empty()) HIPCHK(hipStreamSynchronize(m->pend.st));
+    for (size_t k = 0; k < rows.size(); ++k) left[rows[k]] = got[k];
+    return UNC_OK;
+}
+
+// `uncalled map -t 1`: ONE Mapper maps the reads one after another, and sources_added_ is the one piece of its state that
+// Mapper::new_read does not reset (mapper.cpp:88,219-246): what a read leaves set (only a read whose path buffer was full
+// can, :612-623; UNC_NOTE_FLAGS_LEFT) is what its successor starts with.  The batch was mapped with every read but the
+// first starting clear; a read whose predecessor turned out to leave something else than it assumed is mapped again
+// with that, and so on down the chain until every read has started from what its predecessor really left.
+static int carry_over_t1(unc_mapper *m, bool *pool_went_dry) {
+    const uint32_t n_reads = m->pend.n_reads;
+    hipStream_t st = m->pend.st;
+    const auto t_c = std::chrono::steady_clock::now();
+    std::map<uint32_t, Flags> left;        // read -> flags its CURRENT result leaves set (absent: none)
+    std::map<uint32_t, Flags> assumed;     // read -> flags its current result started from (absent: none)
+    Flags f0; memcpy(f0.data(), m->carry_flags, sizeof f0);
+    if (f0 != Flags{}) assumed[0] = f0;
+    std::vector<uint32_t> todo(n_reads);
+    for (uint32_t i = 0; i < n_reads; ++i) todo[i] = i;
+    if (int rc = fetch_left(m, todo, left)) return rc;
+    todo.clear();
+    for (const auto &kv : left) if (kv.first + 1 < n_reads) todo.push_back(kv.first + 1);
+    while (!todo.empty()) {
+        std::vector<uint32_t> work;
+        for (uint32_t j : todo) if (flags_of(left, j - 1) != flags_of(assumed, j)) work.push_back(j);
+        if (work.empty()) break;
+        for (uint32_t j : work) {
+            const Flags &f = flags_of(left, j - 1);
+            if (f == Flags{}) assumed.erase(j); else assumed[j] = f;
+            HIPCHK(hipMemcpyAsync(m->d_flags_in.p + (size_t)j * FW, f.data(), sizeof f, hipMemcpyHostToDevice, st));
+        }
+        // (this launch's own high-water mark of the pool is not recorded, unlike an overflow round's: pool_fit has always decided without it)
+        if (int rc = remap_round(m, m->sc.v, work, std::min<size_t>(work.size(), m->n_slots))) return rc;
+        if (int rc = resolve_overflows(m, &work, pool_went_dry)) return rc;
+        if (int rc = fetch_left(m, work, left)) return rc;
+        m->carry_reads += (uint32_t)work.size();
+        m->carry_rounds++;
+        todo.clear();
+        for (uint32_t j : work) if (j + 1 < n_reads) todo.push_back(j + 1);
+    }
+    memcpy(m->carry_flags, flags_of(left, n_reads - 1).data(), sizeof m->carry_flags);
+    m->carry_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_c).count();
+    return UNC_OK;
+}
+
+extern "C" int unc_map_batch_end(unc_mapper_t *m, unc_hit_t *hits) {
+    if (!m || !hits) return fail(UNC_ERR_ARG, "null argument");
+    if (!m->pend.active) return fail(UNC_ERR_ARG, "unc_map_batch_end: no batch has been begun on this mapper");
+    m->pend.active = false;       // (whatever happens below, the batch is over)
+    HIPCHK(hipSetDevice(m->ix->device));
+    int rc = collect_first_pass(m);
+    if (rc) return rc;
+    m->pool_hw_last = 0;
+    rc = pool_note_high_water(m, m->pend.st);
+    if (rc) return rc;
+    bool pool_went_dry = false;
+    m->remap_reads = 0; m->remap_ms = 0;
+    rc = resolve_overflows(m, nullptr, &pool_went_dry);
     if (rc) return rc;
     m->carry_reads = 0; m->carry_rounds = 0; m->carry_ms = 0;
-    if (t1) {
-        // `uncalled map -t 1`: ONE Mapper maps the reads one after another, and sources_added_ is the one piece of its state that
-        // Mapper::new_read does not reset (mapper.cpp:88,219-246): what a read leaves set (only a read whose path buffer was full
-        // can, :612-623; UNC_NOTE_FLAGS_LEFT) is what its successor starts with.  The batch was mapped with every read but the
-        // first starting clear; a read whose predecessor turned out to leave something else than it assumed is mapped again
-        // with that, and so on down the chain until every read has started from what its predecessor really left.
-        const auto t_c = std::chrono::steady_clock::now();
-        typedef std::array<uint32_t, FW> Flags;
-        const Flags zero{};
-        std::map<uint32_t, Flags> left;        // read -> flags its CURRENT result leaves set (absent: none)
-        std::map<uint32_t, Flags> assumed;     // read -> flags its current result started from (absent: none)
-        Flags f0; memcpy(f0.data(), m->carry_flags, sizeof f0);
-        if (f0 != zero) assumed[0] = f0;
-        // (a read that is reported with an overflow status has no valid run behind it: it hands NO flags on -- round-4 advice; the
-        // rows of all flagged reads are fetched together, one synchronisation per call)
-        auto fetch_left = [&](const std::vector<uint32_t> &reads) -> int {
-            std::vector<uint32_t> rows;
-            for (uint32_t i : reads) {
-                left.erase(i);
-                if (m->h_results[i].status == 0 && (m->h_results[i].notes & UNC_NOTE_FLAGS_LEFT)) rows.push_back(i);
-            }
-            std::vector<Flags> got(rows.size());
-            for (size_t k = 0; k < rows.size(); ++k)
-                HIPCHK(hipMemcpyAsync(got[k].data(), m->d_flags_out.p + (size_t)rows[k] * FW, sizeof(Flags), hipMemcpyDeviceToHost, st));
-            if (!rows.empty()) HIPCHK(hipStreamSynchronize(st));
-            for (size_t k = 0; k < rows.size(); ++k) left[rows[k]] = got[k];
-            return UNC_OK;
-        };
-        {
-            std::vector<uint32_t> flagged;
-            for (uint32_t i = 0; i < n_reads; ++i) if (m->h_results[i].status == 0 && (m->h_results[i].notes & UNC_NOTE_FLAGS_LEFT)) flagged.push_back(i);
-            rc = fetch_left(flagged);
-            if (rc) return rc;
-        }
-        auto get = [&](const std::map<uint32_t, Flags> &mp, uint32_t i) -> const Flags & { auto it = mp.find(i); return it == mp.end() ? zero : it->second; };
-        std::vector<uint32_t> todo;
-        for (const auto &kv : left) if (kv.first + 1 < n_reads) todo.push_back(kv.first + 1);
-        while (!todo.empty()) {
-            std::vector<uint32_t> work;
-            for (uint32_t j : todo) if (get(left, j - 1) != get(assumed, j)) work.push_back(j);
-            if (work.empty()) break;
-            for (uint32_t j : work) {
-                const Flags &f = get(left, j - 1);
-                if (f == zero) assumed.erase(j); else assumed[j] = f;
-                HIPCHK(hipMemcpyAsync(m->d_flags_in.p + (size_t)j * FW, f.data(), sizeof f, hipMemcpyHostToDevice, st));
-            }
-            HIPCHK(m->d_list.reserve(work.size()));
-            HIPCHK(hipMemcpyAsync(m->d_list.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemsetAsync(m->d_next.p, 0, 4, st));
-            launch_pool_init(m->pool.v, st);
-            DevReads rd2 = rd;
-            rd2.n_reads = (uint32_t)work.size();
-            launch_map(m->ix->dev, m->sc.v, rd2, m->P, m->d_results.p, m->d_next.p, 0xFFFFFFFFu, 0, nullptr,
-                       (uint32_t)std::min<size_t>(work.size(), m->n_slots), st, m->pool.v, m->d_list.p, nullptr, nullptr, false, fl_in, fl_out);
-            HIPCHK(hipGetLastError());
-            for (uint32_t j : work)
-                HIPCHK(hipMemcpyAsync(m->h_results.data() + j, m->d_results.p + j, sizeof(DevResult), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            rc = resolve_overflows(&work);
-            if (rc) return rc;
-            rc = fetch_left(work);
-            if (rc) return rc;
-            m->carry_reads += (uint32_t)work.size();
-            m->carry_rounds++;
-            todo.clear();
-            for (uint32_t j : work) if (j + 1 < n_reads) todo.push_back(j + 1);
-        }
-        const Flags &last = get(left, n_reads - 1);
-        memcpy(m->carry_flags, last.data(), sizeof m->carry_flags);
-        m->carry_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_c).count();
-    }
+    if (m->pend.t1) rc = carry_over_t1(m, &pool_went_dry);
+    if (rc) return rc;
     int worst = UNC_OK;
-    for (uint32_t i = 0; i < n_reads; ++i) {
+    for (uint32_t i = 0; i < m->pend.n_reads; ++i) {
         fill_hit(m->ix, m->P, m->h_results[i], m->h_info[i], m->pend.lens[i], &hits[i], m->wall_khz);
         if (hits[i].status) worst = UNC_ERR_OVERFLOW;
     }
-    rc = pool_fit(m, pool_went_dry, n_reads);
+    rc = pool_fit(m, pool_went_dry, m->pend.n_reads);
     if (rc) return rc;
     if (worst) return fail(worst, "device scratch overflow on at least one read (see unc_hit_t.status); raise pool_chunks / max_clusters / max_seed_paths");
     return UNC_OK;
@@ -1487,7 +1493,9 @@ extern "C" int unc_trace_step(unc_mapper_t *m, uint32_t n_events, int *done) {
     HIPCHK(hipSetDevice(m->ix->device));
     DevReads rd;
     trace_reads(m, &rd);
-    launch_map(m->ix->dev, m->sc.v, rd, m->P, m->d_results.p, m->d_next.p, n_events, 1, nullptr, 1, m->stream, m->pool.v);
+    MapArgs a = mapper_args(m, rd);
+    a.max_steps = n_events; a.resume = 1;       // the read parked in slot 0, for n_events events more
+    launch_map(a, 1, m->stream);
     HIPCHK(hipGetLastError());
     SlotState s;
     HIPCHK(hipMemcpyAsync(&s, slot_state(m->sc.v, 0), sizeof s, hipMemcpyDeviceToHost, m->stream));
@@ -1897,13 +1905,15 @@ static int rt_process(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chu
         launch_rt_events(d_raw, d_pa, rt->d_desc.p, n_act, rt->d_chans.p, rt->d_ring.p, rt->P, rt->ix->model_mean, rt->ix->model_stdv, rt->d_info.p,
                          rt->d_ring0.p, st);
         HIPCHK(hipEventRecord(rt->ev[1], st));
-        DevReads rd;
+        MapArgs a;
+        a.ix = rt->ix->dev; a.sc = rt->sc.v; a.P = rt->P; a.pool = rt->pool.v; a.results = rt->d_results.p; a.next_read = rt->d_next.p;
+        DevReads &rd = a.rd;
         memset(&rd, 0, sizeof rd);
         rd.means = rt->d_ring.p; rd.moff = rt->d_moff.p; rd.info = rt->d_info.p; rd.n_reads = n_act;
         rd.tgt_mean = rt->ix->model_mean; rd.tgt_stdv = rt->ix->model_stdv;
         rd.ring0 = rt->d_ring0.p; rd.new_read = rt->d_newread.p; rd.ring_mod = NORM_LEN;
-        launch_map(rt->ix->dev, rt->sc.v, rd, rt->P, rt->d_results.p, rt->d_next.p, 0xFFFFFFFFu, 1, rt->d_slotmap.p, n_act, st, rt->pool.v, nullptr, nullptr, nullptr,
-                   rt->profile, nullptr, nullptr, rt->team);
+        a.resume = 1; a.slot_map = rt->d_slotmap.p;      // block b goes on with the read of channel slot_map[b], from the channel's ring
+        launch_map(a, n_act, st, rt->profile, rt->team);
         HIPCHK(hipEventRecord(rt->ev[2], st));
         HIPCHK(hipGetLastError());
         rt->h_info.resize(n_act);

@@ -8,11 +8,7 @@ namespace unc {
 void launch_events(const DevReads &rd, const unc_params_t &P, hipStream_t st, uint32_t reads_per_wave = 0);
 void launch_rt_events(const int16_t *raw, const float *raw_pa, const RtChunkDesc *chunks, uint32_t n_chunks, RtChan *chans, float *norm_ring,
                       const unc_params_t &P, float tgt_mean, float tgt_stdv, unc_evt_info_t *info, uint32_t *ring0_out, hipStream_t st);
-void launch_map(const DevIndex &ix, const DevScratch &sc, const DevReads &rd, const unc_params_t &P, DevResult *results,
-                uint32_t *next_read, uint32_t max_steps, uint32_t resume, const uint32_t *slot_map, uint32_t grid, hipStream_t st,
-                const DevPool &pool, const uint32_t *read_list = nullptr, unsigned long long *wave_ticks = nullptr,
-                const DevSched *sched = nullptr, bool profile = false, const uint32_t *flags_in = nullptr, uint32_t *flags_out = nullptr,
-                uint32_t team = 1);   // chunked path only: wavefronts per channel (1, 2 or 4)
+void launch_map(const MapArgs &a, uint32_t grid, hipStream_t st, bool profile = false, uint32_t team = 1);   // team: chunked path only, wavefronts per channel
 void launch_sched_init(const DevSched &S, hipStream_t st);
 void launch_xcd_probe(uint32_t *out, uint32_t n_blocks, hipStream_t st);
 void launch_pool_init(const DevPool &B, hipStream_t st);
