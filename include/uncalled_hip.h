@@ -388,6 +388,60 @@ void unc_dtw_model_tables(float *means1024, float *vars_x2_1024, float *lognorm1
 int unc_ref_kmers(const unc_index_t *ix, const char *bwa_prefix, int32_t rid, uint64_t st, uint64_t en, int fwd, uint16_t *out,
                   uint64_t cap, uint64_t *n);
 
+/* ---- read-to-reference alignment: replaces the pipeline of src/dtw_test.cpp:94-176 for a batch of queries.  A query is a read of
+ * the batch, a sample range [smp_st, smp_en) of it (smp_en == 0: to the end of the read; 0, 0: the whole read, dtw_test.cpp:123-132)
+ * and a run of reference k-mers.  Per query, on the device and without the event means visiting the host:
+ *   EventDetector::get_events on the slice (event_detector.cpp:114-126: the detector is reset at the slice's first sample),
+ *   EventProfiler::get_full_mask (event_profiler.hpp:129-151: events of stalls are dropped),
+ *   the target mean and deviation of the template model's levels over the query's k-mers (dtw_test.cpp:106-116),
+ *   Normalizer::set_signal / pop (normalizer.cpp:31-44,114-128),
+ *   DTW of the levels (columns) against the k-mers (rows), as unc_dtw_batch.
+ * Only the per-query counts return between the stages: the DTW's planner lays out the back-pointers by them. */
+typedef struct {
+    uint32_t read;          /* index into the batch's reads; several queries may name one read */
+    uint32_t pad;
+    uint64_t smp_st, smp_en;
+} unc_align_query_t;
+#define UNC_ALIGN_DTW_PARAMS 1u     /* opts.dtw holds the DTW's parameters (else: DTWr94d, DTWSubSeq::NONE, weights 1, 1, 1 -- dtw_test.cpp:76-78,162) */
+#define UNC_ALIGN_NO_MASK 2u        /* every detected event is kept */
+#define UNC_ALIGN_RAW 4u            /* create_events off (dtw_test.cpp:146-148): the calibrated samples of the slice are normalised and aligned */
+#define UNC_ALIGN_TARGET_MODEL 8u   /* normalise to the model's mean and deviation over all k-mers (the line commented out at dtw_test.cpp:118) */
+typedef struct {
+    uint32_t flags;         /* UNC_ALIGN_*; a zeroed struct is dtw_test */
+    uint32_t max_events;    /* a query with more columns than this is not aligned (dtw_test.cpp:156-159 uses 50000); 0 = no limit */
+    unc_dtw_params_t dtw;   /* read with UNC_ALIGN_DTW_PARAMS only */
+    uint32_t pad;
+} unc_align_opts_t;
+/* per-query status: UNC_DTW_OK, UNC_DTW_TOO_LARGE, UNC_DTW_PATH_TRUNCATED as unc_dtw_batch gives them, or one of */
+#define UNC_ALIGN_NO_COLUMNS 3u     /* nothing left to align: the slice is too short for an event, or every event was masked.  Not aligned */
+#define UNC_ALIGN_TOO_MANY 4u       /* more columns than opts.max_events.  Not aligned (counts, target, scale and shift are filled) */
+typedef struct {
+    unc_dtw_result_t dtw;           /* zero for a query that was not aligned */
+    uint32_t n_events, n_kept;      /* events detected in the slice (samples with UNC_ALIGN_RAW) / columns left after the mask */
+    float tgt_mean, tgt_stdv;       /* the Normalizer's target */
+    float scale, shift;             /* Normalizer::at, normalizer.cpp:114-118 */
+    uint32_t status, pad;
+} unc_align_result_t;
+/* raw / offsets / calib / on_device: the reads, as unc_map_batch takes them.  params: the event detector's (NULL: unc_params_default).
+ * opts: NULL = zeroed.  queries (host, n_queries); query q's k-mers are kmers[km_off[q] .. km_off[q+1]) (host, ascending offsets).
+ * results (host, n_queries).  levels (host, may be NULL) receives the normalised columns of query q from levels[lev_off[q]] on, at
+ * most lev_off[q+1] - lev_off[q] of them (a slice of n samples has at most n / 2 + 16 events): the tap that places a mismatch at a
+ * stage.  path / path_off / workspace_bytes / stream: as unc_dtw_batch.  UNC_ERR_ARG before anything touches the device for a read index
+ * past the batch, a slice outside its read, smp_st > smp_en with smp_en != 0, an empty k-mer run, a k-mer >= 1024 and whatever
+ * unc_dtw_batch refuses in the DTW's parameters.  UNC_ERR_OVERFLOW, for the whole batch and after device work, if a slice of n samples
+ * gave more than n / 2 + 16 events: the detector's windows, which are enforced, space its peaks so that this cannot happen, and the
+ * return code guards that room rather than reports on a query. */
+int unc_align_batch(int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
+                    const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries, const unc_align_query_t *queries,
+                    const uint16_t *kmers, const uint64_t *km_off, uint64_t workspace_bytes, unc_align_result_t *results, float *levels,
+                    const uint64_t *lev_off, uint32_t *path, const uint64_t *path_off, void *stream);
+/* kernel milliseconds of the calling thread's last unc_align_batch (HIP events on the stream): [0] the slices gathered (or calibrated,
+ * with UNC_ALIGN_RAW), [1] event detection, [2] mask + target + normalisation, [3] the DTW (all its rounds) */
+int unc_align_last_timing(float *ms4);
+/* PoreModel::get_means_mean / get_means_stdv (pore_model.hpp:48-56,82-100) of the r9.4 template model: the target of
+ * UNC_ALIGN_TARGET_MODEL */
+void unc_align_model_target(float *mean, float *stdv);
+
 /* ---- measurement aid: `reps` launches that write, then `reps` that read, n_records (made odd) scattered 64-byte records with
  * one lane per record and four 16-byte accesses per lane -- k_map's access shape with an exactly known byte count, for
  * calibrating the HBM traffic counters of rocprofv3 (tools/dev/pmc_calib.py, profiles/r02_pmc_k_map.json) */

@@ -1,4 +1,4 @@
-"""`python -m uncalled_amd {index,map,sim,pafstats}` -- the subcommands of the reference's `scripts/uncalled` that do not need
+"""`python -m uncalled_amd {index,map,sim,dtw,pafstats}` -- the subcommands of the reference's `scripts/uncalled` that do not need
 a sequencer (index_cmd :38-78, map_cmd :126-167, realtime_cmd :170-256 fed from fast5 files, pafstats) with the same options (uncalled/args.py:90-124,244-304) on the GPU path.
 """
 import argparse
@@ -323,6 +323,95 @@ def sim_cmd(args):
         pool.stop_all()
 
 
+def load_dtw_queries(fname):
+    """dtw_test.cpp:27-58: lines of `read_id smp_st smp_en ref_name ref_st ref_en strand`; a later line for the same read replaces
+    the earlier one, as the reference's map does."""
+    queries = {}
+    with open(fname) as fh:
+        for no, line in enumerate(fh, 1):
+            f = line.split()
+            if not f or f[0].startswith("#"):
+                continue
+            if len(f) != 7 or f[6] not in "+-":
+                sys.stderr.write("Error: %s:%d: expected `read_id smp_st smp_en ref_name ref_st ref_en strand`\n" % (fname, no))
+                sys.exit(1)
+            queries[f[0]] = dict(smp_st=int(f[1]), smp_en=int(f[2]), ref=f[3], ref_st=int(f[4]), ref_en=int(f[5]), fwd=f[6] == "+")
+    return queries
+
+
+KMER_BASES = "ACGT"
+
+
+def kmer_str(k, klen=5):
+    return "".join(KMER_BASES[(int(k) >> (2 * (klen - 1 - i))) & 3] for i in range(klen))
+
+
+def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False):
+    """The batches behind `dtw`: reads = [(id, int16 samples, (range, offset, digitisation))], queries as load_dtw_queries gives
+    them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels or None, path or None), in the order of `reads`."""
+    import numpy as np
+    from . import capi
+    names = index.seq_names()
+    for b0 in range(0, len(reads), batch):
+        part = reads[b0:b0 + batch]
+        raw = np.concatenate([np.asarray(r[1], np.int16) for r in part]) if part else np.zeros(0, np.int16)
+        offsets = np.cumsum([0] + [len(r[1]) for r in part]).astype(np.uint64)
+        calib = capi.make_calib(len(part), 0, 0, 1)
+        qs, kms = [], []
+        for i, (rid, _, cal) in enumerate(part):
+            calib[i] = cal
+            q = queries[rid]
+            if q["ref"] not in names:
+                sys.stderr.write("Error: no sequence '%s' in the index\n" % q["ref"])
+                sys.exit(1)
+            qs.append((i, q["smp_st"], q["smp_en"]))
+            kms.append(capi.ref_kmers(index, prefix, names.index(q["ref"]), q["ref_st"], q["ref_en"], q["fwd"]))
+        t0 = time.time()
+        out = capi.align_batch(raw, offsets, calib, qs, kms, opts=capi.align_opts(max_events=max_events), levels=want_paths, paths=want_paths,
+                               device=device)
+        sec = (time.time() - t0) / max(1, len(part))
+        res, levs, paths = out if want_paths else (out, [None] * len(part), [None] * len(part))
+        for i, (rid, _, _) in enumerate(part):
+            yield rid, res[i], sec, kms[i], levs[i], paths[i]
+
+
+def dtw_cmd(args):
+    """`dtw_test` (src/dtw_test.cpp:62-176): one signal-to-reference alignment per query line, all of them on the GPU in batches."""
+    from . import capi
+    from . import _uncalled_amd as unc
+    _assert_exists(args.index_prefix + ".bwt")
+    _assert_exists(args.index_prefix + ".pac")
+    _assert_exists(args.fast5)
+    _assert_exists(args.queries)
+    queries = load_dtw_queries(args.queries)
+    reader = unc.Fast5Reader("", "", 0, max(100, len(queries)))
+    reader.add_fast5(os.path.abspath(args.fast5))
+    for rid in queries:
+        reader.add_read(rid)            # only the named reads are taken from the file (Fast5Reader::add_read)
+    reads = []
+    while not reader.empty():
+        r = reader.pop_read()
+        if r.id in queries:
+            reads.append((r.id, r.raw_i16, r.calibration))
+    index = capi.Index(args.index_prefix, device=args.device)
+    for rid, r, sec, km, lev, path in dtw_align(index, args.index_prefix, reads, queries, max_events=args.max_events, batch=args.batch_queries,
+                                                device=args.device, want_paths=args.out_prefix is not None):
+        st = int(r["status"])
+        if st == capi.ALIGN_TOO_MANY:
+            sys.stderr.write("Skipping %s\n" % rid)            # dtw_test.cpp:156-159
+            continue
+        if st != capi.DTW_OK:
+            sys.stderr.write("Skipping %s: %s\n" % (rid, "no events left to align" if st == capi.ALIGN_NO_COLUMNS else "status %d" % st))
+            continue
+        if args.out_prefix is not None:
+            means = capi.dtw_model_tables()[0]
+            with open(args.out_prefix + rid + ".txt", "w") as out:
+                for j, i in path[::-1]:                          # from the start of the alignment to its end
+                    out.write("%d\t%d\t%s\t%.6g\t%.6g\n" % (j, i, kmer_str(km[i]), lev[j], abs(float(lev[j]) - float(means[km[i]]))))
+        sys.stdout.write("%s\t%.6g\t%.6g\n" % (rid, float(r["dtw"]["mean_score"]), sec))
+        sys.stdout.flush()
+
+
 def get_parser():
     from . import index_params, pafstats
     d = index_params.DEFAULTS
@@ -382,6 +471,22 @@ def get_parser():
     p.add_argument("--duration", type=float, default=None, help="Duration to map real-time run in hours")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
 
+    p = sp.add_parser("dtw", help="Align reads' signal to stretches of the reference by dynamic time warping (the reference's dtw_test)",
+                      description="One alignment per query line `read_id smp_st smp_en ref_name ref_st ref_en strand` (smp_en 0: to the "
+                      "read's end): events of the sample range, stalls masked, normalised to the levels of the stretch's k-mers, DTWr94d. "
+                      "Prints `read_id  mean_score  seconds` per read (seconds: the batch's wall time over its queries). -o writes one "
+                      "path file per read, from the start of the alignment to its end: event index, k-mer index, k-mer, level, cost. "
+                      "(The reference's print_path indexes the k-mers with the event index and the events with the k-mer index and can "
+                      "read past both; that is not reproduced.)")
+    p.add_argument("index_prefix", type=str, help="BWA prefix of the reference (needs the .pac)")
+    p.add_argument("fast5", type=str, help="fast5 file that holds the reads")
+    p.add_argument("queries", type=str, help="Query file, one line per read")
+    p.add_argument("-o", "--out-prefix", type=str, default=None, help="Write the path of read ID to OUT_PREFIX + ID + .txt")
+    p.add_argument("--max-events", type=int, default=50000, help="Skip reads with more events than this (the reference's 50000; 0: no limit -- "
+                   "2 bits per cell make alignments affordable here that the reference skips)")
+    p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
+    p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+
     p = sp.add_parser("pafstats", help="Computes speed and accuracy of UNCALLED mappings")
     pafstats.add_opts(p)
     return ap
@@ -395,6 +500,8 @@ def main(argv=None):
         map_cmd(args)
     elif args.subcmd == "sim":
         sim_cmd(args)
+    elif args.subcmd == "dtw":
+        dtw_cmd(args)
     else:
         from . import pafstats
         pafstats.run(args)

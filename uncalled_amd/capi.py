@@ -133,6 +133,18 @@ DTW_RAW_RSUB = DTWParams(DTW_ROW, DTW_R94P, 10, 1, 1000)
 DTW_RAW_GLOB = DTWParams(DTW_NONE, DTW_R94P, 10, 1, 1000)
 DTW_RESULT = np.dtype([("score", "<f4"), ("mean_score", "<f4"), ("path_len", "<u8"), ("status", "<u4"), ("pad", "<u4")])
 
+
+class AlignOpts(C.Structure):
+    """unc_align_opts_t; AlignOpts() is dtw_test: events, stall mask, target from the k-mers, DTWr94d / NONE / 1, 1, 1."""
+    _fields_ = [("flags", C.c_uint32), ("max_events", C.c_uint32), ("dtw", DTWParams), ("pad", C.c_uint32)]
+
+
+ALIGN_DTW_PARAMS, ALIGN_NO_MASK, ALIGN_RAW, ALIGN_TARGET_MODEL = 1, 2, 4, 8       # unc_align_opts_t.flags
+ALIGN_NO_COLUMNS, ALIGN_TOO_MANY = 3, 4                                           # unc_align_result_t.status beside the DTW_* ones
+ALIGN_QUERY = np.dtype([("read", "<u4"), ("pad", "<u4"), ("smp_st", "<u8"), ("smp_en", "<u8")])
+ALIGN_RESULT = np.dtype([("dtw", DTW_RESULT), ("n_events", "<u4"), ("n_kept", "<u4"), ("tgt_mean", "<f4"), ("tgt_stdv", "<f4"),
+                         ("scale", "<f4"), ("shift", "<f4"), ("status", "<u4"), ("pad", "<u4")])
+
 _libs = {}
 
 
@@ -226,6 +238,12 @@ def load(path=None):
         L.unc_dtw_model_tables.argtypes = [vp, vp, vp]
         L.unc_dtw_model_tables.restype = None
         L.unc_ref_kmers.argtypes = [vp, C.c_char_p, i32, u64, u64, C.c_int, vp, u64, C.POINTER(u64)]
+    if hasattr(L, "unc_align_batch"):
+        L.unc_align_batch.argtypes = [C.c_int, C.POINTER(Params), C.POINTER(AlignOpts), u32, vp, vp, vp, C.c_int, u32, vp, vp, vp, u64, vp,
+                                      vp, vp, vp, vp, vp]
+        L.unc_align_last_timing.argtypes = [vp]
+        L.unc_align_model_target.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.unc_align_model_target.restype = None
     _libs[key] = L
     return L
 
@@ -366,6 +384,91 @@ def dtw_last_timing(lib=None):
     ms, rounds, nbytes = C.c_float(), C.c_uint32(), C.c_uint64()
     L.unc_dtw_last_timing(C.byref(ms), C.byref(rounds), C.byref(nbytes))
     return ms.value, rounds.value, nbytes.value
+
+
+def align_opts(dtw=None, mask=True, create_events=True, target="kmers", max_events=0):
+    """AlignOpts from words: dtw = a DTWParams (None: dtw_test's), target = "kmers" | "model"."""
+    if target not in ("kmers", "model"):
+        raise ValueError("target is 'kmers' or 'model'")
+    o = AlignOpts()
+    o.flags = (ALIGN_DTW_PARAMS if dtw is not None else 0) | (0 if mask else ALIGN_NO_MASK) | (0 if create_events else ALIGN_RAW) | \
+        (ALIGN_TARGET_MODEL if target == "model" else 0)
+    o.max_events = int(max_events)
+    if dtw is not None:
+        o.dtw = dtw
+    return o
+
+
+def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
+                on_device=False, device=0, stream=None, lib=None):
+    """unc_align_batch: the pipeline of the reference's dtw_test (slice -> events -> stall mask -> normalisation to the k-mers'
+    levels -> DTW) for a batch of queries on the GPU.  raw / offsets / calib: the reads as Mapper.map_batch takes them (raw: an int16
+    array, or with on_device=True a device address).  queries: (read index, smp_st, smp_en) triples, smp_en == 0 = to the read's end;
+    kmers_list[q]: query q's reference k-mers.  -> ALIGN_RESULT records (dtw.score, dtw.mean_score, dtw.path_len, n_events, n_kept,
+    tgt_mean, tgt_stdv, scale, shift, status); with levels=True and / or paths=True also a list of the normalised columns per query and
+    a list of paths as dtw_batch returns them (None for a query that was not aligned)."""
+    L = lib or load()
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    calib = np.ascontiguousarray(calib, dtype=CALIB)
+    n_reads, n = offsets.size - 1, len(queries)
+    if n != len(kmers_list):
+        raise ValueError("as many k-mer arrays as queries are needed")
+    qs = np.zeros(n, dtype=ALIGN_QUERY)
+    for i, (r, st, en) in enumerate(queries):
+        qs[i]["read"], qs[i]["smp_st"], qs[i]["smp_en"] = r, st, en
+    kms = [np.ascontiguousarray(k, dtype=np.uint16).ravel() for k in kmers_list]
+    km_off = np.cumsum([0] + [k.size for k in kms]).astype(np.uint64)
+    km = np.concatenate(kms) if n else np.zeros(0, np.uint16)
+    if km.size == 0:
+        km = np.zeros(1, np.uint16)         # (a valid address for the library's own argument checks)
+    if on_device:
+        raw_ptr = int(raw)
+    else:
+        raw = np.ascontiguousarray(raw, dtype=np.int16)
+        raw_ptr = raw.ctypes.data
+    res = np.zeros(n, dtype=ALIGN_RESULT)
+    # room per query: what a slice can give at most (n / 2 + 16 events; its samples without events); a bad slice is the library's to refuse
+    room = []
+    for r, st, en in queries:
+        ln = int(offsets[r + 1] - offsets[r]) if 0 <= r < n_reads else 0
+        ns = max(0, (int(en) if en else ln) - int(st))
+        room.append(ns if opts is not None and opts.flags & ALIGN_RAW else ns // 2 + 16)
+    lev = lev_off = path = path_off = None
+    if levels:
+        lev_off = np.cumsum([0] + room).astype(np.uint64)
+        lev = np.empty(max(1, int(lev_off[-1])), dtype=np.float32)
+    if paths:
+        path_off = np.cumsum([0] + [c + k.size - 1 for c, k in zip(room, kms)]).astype(np.uint64)
+        path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
+    _check(L, L.unc_align_batch(int(device), C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
+                                n_reads, raw_ptr, offsets.ctypes.data, calib.ctypes.data, 1 if on_device else 0, n, qs.ctypes.data,
+                                km.ctypes.data, km_off.ctypes.data, int(workspace_bytes), res.ctypes.data,
+                                lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None,
+                                path.ctypes.data if paths else None, path_off.ctypes.data if paths else None, stream))
+    out = [res]
+    if levels:
+        out.append([lev[int(lev_off[q]):int(lev_off[q]) + int(res["n_kept"][q])].copy() for q in range(n)])
+    if paths:
+        done = (DTW_OK, DTW_PATH_TRUNCATED)
+        out.append([path[int(path_off[q]):int(path_off[q]) + int(res["dtw"]["path_len"][q])].copy() if res["status"][q] in done else None
+                    for q in range(n)])
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def align_last_timing(lib=None):
+    """kernel milliseconds of the calling thread's last align_batch: (slices gathered, event detection, mask + target + normalisation, DTW)."""
+    L = lib or load()
+    ms = np.zeros(4, np.float32)
+    L.unc_align_last_timing(ms.ctypes.data)
+    return tuple(float(x) for x in ms)
+
+
+def align_model_target(lib=None):
+    """(mean, stdv) of the r9.4 template model's levels over all k-mers: the target of target="model"."""
+    L = lib or load()
+    a, b = C.c_float(), C.c_float()
+    L.unc_align_model_target(C.byref(a), C.byref(b))
+    return np.float32(a.value), np.float32(b.value)
 
 
 def ref_kmers(index, prefix, rid, st, en, fwd=True):

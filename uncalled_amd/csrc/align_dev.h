@@ -1,0 +1,45 @@
+// What unc_align.cpp (host) and k_align.hip (kernels) share: the record of one query and the launch wrappers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/uncalled_hip.h"
+
+namespace unc {
+
+struct AlignQuery {
+    uint64_t src_off;             // the slice's first sample in the batch's samples
+    uint64_t dst_off;             // its first sample among the gathered slices (the slices lie one after the other there)
+    uint64_t col_off;             // first float of the query's room in the means and in the levels
+    uint64_t km_off;              // first k-mer
+    uint32_t n_smp, n_km;
+    uint32_t col_cap;             // floats of room
+    uint32_t pad;
+    unc_calib_t calib;            // of the query's read
+    uint32_t pad2;
+};
+
+struct AlignRecord {              // what the host reads back per query
+    uint32_t n_events, n_kept;
+    float tgt_mean, tgt_stdv, scale, shift;
+    uint32_t pad[2];
+};
+
+struct AlignPrep {
+    const AlignQuery *queries;
+    uint32_t n_queries;
+    uint32_t flags;               // UNC_ALIGN_*
+    const unc_evt_info_t *info;   // k_events' counts per query (null with UNC_ALIGN_RAW: the columns are the slice's samples)
+    const float *means;           // kept event means (or calibrated samples), query q from col_off on
+    float *levels;                // out: the columns the DTW reads, same layout
+    const uint16_t *kmers;
+    const float *model;           // [3][1024] of the template model; the means are the first 1024
+    float model_mean, model_stdv; // the target of UNC_ALIGN_TARGET_MODEL
+    AlignRecord *rec;
+};
+
+// slices -> one contiguous run of samples (k_events then takes every slice as a read of its own), or with `calibrated` != null the
+// calibrated samples themselves, query q from col_off on
+void launch_align_gather(const int16_t *raw, const AlignQuery *queries, uint32_t n_queries, int16_t *gathered, float *calibrated, hipStream_t st);
+void launch_align_prep(const AlignPrep &p, hipStream_t st);
+}  // namespace unc

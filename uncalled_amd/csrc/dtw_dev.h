@@ -9,6 +9,7 @@ namespace unc {
 
 constexpr uint32_t DTW_LANES = 64;          // rows of a strip: one per lane
 constexpr uint32_t DTW_CRUMBS_PER_WORD = 16;
+constexpr int DTW_MAX_DEVICES = 64;         // devices the per-device copy of the model is kept for
 
 // Back-pointers of one alignment: strips of 64 rows, each swept in cols + 63 steps (lane l is at column t - l in step t).  A strip's
 // steps are cut into blocks of 16; a block is 64 words, lane l's word holds its 16 moves of the block at 2 bits each: one
@@ -45,4 +46,16 @@ struct DtwBatch {
 };
 
 void launch_dtw(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st);
+
+// unc_dtw.cpp: what unc_dtw_batch does once its columns and k-mers are in device memory -- the queue in descending cell count, the
+// rounds that fit the workspace, the launches and the copies of results and paths to the host.  jobs[a] names alignment a's first
+// column and first k-mer in d_events / d_kmers, its rows and columns, path_cap and out = a (the three offsets of a round are filled
+// here).  skip (may be null): alignments with skip[a] != 0 are left out and res[a] is not written.  The arguments are the caller's
+// to check.  unc_align.cpp hands over the levels its own kernels have written: they never visit the host.
+int dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
+                   const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off,
+                   hipStream_t st);
+// the template model's 3 x 1024 floats on `device` (uploaded once per device) and on the host
+int dtw_model_device(int device, const float **out);
+const float *dtw_model_host();
 }  // namespace unc

@@ -21,7 +21,7 @@ using namespace unc;
 // ------------------------------------------------------------------ the template model
 // PoreModel(vector, cmpl=false), pore_model.hpp:58-62,77-103: the arithmetic of build_model (unc_host.cpp), rows not complemented --
 // row k here is row k ^ 0x3FF there.
-static const float *dtw_model_host() {
+const float *unc::dtw_model_host() {
     static std::vector<float> tab;
     static std::once_flag once;
     std::call_once(once, [] {
@@ -49,10 +49,9 @@ extern "C" void unc_dtw_model_tables(float *means1024, float *vars_x2_1024, floa
 }
 
 // one copy per device, uploaded by the first batch there and kept for the life of the process
-static constexpr int DTW_MAX_DEVICES = 64;
 static std::mutex g_model_mutex;
 static DevBuf<float> *g_model[DTW_MAX_DEVICES];
-static int dtw_model_device(int device, const float **out) {
+int unc::dtw_model_device(int device, const float **out) {
     std::lock_guard<std::mutex> lk(g_model_mutex);
     if (!g_model[device]) {
         DevBuf<float> buf;
@@ -83,44 +82,16 @@ struct HipEvent {       // (timing only)
 };
 }  // namespace
 
-extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
-                             const uint64_t *km_off, const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res,
-                             uint32_t *path, const uint64_t *path_off, void *stream) {
-    // ---- arguments: everything is checked before the device is touched
-    if (!events || !ev_off || !kmers || !km_off || !prm || !res) return fail(UNC_ERR_ARG, "unc_dtw_batch: null argument");
-    if (path && !path_off) return fail(UNC_ERR_ARG, "unc_dtw_batch: path without path_off");
-    if (device < 0 || device >= DTW_MAX_DEVICES) return fail(UNC_ERR_ARG, "unc_dtw_batch: device %d", device);
-    if (prm->subseq > UNC_DTW_COL) return fail(UNC_ERR_ARG, "unc_dtw_batch: unknown subseq %u", prm->subseq);
-    if (prm->cost > UNC_DTW_R94D) return fail(UNC_ERR_ARG, "unc_dtw_batch: unknown cost %u", prm->cost);
+// The queue, the rounds and the launches over columns and k-mers that lie in device memory already (dtw_dev.h).
+int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
+                        const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off,
+                        hipStream_t st) {
     g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
-    if (n == 0) return UNC_OK;
-    std::vector<DtwJob> jobs(n);
     std::vector<uint64_t> cells(n), words(n);
     for (uint32_t a = 0; a < n; ++a) {
-        if (ev_off[a + 1] <= ev_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u has no events", a);
-        if (km_off[a + 1] <= km_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u has no k-mers", a);
-        if (a && (ev_off[a] < ev_off[a - 1] || km_off[a] < km_off[a - 1])) return fail(UNC_ERR_ARG, "unc_dtw_batch: offsets must ascend");
-        const uint64_t cols = ev_off[a + 1] - ev_off[a], rows = km_off[a + 1] - km_off[a];
-        if (cols >= (1ull << 31) || rows >= (1ull << 31)) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u: 2^31 or more rows or columns", a);
-        if (path && path_off[a + 1] < path_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: path_off must ascend");
-        DtwJob &j = jobs[a];
-        j.ev_off = ev_off[a] - ev_off[0];
-        j.km_off = km_off[a] - km_off[0];
-        j.rows = (uint32_t)rows; j.cols = (uint32_t)cols;
-        j.out = a;
-        const uint64_t room = path ? path_off[a + 1] - path_off[a] : 0;
-        j.path_cap = (uint32_t)std::min<uint64_t>(room, rows + cols - 1);
-        cells[a] = rows * cols;
-        words[a] = dtw_crumb_words(j.rows, j.cols);
+        cells[a] = (uint64_t)jobs[a].rows * jobs[a].cols;
+        words[a] = dtw_crumb_words(jobs[a].rows, jobs[a].cols);
     }
-    const uint64_t n_ev = ev_off[n] - ev_off[0], n_km = km_off[n] - km_off[0];
-    for (uint64_t i = 0; i < n_km; ++i)
-        if (kmers[km_off[0] + i] >= UNC_NKMER) return fail(UNC_ERR_ARG, "unc_dtw_batch: k-mer %u at %llu is not below %d", kmers[km_off[0] + i],
-                                                           (unsigned long long)(km_off[0] + i), UNC_NKMER);
-
-    // ---- device
-    HIPCHK(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
     if (workspace_bytes == 0) {
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -132,6 +103,7 @@ extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const 
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells[x] > cells[y]; });
     std::vector<uint32_t> todo;
     for (uint32_t a : order) {
+        if (skip && skip[a]) continue;
         if (words[a] * 4 > workspace_bytes) {
             res[a].score = 0; res[a].mean_score = 0; res[a].path_len = 0; res[a].status = UNC_DTW_TOO_LARGE; res[a].pad = 0;
         } else todo.push_back(a);
@@ -140,14 +112,11 @@ extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const 
 
     const float *d_model = nullptr;
     if (int rc = dtw_model_device(device, &d_model)) return rc;
-    DevBuf<float> d_events, d_lines;
-    DevBuf<uint16_t> d_kmers;
+    DevBuf<float> d_lines;
     DevBuf<uint32_t> d_crumbs, d_path, d_next;
     DevBuf<DtwJob> d_jobs;
     DevBuf<unc_dtw_result_t> d_res;
-    HIPCHK(d_events.alloc(n_ev)); HIPCHK(d_kmers.alloc(n_km)); HIPCHK(d_res.alloc(n)); HIPCHK(d_next.alloc(1));
-    HIPCHK(hipMemcpyAsync(d_events.p, events + ev_off[0], n_ev * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_kmers.p, kmers + km_off[0], n_km * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIPCHK(d_res.alloc(n)); HIPCHK(d_next.alloc(1));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
@@ -177,7 +146,7 @@ extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const 
         HIPCHK(hipMemcpyAsync(d_jobs.p, round.data(), nr * sizeof(DtwJob), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(d_next.p, 0, sizeof(uint32_t), st));
         DtwBatch b{};
-        b.events = d_events.p; b.kmers = d_kmers.p; b.model = d_model; b.jobs = d_jobs.p; b.n_jobs = nr;
+        b.events = d_events; b.kmers = d_kmers; b.model = d_model; b.jobs = d_jobs.p; b.n_jobs = nr;
         b.subseq = prm->subseq; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
         b.crumbs = d_crumbs.p; b.lines = d_lines.p; b.path = path ? d_path.p : nullptr; b.res = d_res.p; b.next = d_next.p;
         const uint32_t grid = std::min<uint32_t>(nr, (uint32_t)n_cu * 16u);
@@ -207,6 +176,49 @@ extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const 
         }
     }
     return UNC_OK;
+}
+
+extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
+                             const uint64_t *km_off, const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res,
+                             uint32_t *path, const uint64_t *path_off, void *stream) {
+    // ---- arguments: everything is checked before the device is touched
+    if (!events || !ev_off || !kmers || !km_off || !prm || !res) return fail(UNC_ERR_ARG, "unc_dtw_batch: null argument");
+    if (path && !path_off) return fail(UNC_ERR_ARG, "unc_dtw_batch: path without path_off");
+    if (device < 0 || device >= DTW_MAX_DEVICES) return fail(UNC_ERR_ARG, "unc_dtw_batch: device %d", device);
+    if (prm->subseq > UNC_DTW_COL) return fail(UNC_ERR_ARG, "unc_dtw_batch: unknown subseq %u", prm->subseq);
+    if (prm->cost > UNC_DTW_R94D) return fail(UNC_ERR_ARG, "unc_dtw_batch: unknown cost %u", prm->cost);
+    g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
+    if (n == 0) return UNC_OK;
+    std::vector<DtwJob> jobs(n);
+    for (uint32_t a = 0; a < n; ++a) {
+        if (ev_off[a + 1] <= ev_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u has no events", a);
+        if (km_off[a + 1] <= km_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u has no k-mers", a);
+        if (a && (ev_off[a] < ev_off[a - 1] || km_off[a] < km_off[a - 1])) return fail(UNC_ERR_ARG, "unc_dtw_batch: offsets must ascend");
+        const uint64_t cols = ev_off[a + 1] - ev_off[a], rows = km_off[a + 1] - km_off[a];
+        if (cols >= (1ull << 31) || rows >= (1ull << 31)) return fail(UNC_ERR_ARG, "unc_dtw_batch: alignment %u: 2^31 or more rows or columns", a);
+        if (path && path_off[a + 1] < path_off[a]) return fail(UNC_ERR_ARG, "unc_dtw_batch: path_off must ascend");
+        DtwJob &j = jobs[a];
+        j.ev_off = ev_off[a] - ev_off[0];
+        j.km_off = km_off[a] - km_off[0];
+        j.rows = (uint32_t)rows; j.cols = (uint32_t)cols;
+        j.out = a;
+        const uint64_t room = path ? path_off[a + 1] - path_off[a] : 0;
+        j.path_cap = (uint32_t)std::min<uint64_t>(room, rows + cols - 1);
+    }
+    const uint64_t n_ev = ev_off[n] - ev_off[0], n_km = km_off[n] - km_off[0];
+    for (uint64_t i = 0; i < n_km; ++i)
+        if (kmers[km_off[0] + i] >= UNC_NKMER) return fail(UNC_ERR_ARG, "unc_dtw_batch: k-mer %u at %llu is not below %d", kmers[km_off[0] + i],
+                                                           (unsigned long long)(km_off[0] + i), UNC_NKMER);
+
+    // ---- device
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<float> d_events;
+    DevBuf<uint16_t> d_kmers;
+    HIPCHK(d_events.alloc(n_ev)); HIPCHK(d_kmers.alloc(n_km));
+    HIPCHK(hipMemcpyAsync(d_events.p, events + ev_off[0], n_ev * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_kmers.p, kmers + km_off[0], n_km * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    return dtw_run_device(device, n, d_events.p, d_kmers.p, jobs.data(), nullptr, prm, workspace_bytes, res, path, path_off, st);
 }
 
 // ------------------------------------------------------------------ BwaIndex::get_kmers
