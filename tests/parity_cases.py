@@ -80,6 +80,7 @@ def case_radix_sort(lib, big=False):
         vals = rng.integers(0, 2 ** 63, size=n, dtype=np.uint64)
         sk2, sv = capi.sort_pairs(keys, vals, bits, lib=lib)
         assert np.array_equal(sk2, sk) and np.array_equal(sv, vals[want]), (n, bits)
+    case_radix_sort_edges(lib)
 
 
 def case_events_sweep_reads(lib, oracle_lib, example):
@@ -1162,3 +1163,203 @@ def case_chunked_per_channel_calibration(lib, oracle_lib, example, goldens, n_ch
     assert mapped >= 0.6 * len(reads), (mapped, len(reads))
     assert all(reads[k][1].size > pool.chunk_len for k in reads) and any(want[k][1] > 1 for k in reads)     # reads of several chunks
     return mapped, len(reads)
+
+
+# ---------------------------------------------------------------- the FM layer (fm_dev.h, k_taps.hip) against tests/fm_naive.py
+# Tiny references whose rows end, and whose primary row falls, at every edge of the 64-symbol blocks of the 32-bit rank table and the
+# 128-symbol blocks of the BWA layout; each is loaded as k_map meets it (32-bit table, dense SA), on the BWA-sampled SA, and without
+# the 32-bit table (the 64-bit arithmetic of the references of 2^32 rows and more).
+FM_RANDOM_LPAC = (1, 2, 3, 5, 16, 31, 32, 33, 63, 64, 65, 96, 127, 128, 129)
+FM_PRIMARY_SEEDS = {291: 1, 51: 63, 198: 64, 75: 65, 146: 127, 13: 128}       # default_rng(seed).integers(0, 4, 64) -> the primary row
+FM_DEGENERATE = ("allA", "period2", "period2rc", "unit21")
+FM_SELF_ALIGN = ("random-33", "random-64", "random-129", "contigs")
+FM_LOADS = (("default", {}), ("bwa_sa", {"UNC_DENSE_SA": "0"}), ("no_fm32", {"UNC_FM32": "0"}))
+FM_REFERENCES = tuple("random-%d" % n for n in FM_RANDOM_LPAC) + tuple("primary-%d" % s for s in FM_PRIMARY_SEEDS) + FM_DEGENERATE + ("contigs",)
+_fm_cache = {}
+
+
+def fm_reference_codes(name):
+    """-> (codes, contig lengths or None)"""
+    kind, _, arg = name.partition("-")
+    if kind == "random":
+        return np.random.default_rng(0).integers(0, 4, int(arg)).astype(np.uint8), None
+    if kind == "primary":
+        return np.random.default_rng(int(arg)).integers(0, 4, 64).astype(np.uint8), None
+    if kind == "allA":
+        return np.zeros(64, dtype=np.uint8), None                               # the text is A^64 T^64
+    if kind == "period2":
+        return np.tile(np.array([0, 1], dtype=np.uint8), 32), None              # (AC)^32 (GT)^32
+    if kind == "period2rc":
+        return np.tile(np.array([0, 3], dtype=np.uint8), 32), None              # (AT)^64: its own reverse complement
+    if kind == "unit21":
+        return np.tile(np.random.default_rng(21).integers(0, 4, 21).astype(np.uint8), 4)[:64], None
+    if kind == "contigs":
+        return np.random.default_rng(7).integers(0, 4, 1000).astype(np.uint8), [300, 700]
+    raise KeyError(name)
+
+
+def fm_reference(name, tmp_path):
+    """the index files of a reference under tmp_path -> (prefix, its NaiveFM with the k-mer ranges and trajectories worked out once)"""
+    from tests import fm_naive
+    codes, lens = fm_reference_codes(name)
+    prefix = tmp_path / name
+    if name not in _fm_cache:
+        fm = fm_naive.build(prefix, codes, lens)
+        fm.kr = fm.kmer_ranges()
+        fm.traj = fm.self_align() if name in FM_SELF_ALIGN else None
+        _fm_cache[name] = fm
+    else:
+        from uncalled_amd.build_index import build_from_codes
+        lens = lens or [codes.size]
+        build_from_codes(prefix, ["c%d" % i for i in range(len(lens))], [""] * len(lens), lens, codes)
+    return prefix, _fm_cache[name]
+
+
+def _first_diff(got_s, got_e, want_s, want_e, s, e, c):
+    bad = np.flatnonzero((got_s != want_s) | (got_e != want_e))
+    if bad.size == 0:
+        return None
+    i = int(bad[0])
+    return "%d of %d steps differ; the first: get_neighbor(%d, %d, %d) = (%d, %d), naive (%d, %d)" % (
+        bad.size, s.size, s[i], e[i], c[i], got_s[i], got_e[i], want_s[i], want_e[i])
+
+
+def fm_queries(fm):
+    """(s, e, c) of the backward steps asked of a reference.  Up to 258 rows: every range 1 <= s <= e <= seq_len with every base,
+    and every INVERTED pair e + 1 < s <= seq_len + 1 -- no path holds one, but fm_nbr_issue guards its shared-block load against them
+    (`kk <= ll`) and the tap answers them with the two plain ranks.  The 2 000-row reference: every single-row range and 20 000 random ones, with e == seq_len, s - 1 == primary and e == primary among them."""
+    n = fm.n
+    if n <= 258:
+        i, j = np.triu_indices(n)                       # i <= j
+        s, e = i + 1, j + 1
+        i2, j2 = np.triu_indices(n, 1)                  # i2 < j2: e = i2 + 1, s = j2 + 2  (e + 1 < s <= n + 1)
+        s, e = np.concatenate((s, j2 + 2)), np.concatenate((e, i2 + 1))
+    else:
+        rng = np.random.default_rng(n)
+        m = 20000
+        rs = rng.integers(1, n + 1, m)
+        re = np.minimum(n, rs + np.where(rng.integers(0, 2, m) == 0, rng.integers(0, 70, m), rng.integers(0, n, m)))
+        re[:2000] = n                                                       # e == seq_len
+        rs[2000:3000] = fm.primary + 1                                      # s - 1 == primary
+        re[2000:3000] = np.minimum(n, fm.primary + 1 + rng.integers(0, 300, 1000))
+        re[3000:4000] = fm.primary                                          # e == primary
+        rs[3000:4000] = np.maximum(1, fm.primary - rng.integers(0, 300, 1000))
+        rows = np.arange(1, n + 1)
+        s, e = np.concatenate((rows, rs)), np.concatenate((rows, re))
+    s, e = np.repeat(s, 4), np.repeat(e, 4)
+    c = np.tile(np.arange(4), s.size // 4)
+    return s.astype(np.uint64), e.astype(np.uint64), c.astype(np.uint8)
+
+
+def case_fm_tiny(lib, oracle_lib, tmp_path, monkeypatch, name):
+    prefix, fm = fm_reference(name, tmp_path)
+    n = fm.n
+    kind, _, arg = name.partition("-")
+    if kind == "primary":
+        assert (n, fm.primary) == (128, FM_PRIMARY_SEEDS[int(arg)]), (name, fm.primary)
+    s, e, c = fm_queries(fm)
+    want_s, want_e = fm.get_neighbors(s, e, c)
+    rows = np.arange(n + 1, dtype=np.uint64)
+    want_sa = fm.sa_rows()
+    # the oracle on the same files: the naive module is not wrong the way the device is
+    oix = oracle_lib.Index(prefix)
+    assert int(oix.size) == n
+    assert np.array_equal(oix.kmer_ranges(), fm.kr), name
+    legal = np.flatnonzero(s <= e)
+    for i in legal[:: max(1, legal.size // 300)]:
+        assert oix.get_neighbor(int(s[i]), int(e[i]), int(c[i])) == (int(want_s[i]), int(want_e[i])), (name, s[i], e[i], c[i])
+    for r in range(0, n + 1, max(1, n // 300)):
+        assert oix.sa(r) == int(want_sa[r]), (name, r)
+    sizes = {}
+    for what, env in FM_LOADS:
+        for k in ("UNC_DENSE_SA", "UNC_FM32"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        ix = capi.Index(prefix, lib=lib)
+        sizes[what] = ix.device_bytes()
+        assert ix.size == n
+        got_s, got_e = ix.get_neighbor(s, e, c)
+        assert _first_diff(got_s, got_e, want_s, want_e, s, e, c) is None, (name, what, _first_diff(got_s, got_e, want_s, want_e, s, e, c))
+        got_sa = ix.sa(rows)
+        bad = np.flatnonzero(got_sa != want_sa)
+        assert bad.size == 0, (name, what, "sa(%d) = %d, naive %d" % (bad[0], got_sa[bad[0]], want_sa[bad[0]]))
+        kr = ix.kmer_ranges()
+        bad = np.flatnonzero((kr != fm.kr).any(axis=1))
+        assert bad.size == 0, (name, what, "k-mer %d: %s, naive %s" % (bad[0], kr[bad[0]], fm.kr[bad[0]]))
+        if fm.traj is not None:
+            lens, full_len = ix.self_align(prefix, 1, cap=64)
+            assert [int(x) for x in full_len] == [len(t) for t in fm.traj], (name, what)
+            for i, t in enumerate(fm.traj):
+                assert [int(x) for x in lens[i, :min(64, len(t))]] == t[:64] and not lens[i, len(t):].any(), (name, what, i)
+        ix.close()
+    # the knobs did what they say: the dense table / the 32-bit table are what the two other loads leave out
+    assert sizes["default"] - sizes["bwa_sa"] == ((n + 2) // 2) * 12 + 16, sizes
+    assert sizes["default"] - sizes["no_fm32"] == ((n + 63) // 64 + 1) * 32, sizes
+
+
+# ---------------------------------------------------------------- the suffix sort (k_sort.hip) at its edges
+SA_EDGE_LENGTHS = (1, 2, 20, 21, 22, 41, 42, 43, 63, 64, 65, 2047, 2048, 2049, 4097)
+
+
+def sa_edge_texts(n):
+    """texts of n symbols around the 21-symbol first key: (name, codes)"""
+    rng = np.random.default_rng(1000 + n)
+    yield "random", rng.integers(0, 4, n).astype(np.uint8)
+    yield "zeros", np.zeros(n, dtype=np.uint8)                              # ties run to the end of the text: doubling until k > n / 2
+    yield "period2", (np.arange(n) & 1).astype(np.uint8)
+    yield "unit21", np.tile(rng.integers(0, 4, 21).astype(np.uint8), n // 21 + 1)[:n]      # ties exactly one first key wide
+    t = rng.integers(0, 4, n).astype(np.uint8)
+    t[-30:] = 0                                                             # symbol 0 against the past-the-end marker of the first key
+    yield "zero_tail", t
+
+
+def case_suffix_sort_edges(lib):
+    from uncalled_amd.build_index import suffix_array
+    for n in SA_EDGE_LENGTHS:
+        for name, t in sa_edge_texts(n):
+            s = bytes(t + 1)
+            naive = np.array(sorted(range(n), key=lambda i: s[i:]), dtype=np.int64)
+            got = capi.build_suffix_array(t, 0, lib)
+            assert np.array_equal(got, naive), (n, name)
+            assert np.array_equal(suffix_array(t), naive), (n, name)
+
+
+def case_radix_sort_edges(lib):
+    """unc_sort_pairs_u64 on the inputs a random draw does not give: one key, two values per digit, sorted and reversed keys, a top
+    digit that is partly used -- around the 2 048-pair tile, values given and generated."""
+    rng = np.random.default_rng(2)
+    for n in (65, 2047, 4096, 4097):
+        two = np.where(rng.integers(0, 2, n) == 0, np.uint64(0x01FE01FE01FE01FE), np.uint64(0xFE01FE01FE01FE01))
+        inputs = [("equal", np.full(n, 0x0123456789ABCDEF, dtype=np.uint64), 64),
+                  ("two_values", two, 64), ("two_values_low_byte", two & np.uint64(0xFF), 8),
+                  ("ascending", np.arange(n, dtype=np.uint64), 16), ("descending", np.arange(n, dtype=np.uint64)[::-1].copy(), 16),
+                  ("bits9", rng.integers(0, 1 << 9, n, dtype=np.uint64), 9), ("bits17", rng.integers(0, 1 << 17, n, dtype=np.uint64), 17)]
+        for name, keys, bits in inputs:
+            want = np.argsort(keys, kind="stable").astype(np.uint64)
+            sk, perm = capi.sort_pairs(keys, None, bits, lib=lib)
+            assert np.array_equal(perm, want) and np.array_equal(sk, keys[want]), (n, name, "iota")
+            vals = rng.integers(0, 2 ** 63, size=n, dtype=np.uint64)
+            sk2, sv = capi.sort_pairs(keys, vals, bits, lib=lib)
+            assert np.array_equal(sk2, keys[want]) and np.array_equal(sv, vals[want]), (n, name, "values")
+
+
+# ---------------------------------------------------------------- unc_match_probs beyond one read's levels
+def case_match_probs_levels(lib, oracle_lib, example):
+    """PoreModel::match_prob of all 1 024 k-mers (k_match_probs) for levels over the whole range of a normalised read, every model mean
+    itself (a difference of exactly zero) and the values a float can take at its ends -- bit for bit what the oracle gives, NaN where it
+    gives NaN."""
+    dev_index = _index(lib, example)
+    rng = np.random.default_rng(5)
+    means = np.asarray(oracle_lib.model_tables()[0], dtype=np.float32)
+    special = np.array([0.0, -0.0, 1e-40, 1e30, -1e30, np.inf, -np.inf, np.nan], dtype=np.float32)
+    levels = np.concatenate((rng.uniform(40.0, 140.0, 1000).astype(np.float32), means, special))
+    assert levels.size == 2032 and np.signbit(special[1]) and 0 < special[2] < np.finfo(np.float32).tiny
+    got = dev_index.match_probs(levels)
+    want = np.stack([oracle_lib.match_probs(lv) for lv in levels])
+    nan = np.isnan(want)
+    assert nan[-1].all() and not nan[:-3].any()      # (NaN in, NaN out; no finite level gives one)
+    assert np.array_equal(np.isnan(got), nan)
+    bad = np.argwhere((got.view(np.uint32) != want.view(np.uint32)) & ~nan)
+    assert bad.size == 0, "%d differ; level %r, k-mer %d: %r, oracle %r" % (
+        len(bad), levels[bad[0][0]], bad[0][1], got[tuple(bad[0])], want[tuple(bad[0])])

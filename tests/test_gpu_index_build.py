@@ -107,6 +107,12 @@ def test_radix_sort_against_numpy(hip_lib):
     case_radix_sort(hip_lib, big=True)
 
 
+def test_suffix_array_at_the_edges_of_the_first_key(hip_lib):
+    """tests/test_lanesim_parity.py::test_suffix_array_at_the_edges_of_the_first_key on the GPU"""
+    from tests.parity_cases import case_suffix_sort_edges
+    case_suffix_sort_edges(hip_lib)
+
+
 def test_device_built_suffix_array_against_naive(tmp_path, hip_lib, oracle_lib):
     """20 kb slice: SA of every row of the device-built index (through the C ABI on the GPU: unc_fm_sa) == naive suffix array of
     fwd + revcomp; the oracle on the same files agrees row by row (as tests/test_oracle.py does for the bundled `bwa index` files)."""

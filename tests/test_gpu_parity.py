@@ -22,6 +22,16 @@ def test_fm_primitives(hip_lib, oracle_lib, example, goldens):
     pc.case_fm_primitives(hip_lib, oracle_lib, example, goldens)
 
 
+@pytest.mark.parametrize("name", pc.FM_REFERENCES)
+def test_fm_layer_on_tiny_references(hip_lib, oracle_lib, tmp_path, monkeypatch, name):
+    """tests/test_lanesim_parity.py::test_fm_layer_on_tiny_references on the GPU"""
+    pc.case_fm_tiny(hip_lib, oracle_lib, tmp_path, monkeypatch, name)
+
+
+def test_match_probs_over_the_level_range(hip_lib, oracle_lib, example):
+    pc.case_match_probs_levels(hip_lib, oracle_lib, example)
+
+
 def test_events_and_normaliser(hip_lib, oracle_lib, example, goldens):
     pc.case_events_and_normaliser(hip_lib, oracle_lib, example, goldens)
 

@@ -57,6 +57,25 @@ def test_suffix_array_built_behind_the_c_abi(sim_lib):
         assert np.array_equal(capi.build_suffix_array(t, 0, sim_lib), suffix_array(t)), n
 
 
+def test_suffix_array_at_the_edges_of_the_first_key(sim_lib):
+    """unc_build_suffix_array against the sorted suffixes themselves (and the numpy prefix doubling) at the lengths around one, two and
+    three first keys of 21 symbols and around the sort's tile of 2 048, on texts whose ties end at the text's end (all zeros, period 2),
+    are exactly one first key wide (a 21-symbol unit tiled), or set symbol 0 against the first key's past-the-end marker (a zero tail)."""
+    pc.case_suffix_sort_edges(sim_lib)
+
+
+@pytest.mark.parametrize("name", pc.FM_REFERENCES)
+def test_fm_layer_on_tiny_references(sim_lib, oracle_lib, tmp_path, monkeypatch, name):
+    """fm_dev.h and the kernels of k_taps.hip against tests/fm_naive.py: every backward step, every SA row, the k-mer ranges and the
+    self-alignment of references whose last block is partial, empty or exactly full and whose primary row sits on a block edge, with the
+    32-bit rank table, on the BWA-sampled SA (UNC_DENSE_SA=0) and on the 64-bit arithmetic (UNC_FM32=0)."""
+    pc.case_fm_tiny(sim_lib, oracle_lib, tmp_path, monkeypatch, name)
+
+
+def test_match_probs_over_the_level_range(sim_lib, oracle_lib, example):
+    pc.case_match_probs_levels(sim_lib, oracle_lib, example)
+
+
 def test_events_of_the_reads_the_sweep_found_wrong(sim_lib, oracle_lib, example):
     pc.case_events_sweep_reads(sim_lib, oracle_lib, example)
 

@@ -312,9 +312,11 @@ extern "C" int unc_index_load(const char *bwa_prefix, const char *idx_preset, in
     }
     // References of fewer than 2^32 rows (the reference's own 32-bit regime, range.hpp:37) get the 32-bit rank table k_map
     // works on there (fm_dev.h: 32 bytes per 64 symbols, counts with L2 folded in, symbols as bit planes), checked against the
-    // BWA-format arithmetic on 16 384 pseudo-random steps.
+    // BWA-format arithmetic on 16 384 pseudo-random steps.  UNC_FM32=0 (tests) leaves the table out: key_len_bits is then 0 below, and
+    // the taps and k_map run the 64-bit arithmetic of the references of 2^32 rows and more on a small one.
     d.fm32 = nullptr;
-    if (n < 0xFFFFFF00ull) {
+    const char *fm32_env = getenv("UNC_FM32");
+    if (n < 0xFFFFFF00ull && !(fm32_env && fm32_env[0] == '0')) {
         const uint32_t n_blk = (uint32_t)((n + 63) / 64 + 1);
         HIPCHK(ix->d_fm32.alloc((size_t)n_blk * 8));
         launch_build_fm32(d, ix->d_fm32.p, n_blk, nullptr);
