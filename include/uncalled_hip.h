@@ -339,8 +339,9 @@ int unc_build_suffix_array(int device, const uint8_t *codes, uint64_t n, int64_t
 /* ---- signal-to-reference alignment: replaces DTW<float, u16, Func> (src/dtw.hpp:31-186) with the two cost functions the
  * reference ships, DTWr94p (dtw.hpp:188-210: -PoreModel::match_prob of the r9.4 TEMPLATE model, pore_model.hpp:163-165) and DTWr94d
  * (dtw.hpp:212-233: |event - model mean|), for a whole batch of alignments.  Rows are the reference k-mers, columns the event
- * means.  Full matrix, no band: every cell is the reference's float arithmetic (dtw.hpp:51-74), so scores and paths are the
- * reference's bit for bit.  Only 2 bits per cell (the back-pointer) reach HBM; the scores live in registers. */
+ * means.  unc_dtw_batch: full matrix, no band: every cell is the reference's float arithmetic (dtw.hpp:51-74), so scores and paths
+ * are the reference's bit for bit.  Only 2 bits per cell (the back-pointer) reach HBM; the scores live in registers.
+ * unc_dtw_band_batch: the same arithmetic on the cells of a band around the diagonal (below). */
 #define UNC_DTW_NONE 0u   /* DTWSubSeq::NONE: global alignment */
 #define UNC_DTW_ROW 1u    /* DTWSubSeq::ROW: the events may align to a sub-range of the k-mers */
 #define UNC_DTW_COL 2u    /* DTWSubSeq::COL: the k-mers may align to a sub-range of the events */
@@ -362,6 +363,8 @@ typedef struct {
 #define UNC_DTW_OK 0u
 #define UNC_DTW_TOO_LARGE 1u        /* the alignment's back-pointers alone exceed the workspace: not computed, score and path_len are 0 */
 #define UNC_DTW_PATH_TRUNCATED 2u   /* path_len exceeds the room the caller gave: score and path_len are right, the first pairs are written */
+#define UNC_DTW_BAND_TOO_NARROW 5u   /* band calls: the band does not hold a path to the last cell: not computed, score and path_len are 0 */
+#define UNC_DTW_LEFT_BAND 6u        /* band calls: the traceback met a cell outside the band and stopped (see unc_dtw_band_batch) */
 typedef struct {
     float score, mean_score;        /* DTW::score / DTW::mean_score, dtw.hpp:126-132 */
     uint64_t path_len;              /* DTW::get_path().size() */
@@ -377,8 +380,31 @@ typedef struct {
 int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
                   const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
                   const uint64_t *path_off, void *stream);
-/* milliseconds the DTW kernel of the calling thread's last unc_dtw_batch ran (HIP events on the stream, summed over its rounds), the
- * rounds it took and the bytes of back-pointers it held at most */
+/* unc_dtw_batch within a band of half-width `band` >= 1 around the diagonal; every other argument as unc_dtw_batch.  For an
+ * alignment of R rows (k-mers) and C columns (events), with W = band:
+ *   centre      c(j) = floor(j * R / C), in unsigned 64-bit arithmetic;
+ *   membership  cell (i, j) is in the band iff i + W >= c(j) and i <= c(j) + W.  c is non-decreasing, so a row's cells are one
+ *               interval of columns;
+ *   feasibility the band always holds (0, 0); it holds (R - 1, C - 1) and a connected monotone path iff ceil(R / C) <= W + 1.  An
+ *               alignment that violates this gets UNC_DTW_BAND_TOO_NARROW: not computed, score and path_len 0, the others unaffected;
+ *   recurrence  the reference's (dtw.hpp:51-74): the same float additions and multiplications, the same D, H, V tie rule, the same
+ *               values for predecessors outside the matrix.  A predecessor inside the matrix but outside the band reads as
+ *               FLT_MAX / 2, what the reference gives cells outside the matrix in a global alignment.  Cells outside the band are
+ *               neither computed nor stored: work and back-pointers are about C * (2 W + 1) cells, not R * C;
+ *   traceback   the reference's (dtw.hpp:100-119) from (R - 1, C - 1).  If the next cell lies outside the band -- only non-finite
+ *               scores lead there: a NaN event makes its whole column choose V, a -inf event lets D win its ties against an absent
+ *               cell -- the traceback stops: status UNC_DTW_LEFT_BAND, path_len counts the pairs up to and including the last cell
+ *               in the band, those pairs are written, the score is the last cell's as computed.  UNC_DTW_PATH_TRUNCATED keeps its
+ *               meaning; UNC_DTW_LEFT_BAND takes precedence where both apply.
+ * For finite events a banded cell's value is never below its full-matrix value (float add and multiply are monotone), hence: with
+ * every cell in the band (W >= R) results equal unc_dtw_batch's; with the full matrix's path inside the band, the bits of the score
+ * and the whole path equal the full matrix's.  The band is global only: band == 0, or prm->subseq != UNC_DTW_NONE, is UNC_ERR_ARG
+ * before anything touches the device.  workspace_bytes, rounds and UNC_DTW_TOO_LARGE go by the banded back-pointers. */
+int unc_dtw_band_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
+                       const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
+                       const uint64_t *path_off, void *stream);
+/* milliseconds the DTW kernel of the calling thread's last unc_dtw_batch / unc_dtw_band_batch ran (HIP events on the stream, summed
+ * over its rounds), the rounds it took and the bytes of back-pointers it held at most */
 int unc_dtw_last_timing(float *ms_kernel, uint32_t *rounds, uint64_t *crumb_bytes);
 /* host copies of the three tables of the r9.4 template model the DTW costs read (PoreModel(vector, cmpl=false), pore_model.hpp:77-103) */
 void unc_dtw_model_tables(float *means1024, float *vars_x2_1024, float *lognorm1024);
@@ -410,9 +436,10 @@ typedef struct {
     uint32_t flags;         /* UNC_ALIGN_*; a zeroed struct is dtw_test */
     uint32_t max_events;    /* a query with more columns than this is not aligned (dtw_test.cpp:156-159 uses 50000); 0 = no limit */
     unc_dtw_params_t dtw;   /* read with UNC_ALIGN_DTW_PARAMS only */
-    uint32_t pad;
+    uint32_t band;          /* 0: the full matrix; W > 0: the DTW stage runs as unc_dtw_band_batch with this half-width (global only) */
 } unc_align_opts_t;
-/* per-query status: UNC_DTW_OK, UNC_DTW_TOO_LARGE, UNC_DTW_PATH_TRUNCATED as unc_dtw_batch gives them, or one of */
+/* per-query status: UNC_DTW_OK, UNC_DTW_TOO_LARGE, UNC_DTW_PATH_TRUNCATED (with a band also UNC_DTW_BAND_TOO_NARROW and
+ * UNC_DTW_LEFT_BAND) as unc_dtw_batch / unc_dtw_band_batch give them, or one of */
 #define UNC_ALIGN_NO_COLUMNS 3u     /* nothing left to align: the slice is too short for an event, or every event was masked.  Not aligned */
 #define UNC_ALIGN_TOO_MANY 4u       /* more columns than opts.max_events.  Not aligned (counts, target, scale and shift are filled) */
 typedef struct {
@@ -428,7 +455,8 @@ typedef struct {
  * most lev_off[q+1] - lev_off[q] of them (a slice of n samples has at most n / 2 + 16 events): the tap that places a mismatch at a
  * stage.  path / path_off / workspace_bytes / stream: as unc_dtw_batch.  UNC_ERR_ARG before anything touches the device for a read index
  * past the batch, a slice outside its read, smp_st > smp_en with smp_en != 0, an empty k-mer run, a k-mer >= 1024 and whatever
- * unc_dtw_batch refuses in the DTW's parameters.  UNC_ERR_OVERFLOW, for the whole batch and after device work, if a slice of n samples
+ * unc_dtw_batch refuses in the DTW's parameters (with opts->band > 0: what unc_dtw_band_batch refuses, a subseq other than
+ * UNC_DTW_NONE among it).  UNC_ERR_OVERFLOW, for the whole batch and after device work, if a slice of n samples
  * gave more than n / 2 + 16 events: the detector's windows, which are enforced, space its peaks so that this cannot happen, and the
  * return code guards that room rather than reports on a query. */
 int unc_align_batch(int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,

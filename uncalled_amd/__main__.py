@@ -346,7 +346,7 @@ def kmer_str(k, klen=5):
     return "".join(KMER_BASES[(int(k) >> (2 * (klen - 1 - i))) & 3] for i in range(klen))
 
 
-def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False):
+def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False, band=0):
     """The batches behind `dtw`: reads = [(id, int16 samples, (range, offset, digitisation))], queries as load_dtw_queries gives
     them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels or None, path or None), in the order of `reads`."""
     import numpy as np
@@ -367,8 +367,8 @@ def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, devic
             qs.append((i, q["smp_st"], q["smp_en"]))
             kms.append(capi.ref_kmers(index, prefix, names.index(q["ref"]), q["ref_st"], q["ref_en"], q["fwd"]))
         t0 = time.time()
-        out = capi.align_batch(raw, offsets, calib, qs, kms, opts=capi.align_opts(max_events=max_events), levels=want_paths, paths=want_paths,
-                               device=device)
+        out = capi.align_batch(raw, offsets, calib, qs, kms, opts=capi.align_opts(max_events=max_events, band=band), levels=want_paths,
+                               paths=want_paths, device=device)
         sec = (time.time() - t0) / max(1, len(part))
         res, levs, paths = out if want_paths else (out, [None] * len(part), [None] * len(part))
         for i, (rid, _, _) in enumerate(part):
@@ -395,12 +395,16 @@ def dtw_cmd(args):
             reads.append((r.id, r.raw_i16, r.calibration))
     index = capi.Index(args.index_prefix, device=args.device)
     for rid, r, sec, km, lev, path in dtw_align(index, args.index_prefix, reads, queries, max_events=args.max_events, batch=args.batch_queries,
-                                                device=args.device, want_paths=args.out_prefix is not None):
+                                                device=args.device, want_paths=args.out_prefix is not None, band=args.band):
         st = int(r["status"])
         if st == capi.ALIGN_TOO_MANY:
             sys.stderr.write("Skipping %s\n" % rid)            # dtw_test.cpp:156-159
             continue
-        if st != capi.DTW_OK:
+        if st == capi.DTW_BAND_TOO_NARROW:
+            sys.stdout.write("%s\t%.6g\t%.6g\tstatus %d\n" % (rid, 0.0, sec, st))      # (nothing computed: the line says why)
+            sys.stdout.flush()
+            continue
+        if st not in (capi.DTW_OK, capi.DTW_LEFT_BAND):
             sys.stderr.write("Skipping %s: %s\n" % (rid, "no events left to align" if st == capi.ALIGN_NO_COLUMNS else "status %d" % st))
             continue
         if args.out_prefix is not None:
@@ -408,7 +412,7 @@ def dtw_cmd(args):
             with open(args.out_prefix + rid + ".txt", "w") as out:
                 for j, i in path[::-1]:                          # from the start of the alignment to its end
                     out.write("%d\t%d\t%s\t%.6g\t%.6g\n" % (j, i, kmer_str(km[i]), lev[j], abs(float(lev[j]) - float(means[km[i]]))))
-        sys.stdout.write("%s\t%.6g\t%.6g\n" % (rid, float(r["dtw"]["mean_score"]), sec))
+        sys.stdout.write("%s\t%.6g\t%.6g%s\n" % (rid, float(r["dtw"]["mean_score"]), sec, "\tstatus %d" % st if st else ""))
         sys.stdout.flush()
 
 
@@ -484,6 +488,9 @@ def get_parser():
     p.add_argument("-o", "--out-prefix", type=str, default=None, help="Write the path of read ID to OUT_PREFIX + ID + .txt")
     p.add_argument("--max-events", type=int, default=50000, help="Skip reads with more events than this (the reference's 50000; 0: no limit -- "
                    "2 bits per cell make alignments affordable here that the reference skips)")
+    p.add_argument("--band", type=int, default=0, help="Align within a band of this half-width (in k-mers) around the diagonal: work and memory "
+                   "grow with the events times the band, not with events times k-mers (0: the full matrix). A line then ends in "
+                   "`status 5` (the band is too narrow to reach the end: not aligned) or `status 6` (the path left the band) where so")
     p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
 

@@ -124,6 +124,7 @@ class DTWParams(C.Structure):
 DTW_NONE, DTW_ROW, DTW_COL = 0, 1, 2                  # DTWSubSeq
 DTW_R94P, DTW_R94D = 0, 1                             # dtwcost_r94p / dtwcost_r94d
 DTW_OK, DTW_TOO_LARGE, DTW_PATH_TRUNCATED = 0, 1, 2   # unc_dtw_result_t.status
+DTW_BAND_TOO_NARROW, DTW_LEFT_BAND = 5, 6             # ... of band calls (3 and 4 are the ALIGN_* ones below)
 # the presets of dtw.hpp:15-28 (cost r94p; .with_cost(DTW_R94D) for the other)
 DTW_EVENT_GLOB = DTWParams(DTW_NONE, DTW_R94P, 2, 1, 100)
 DTW_EVENT_QSUB = DTWParams(DTW_COL, DTW_R94P, 2, 1, 100)
@@ -136,7 +137,7 @@ DTW_RESULT = np.dtype([("score", "<f4"), ("mean_score", "<f4"), ("path_len", "<u
 
 class AlignOpts(C.Structure):
     """unc_align_opts_t; AlignOpts() is dtw_test: events, stall mask, target from the k-mers, DTWr94d / NONE / 1, 1, 1."""
-    _fields_ = [("flags", C.c_uint32), ("max_events", C.c_uint32), ("dtw", DTWParams), ("pad", C.c_uint32)]
+    _fields_ = [("flags", C.c_uint32), ("max_events", C.c_uint32), ("dtw", DTWParams), ("band", C.c_uint32)]
 
 
 ALIGN_DTW_PARAMS, ALIGN_NO_MASK, ALIGN_RAW, ALIGN_TARGET_MODEL = 1, 2, 4, 8       # unc_align_opts_t.flags
@@ -234,6 +235,8 @@ def load(path=None):
     L.unc_trace_finish.argtypes = [vp, vp]
     if hasattr(L, "unc_dtw_batch"):                   # (the emulator build of the mapper's sources does not hold the DTW entry points)
         L.unc_dtw_batch.argtypes = [C.c_int, u32, vp, vp, vp, vp, C.POINTER(DTWParams), u64, vp, vp, vp, vp]
+        if hasattr(L, "unc_dtw_band_batch"):
+            L.unc_dtw_band_batch.argtypes = [C.c_int, u32, vp, vp, vp, vp, C.POINTER(DTWParams), u32, u64, vp, vp, vp, vp]
         L.unc_dtw_last_timing.argtypes = [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(u64)]
         L.unc_dtw_model_tables.argtypes = [vp, vp, vp]
         L.unc_dtw_model_tables.restype = None
@@ -342,11 +345,13 @@ def dtw_model_tables(lib=None):
     return a, b, c
 
 
-def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, device=0, stream=None, lib=None, full=False):
+def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, device=0, stream=None, lib=None, full=False, band=0):
     """unc_dtw_batch: DTWr94p / DTWr94d (dtw.hpp) of events_list[a] (columns) against kmers_list[a] (rows) for every a, on the GPU.
     -> (scores float32[n], mean scores float32[n], paths): paths[a] is DTW::get_path() as an (len, 2) uint32 array of (event, k-mer)
-    pairs, end cell first (None with paths=False, and for an alignment whose status is DTW_TOO_LARGE).  full=True returns the
-    DTW_RESULT records (score, mean_score, path_len, status) in place of the first two."""
+    pairs, end cell first (None with paths=False, and for an alignment that was not computed: status DTW_TOO_LARGE or
+    DTW_BAND_TOO_NARROW).  full=True returns the DTW_RESULT records (score, mean_score, path_len, status) in place of the first two.
+    band=W > 0: unc_dtw_band_batch, the same within a band of half-width W around the diagonal (global alignment only); with
+    status DTW_LEFT_BAND paths[a] holds the pairs up to the last cell in the band."""
     L = lib or load()
     n = len(events_list)
     if n != len(kmers_list):
@@ -366,12 +371,16 @@ def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, de
     if paths:
         path_off = np.cumsum([0] + [max(0, e.size + k.size - 1) for e, k in zip(evs, kms)]).astype(np.uint64)
         path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
-    _check(L, L.unc_dtw_batch(int(device), n, ev.ctypes.data, ev_off.ctypes.data, km.ctypes.data, km_off.ctypes.data, C.byref(params),
-                              int(workspace_bytes), res.ctypes.data, path.ctypes.data if paths else None,
-                              path_off.ctypes.data if paths else None, stream))
+    args = (int(workspace_bytes), res.ctypes.data, path.ctypes.data if paths else None, path_off.ctypes.data if paths else None, stream)
+    if band:
+        _check(L, L.unc_dtw_band_batch(int(device), n, ev.ctypes.data, ev_off.ctypes.data, km.ctypes.data, km_off.ctypes.data,
+                                       C.byref(params), int(band), *args))
+    else:
+        _check(L, L.unc_dtw_batch(int(device), n, ev.ctypes.data, ev_off.ctypes.data, km.ctypes.data, km_off.ctypes.data, C.byref(params),
+                                  *args))
     out_paths = None
     if paths:
-        out_paths = [None if res["status"][a] == DTW_TOO_LARGE else path[int(path_off[a]):int(path_off[a]) + int(res["path_len"][a])].copy()
+        out_paths = [None if res["status"][a] in (DTW_TOO_LARGE, DTW_BAND_TOO_NARROW) else path[int(path_off[a]):int(path_off[a]) + int(res["path_len"][a])].copy()
                      for a in range(n)]
     if full:
         return res, out_paths
@@ -379,21 +388,23 @@ def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, de
 
 
 def dtw_last_timing(lib=None):
-    """(kernel milliseconds, rounds, bytes of back-pointers held at most) of the calling thread's last dtw_batch."""
+    """(kernel milliseconds, rounds, bytes of back-pointers held at most) of the calling thread's last dtw_batch, with or without a band."""
     L = lib or load()
     ms, rounds, nbytes = C.c_float(), C.c_uint32(), C.c_uint64()
     L.unc_dtw_last_timing(C.byref(ms), C.byref(rounds), C.byref(nbytes))
     return ms.value, rounds.value, nbytes.value
 
 
-def align_opts(dtw=None, mask=True, create_events=True, target="kmers", max_events=0):
-    """AlignOpts from words: dtw = a DTWParams (None: dtw_test's), target = "kmers" | "model"."""
+def align_opts(dtw=None, mask=True, create_events=True, target="kmers", max_events=0, band=0):
+    """AlignOpts from words: dtw = a DTWParams (None: dtw_test's), target = "kmers" | "model", band = the DTW's half-width (0: the
+    full matrix)."""
     if target not in ("kmers", "model"):
         raise ValueError("target is 'kmers' or 'model'")
     o = AlignOpts()
     o.flags = (ALIGN_DTW_PARAMS if dtw is not None else 0) | (0 if mask else ALIGN_NO_MASK) | (0 if create_events else ALIGN_RAW) | \
         (ALIGN_TARGET_MODEL if target == "model" else 0)
     o.max_events = int(max_events)
+    o.band = int(band)
     if dtw is not None:
         o.dtw = dtw
     return o
@@ -449,7 +460,7 @@ def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None
     if levels:
         out.append([lev[int(lev_off[q]):int(lev_off[q]) + int(res["n_kept"][q])].copy() for q in range(n)])
     if paths:
-        done = (DTW_OK, DTW_PATH_TRUNCATED)
+        done = (DTW_OK, DTW_PATH_TRUNCATED, DTW_LEFT_BAND)
         out.append([path[int(path_off[q]):int(path_off[q]) + int(res["dtw"]["path_len"][q])].copy() if res["status"][q] in done else None
                     for q in range(n)])
     return out[0] if len(out) == 1 else tuple(out)

@@ -15,12 +15,16 @@ using namespace unc_host;
 extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
                              const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
                              const uint64_t *path_off, void *stream) __attribute__((weak));
+extern "C" int unc_dtw_band_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
+                                  const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes,
+                                  unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) __attribute__((weak));
 namespace {
 template <uint32_t COST> struct DtwOne {
     std::vector<std::pair<uint64_t, uint64_t>> path;
     float score_sum = 0, mean = 0;
-    DtwOne(const std::vector<float> &means, const std::vector<uint16_t> &kmers, const unc_dtw_params_t &prms) {
-        if (!unc_dtw_batch) throw std::runtime_error("this build of the library has no unc_dtw_batch");
+    // band (not in the reference's signature): 0 = the full matrix, W > 0 = unc_dtw_band_batch with that half-width
+    DtwOne(const std::vector<float> &means, const std::vector<uint16_t> &kmers, const unc_dtw_params_t &prms, uint32_t band = 0) {
+        if (!unc_dtw_batch || (band && !unc_dtw_band_batch)) throw std::runtime_error("this build of the library has no unc_dtw_batch");
         unc_dtw_params_t p = prms;
         p.cost = COST;
         const uint64_t ev_off[2] = {0, means.size()}, km_off[2] = {0, kmers.size()};
@@ -30,9 +34,13 @@ template <uint32_t COST> struct DtwOne {
         unc_dtw_result_t r{};
         const float none_f = 0;
         const uint16_t none_k = 0;
-        if (unc_dtw_batch(0, 1, means.empty() ? &none_f : means.data(), ev_off, kmers.empty() ? &none_k : kmers.data(), km_off, &p, 0, &r,
-                          pairs.data(), path_off, nullptr) != UNC_OK)
-            throw std::runtime_error(unc_last_error());
+        const float *e = means.empty() ? &none_f : means.data();
+        const uint16_t *k = kmers.empty() ? &none_k : kmers.data();
+        const int rc = band ? unc_dtw_band_batch(0, 1, e, ev_off, k, km_off, &p, band, 0, &r, pairs.data(), path_off, nullptr)
+                            : unc_dtw_batch(0, 1, e, ev_off, k, km_off, &p, 0, &r, pairs.data(), path_off, nullptr);
+        if (rc != UNC_OK) throw std::runtime_error(unc_last_error());
+        if (r.status == UNC_DTW_BAND_TOO_NARROW) throw std::runtime_error("the band is too narrow to reach the last cell");
+        if (r.status == UNC_DTW_LEFT_BAND) throw std::runtime_error("the traceback left the band");
         if (r.status != UNC_DTW_OK) throw std::runtime_error("the alignment does not fit the device's memory");
         score_sum = r.score; mean = r.mean_score;
         path.reserve(r.path_len);
@@ -43,7 +51,8 @@ template <uint32_t COST> struct DtwOne {
     float mean_score() const { return mean; }
 };
 template <class T> void bind_dtw(py::class_<T> &c) {
-    c.def(py::init<const std::vector<float> &, const std::vector<uint16_t> &, const unc_dtw_params_t &>())
+    c.def(py::init<const std::vector<float> &, const std::vector<uint16_t> &, const unc_dtw_params_t &, uint32_t>(), py::arg("means"),
+          py::arg("kmers"), py::arg("prms"), py::arg("band") = 0u)
         .def("get_path", &T::get_path).def("score", &T::score).def("mean_score", &T::mean_score);
 }
 }  // namespace

@@ -1,5 +1,6 @@
 // Batched full-matrix dynamic time warping of event means against reference k-mers: DTW<float, u16, Func>::compute_matrix and
-// ::traceback (src/dtw.hpp:51-120) with the costs of DTWr94p / DTWr94d (dtw.hpp:188-214).
+// ::traceback (src/dtw.hpp:51-120) with the costs of DTWr94p / DTWr94d (dtw.hpp:188-214).  (dtw_band_one, further down, is the same
+// arithmetic on the cells of a band around the diagonal.)
 //
 // One wavefront per alignment, alignments taken from a queue in descending cell count.  The matrix is swept in strips of 64 rows
 // (k-mers), one row per lane, skewed: in step t lane l computes column t - l, so that its three predecessors are its own last
@@ -201,9 +202,173 @@ template <int COST> __global__ void __launch_bounds__(64) k_dtw(DtwBatch B) {
     }
 }
 
+// ---- the band.  The same sweep over fewer cells: cell (i, j) exists iff i + W >= c(j) and i <= c(j) + W, c(j) = floor(j * rows /
+// cols); global alignment only.  A row's cells are one column interval [lo, hi], a strip sweeps the union of its rows' intervals,
+// [wlo, whi] = [lo(first row), hi(last row)], in whi - wlo + 1 steps plus the skew: in step t lane l is at column wlo + t - l and
+// computes iff that lies in its own interval.  A lane outside its interval holds DTW_MAX_COST, the value an absent cell reads as,
+// so that H (its own last value), V (lane l - 1's value one step ago) and D (the V of the step before) need no further masking;
+// lane 0 masks what it reads from the line by the interval of the row above, because the line holds values of two strips ago at
+// the columns the strip above never wrote.  Back-pointers: per strip dtw_band_step_blocks() blocks of 16 steps over its window
+// only, step = column - wlo + lane.  The traceback keeps the intervals of the 64 rows of the strip it is in, one per lane, and
+// stops before it would read a cell outside them (only non-finite scores lead there).
+template <int COST> __device__ void dtw_band_one(const DtwBatch &B, const DtwJob &J) {
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t rows = uniform32(J.rows), cols = uniform32(J.cols);
+    const uint32_t W = dtw_band_eff(rows, uniform32(B.band));
+    const float dw = B.dw, hw = B.hw, vw = B.vw;
+    const float *ev = B.events + J.ev_off;
+    const uint16_t *km = B.kmers + J.km_off;
+    uint32_t *crumbs = B.crumbs + J.crumb_off;
+    const uint64_t line_floats = dtw_line_floats(cols);
+    float *line0 = B.lines + J.line_off, *line1 = line0 + line_floats;
+    const uint32_t n_strips = (uint32_t)dtw_strips(rows), n_blocks = (uint32_t)dtw_band_step_blocks(rows, cols, W);
+
+    float score = 0.0f;
+    uint32_t plo = 1, phi = 0;              // the interval of the row above the strip (none above the first)
+    for (uint32_t s = 0; s < n_strips; ++s) {
+        const uint32_t i = s * 64 + lane;
+        const bool row_ok = i < rows;
+        const uint32_t last_lane = rows - 1 - s * 64 < 63u ? rows - 1 - s * 64 : 63u;
+        const float *lin = (s & 1u) ? line0 : line1;
+        float *lout = (s & 1u) ? line1 : line0;
+        float mu = 0.0f, v2 = 1.0f, ln = 0.0f;
+        uint32_t lo = 1, hi = 0;
+        if (row_ok) {
+            const uint32_t k = km[i];
+            mu = B.model[k]; v2 = B.model[1024 + k]; ln = B.model[2048 + k];
+            lo = dtw_band_lo(i, rows, cols, W); hi = dtw_band_hi(i, rows, cols, W);
+        }
+        const uint32_t wlo = lane_value(lo, 0), llo = lane_value(lo, last_lane), whi = lane_value(hi, last_lane);
+        // (whi >= wlo whenever the band is feasible, and the steps fit the strip's room by dtw_band_width; neither is left to trust)
+        uint32_t n_steps = whi >= wlo ? whi - wlo + 1 + last_lane : 0;
+        if (n_steps > n_blocks * 16) n_steps = n_blocks * 16;
+        float cur = DTW_MAX_COST;
+        // D of lane 0's first cell: the matrix's corner, or the cell left of the window in the row above
+        float prev_up = DTW_MAX_COST;
+        if (lane == 0) {
+            if (i == 0) prev_up = 0.0f;
+            else if (wlo > 0 && wlo - 1 >= plo && wlo - 1 <= phi) prev_up = lin[wlo - 1];
+        }
+        float e = 0.0f, ev_reg = 0.0f, in_reg = DTW_MAX_COST, out_reg = 0.0f;
+        uint32_t cw = 0;
+        uint32_t *cstrip = crumbs + (uint64_t)s * n_blocks * 64;
+        for (uint32_t t = 0; t < n_steps; ++t) {
+            const uint32_t u = t & 63u;
+            if (u == 0) {
+                const uint32_t c = wlo + t + lane;
+                ev_reg = c < cols ? ev[c] : 0.0f;
+                in_reg = c >= plo && c <= phi ? lin[c] : DTW_MAX_COST;
+            }
+            float e_in = __shfl_up(e, 1), up = __shfl_up(cur, 1);
+            const float e0 = lane_value(ev_reg, u), up0 = lane_value(in_reg, u);
+            if (lane == 0) { e_in = e0; up = up0; }
+            e = e_in;
+            const uint32_t j = wlo + t - lane;          // (wraps below the window: then above hi)
+            const bool act = t >= lane && j >= lo && j <= hi;
+            const float c = dtw_cost<COST>(e, mu, v2, ln);
+            const float ds = __fadd_rn(prev_up, __fmul_rn(dw, c));
+            const float hs = __fadd_rn(cur, __fmul_rn(hw, c));
+            const float vs = __fadd_rn(up, __fmul_rn(vw, c));
+            float m;
+            uint32_t mv;
+            if (ds <= hs && ds <= vs) { m = ds; mv = MOVE_D; }
+            else if (hs <= vs) { m = hs; mv = MOVE_H; }
+            else { m = vs; mv = MOVE_V; }
+            prev_up = up;
+            cur = act ? m : DTW_MAX_COST;
+            if (act) cw |= mv << (2u * (t & 15u));
+            if ((t & 15u) == 15u || t == n_steps - 1) {
+                UNC_SIM_CHECK((uint64_t)s * n_blocks * 64 + (uint64_t)(t >> 4) * 64 + lane < dtw_band_crumb_words(rows, cols, W));
+                cstrip[(uint64_t)(t >> 4) * 64 + lane] = cw;
+                cw = 0;
+            }
+            // the strip's last row over its own interval, for the strip below
+            const float lv = lane_value(cur, last_lane);
+            const uint32_t jl = wlo + t - last_lane;
+            if (s + 1 < n_strips && t >= last_lane && jl >= llo && jl <= whi) {
+                if (lane == (jl & 63u)) out_reg = lv;
+                if (((jl & 63u) == 63u || jl == whi) && lane <= (jl & 63u) && (jl & ~63u) + lane >= llo) {
+                    UNC_SIM_CHECK((jl & ~63u) + lane < cols);
+                    lout[(jl & ~63u) + lane] = out_reg;
+                }
+            }
+        }
+        if (s == n_strips - 1) score = lane_value(cur, last_lane);       // the last step computed (rows - 1, cols - 1)
+        plo = llo; phi = whi;
+        __threadfence();
+    }
+    score = __uint_as_float(uniform32(__float_as_uint(score)));
+
+    // traceback from (rows - 1, cols - 1).  lo / hi: the intervals of the 64 rows of strip held_s, one per lane
+    const bool want_path = B.path != nullptr;
+    const uint32_t cap = J.path_cap;
+    uint2 *path = want_path ? reinterpret_cast<uint2 *>(B.path) + J.path_off : nullptr;
+    uint32_t i = rows - 1, j = cols - 1, held_s = DTW_NONE_IDX, held_b = DTW_NONE_IDX, w = 0, lo = 1, hi = 0, wlo = 0;
+    uint32_t pj = 0, pi = 0;
+    uint64_t p = 0;
+    bool left = false;
+    for (;;) {
+        const uint32_t s = i >> 6, l = i & 63u;
+        if (s != held_s) {
+            const uint32_t r = s * 64 + lane;
+            lo = 1; hi = 0;
+            if (r < rows) { lo = dtw_band_lo(r, rows, cols, W); hi = dtw_band_hi(r, rows, cols, W); }
+            wlo = lane_value(lo, 0);
+            held_s = s; held_b = DTW_NONE_IDX;
+        }
+        const uint32_t t = j - wlo + l, b = t >> 4;
+        if (j < lane_value(lo, l) || j > lane_value(hi, l) || b >= n_blocks) { left = true; break; }     // no such cell: nothing stored
+        if (lane == (uint32_t)(p & 63u)) { pj = j; pi = i; }
+        ++p;
+        if ((p & 63u) == 0) {
+            const uint64_t at = p - 64 + lane;
+            if (want_path && at < cap) path[at] = make_uint2(pj, pi);
+        }
+        if (i == 0 && j == 0) break;
+        if (b != held_b) {
+            w = crumbs[((uint64_t)s * n_blocks + b) * 64 + lane];
+            held_b = b;
+        }
+        const uint32_t mv = (lane_value(w, l) >> (2u * (t & 15u))) & 3u;
+        if (i == 0 || (mv == MOVE_H && j > 0)) --j;
+        else if (j == 0 || mv == MOVE_V) --i;
+        else { --i; --j; }
+    }
+    if ((p & 63u) != 0) {
+        const uint64_t at = (p & ~(uint64_t)63) + lane;
+        if (want_path && lane < (uint32_t)(p & 63u) && at < cap) path[at] = make_uint2(pj, pi);
+    }
+    if (lane == 0) {
+        unc_dtw_result_t r;
+        r.score = score;
+        r.mean_score = 0.0f;
+        r.path_len = p;
+        r.status = left ? UNC_DTW_LEFT_BAND : want_path && p > cap ? UNC_DTW_PATH_TRUNCATED : UNC_DTW_OK;
+        r.pad = 0;
+        B.res[J.out] = r;
+    }
+}
+
+template <int COST> __global__ void __launch_bounds__(64) k_dtw_band(DtwBatch B) {
+    for (;;) {
+        uint32_t q = 0;
+        if (lane_id() == 0) q = atomicAdd(B.next, 1u);
+        q = uniform32(q);
+        if (q >= B.n_jobs) return;
+        const DtwJob J = B.jobs[q];
+        dtw_band_one<COST>(B, J);
+        wave_sync();
+    }
+}
+
 }  // namespace
 
 void launch_dtw(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st) {
+    if (b.band) {
+        if (cost == UNC_DTW_R94D) hipLaunchKernelGGL(k_dtw_band<(int)UNC_DTW_R94D>, dim3(grid), dim3(64), 0, st, b);
+        else hipLaunchKernelGGL(k_dtw_band<(int)UNC_DTW_R94P>, dim3(grid), dim3(64), 0, st, b);
+        return;
+    }
     if (cost == UNC_DTW_R94D) hipLaunchKernelGGL(k_dtw<(int)UNC_DTW_R94D>, dim3(grid), dim3(64), 0, st, b);
     else hipLaunchKernelGGL(k_dtw<(int)UNC_DTW_R94P>, dim3(grid), dim3(64), 0, st, b);
 }

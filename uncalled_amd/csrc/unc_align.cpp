@@ -67,6 +67,7 @@ extern "C" int unc_align_batch(int device, const unc_params_t *params, const unc
     if (O.flags & UNC_ALIGN_DTW_PARAMS) prm = O.dtw;
     if (prm.subseq > UNC_DTW_COL) return fail(UNC_ERR_ARG, "unc_align_batch: unknown subseq %u", prm.subseq);
     if (prm.cost > UNC_DTW_R94D) return fail(UNC_ERR_ARG, "unc_align_batch: unknown cost %u", prm.cost);
+    if (O.band && prm.subseq != UNC_DTW_NONE) return fail(UNC_ERR_ARG, "unc_align_batch: the band is global only (subseq %u)", prm.subseq);
     unc_params_t P;
     if (params) P = *params;
     else unc_params_default(&P);
@@ -212,8 +213,8 @@ extern "C" int unc_align_batch(int device, const unc_params_t *params, const unc
         const uint64_t room = path ? path_off[q + 1] - path_off[q] : 0;
         j.path_cap = skip[q] ? 0 : (uint32_t)std::min<uint64_t>(room, (uint64_t)j.rows + j.cols - 1);
     }
-    if (int rc = dtw_run_device(device, n_queries, d_levels.p, d_kmers.p, jobs.data(), skip.data(), &prm, workspace_bytes, dres.data(), path,
-                                path_off, st))
+    if (int rc = dtw_run_device(device, n_queries, d_levels.p, d_kmers.p, jobs.data(), skip.data(), &prm, O.band, workspace_bytes, dres.data(),
+                                path, path_off, st))
         return rc;
     (void)unc_dtw_last_timing(&g_align_ms[3], nullptr, nullptr);
     for (uint32_t q = 0; q < n_queries; ++q) {

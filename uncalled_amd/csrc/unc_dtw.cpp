@@ -1,5 +1,6 @@
-// Host side of the DTW entry points of include/uncalled_hip.h: argument checks, the queue of alignments in descending cell count, the
-// split of a batch into rounds that fit the workspace, and BwaIndex::get_kmers on the packed reference (host only).
+// Host side of the DTW entry points of include/uncalled_hip.h: argument checks, the queue of alignments in descending cell count
+// (with a band: descending steps), the split of a batch into rounds that fit the workspace, and BwaIndex::get_kmers on the packed
+// reference (host only).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -84,13 +85,20 @@ struct HipEvent {       // (timing only)
 
 // The queue, the rounds and the launches over columns and k-mers that lie in device memory already (dtw_dev.h).
 int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
-                        const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off,
-                        hipStream_t st) {
+                        const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
+                        const uint64_t *path_off, hipStream_t st) {
     g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
     std::vector<uint64_t> cells(n), words(n);
     for (uint32_t a = 0; a < n; ++a) {
-        cells[a] = (uint64_t)jobs[a].rows * jobs[a].cols;
-        words[a] = dtw_crumb_words(jobs[a].rows, jobs[a].cols);
+        const uint32_t rows = jobs[a].rows, cols = jobs[a].cols;
+        if (band) {     // the banded layout: a wavefront's steps and the back-pointers of the strips' windows
+            const uint32_t W = dtw_band_eff(rows, band);
+            cells[a] = dtw_band_steps(rows, cols, W);
+            words[a] = dtw_band_crumb_words(rows, cols, W);
+        } else {
+            cells[a] = (uint64_t)rows * cols;
+            words[a] = dtw_crumb_words(rows, cols);
+        }
     }
     if (workspace_bytes == 0) {
         size_t free_b = 0, total_b = 0;
@@ -104,8 +112,10 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
     std::vector<uint32_t> todo;
     for (uint32_t a : order) {
         if (skip && skip[a]) continue;
-        if (words[a] * 4 > workspace_bytes) {
-            res[a].score = 0; res[a].mean_score = 0; res[a].path_len = 0; res[a].status = UNC_DTW_TOO_LARGE; res[a].pad = 0;
+        const bool narrow = band && !dtw_band_feasible(jobs[a].rows, jobs[a].cols, band);
+        if (narrow || words[a] * 4 > workspace_bytes) {
+            res[a].score = 0; res[a].mean_score = 0; res[a].path_len = 0; res[a].pad = 0;
+            res[a].status = narrow ? UNC_DTW_BAND_TOO_NARROW : UNC_DTW_TOO_LARGE;
         } else todo.push_back(a);
     }
     if (todo.empty()) return UNC_OK;
@@ -147,7 +157,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
         HIPCHK(hipMemsetAsync(d_next.p, 0, sizeof(uint32_t), st));
         DtwBatch b{};
         b.events = d_events; b.kmers = d_kmers; b.model = d_model; b.jobs = d_jobs.p; b.n_jobs = nr;
-        b.subseq = prm->subseq; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
+        b.subseq = prm->subseq; b.band = band; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
         b.crumbs = d_crumbs.p; b.lines = d_lines.p; b.path = path ? d_path.p : nullptr; b.res = d_res.p; b.next = d_next.p;
         const uint32_t grid = std::min<uint32_t>(nr, (uint32_t)n_cu * 16u);
         HIPCHK(hipEventRecord(t0.e, st));
@@ -178,9 +188,10 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
     return UNC_OK;
 }
 
-extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
-                             const uint64_t *km_off, const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res,
-                             uint32_t *path, const uint64_t *path_off, void *stream) {
+// unc_dtw_batch (band == 0) and unc_dtw_band_batch (band > 0: its own two rules are checked by the entry point)
+static int dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
+                     const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
+                     const uint64_t *path_off, void *stream) {
     // ---- arguments: everything is checked before the device is touched
     if (!events || !ev_off || !kmers || !km_off || !prm || !res) return fail(UNC_ERR_ARG, "unc_dtw_batch: null argument");
     if (path && !path_off) return fail(UNC_ERR_ARG, "unc_dtw_batch: path without path_off");
@@ -218,7 +229,22 @@ extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const 
     HIPCHK(d_events.alloc(n_ev)); HIPCHK(d_kmers.alloc(n_km));
     HIPCHK(hipMemcpyAsync(d_events.p, events + ev_off[0], n_ev * sizeof(float), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_kmers.p, kmers + km_off[0], n_km * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    return dtw_run_device(device, n, d_events.p, d_kmers.p, jobs.data(), nullptr, prm, workspace_bytes, res, path, path_off, st);
+    return dtw_run_device(device, n, d_events.p, d_kmers.p, jobs.data(), nullptr, prm, band, workspace_bytes, res, path, path_off, st);
+}
+
+extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
+                             const uint64_t *km_off, const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res,
+                             uint32_t *path, const uint64_t *path_off, void *stream) {
+    return dtw_batch(device, n, events, ev_off, kmers, km_off, prm, 0, workspace_bytes, res, path, path_off, stream);
+}
+
+extern "C" int unc_dtw_band_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
+                                  const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes,
+                                  unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) {
+    if (band == 0) return fail(UNC_ERR_ARG, "unc_dtw_band_batch: a band of 0 (unc_dtw_batch is the full matrix)");
+    if (prm && prm->subseq != UNC_DTW_NONE && prm->subseq <= UNC_DTW_COL)
+        return fail(UNC_ERR_ARG, "unc_dtw_band_batch: the band is global only (subseq %u)", prm->subseq);
+    return dtw_batch(device, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream);
 }
 
 // ------------------------------------------------------------------ BwaIndex::get_kmers
