@@ -301,7 +301,8 @@ typedef struct unc_rt unc_rt_t;
 int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint32_t n_channels, unc_rt_t **out);
 void unc_rt_free(unc_rt_t *rt);
 uint64_t unc_rt_device_bytes(const unc_rt_t *rt);
-/* raw: int16 samples (host, or device when on_device != 0); chunks/results: host arrays of n_chunks */
+/* raw: int16 samples (host, or device when on_device != 0); chunks/results: host arrays of n_chunks.  A call that is rejected
+ * with UNC_ERR_ARG leaves the unc_rt_t and results[] exactly as they were before the call. */
 int unc_rt_process_chunks(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, const int16_t *raw, int on_device,
                           void *stream, unc_rt_result_t *results);
 /* the same for chunks that already hold floats -- what the reference's Chunk keeps (src/chunk.cpp:27-66: float32 as sent by

@@ -570,6 +570,98 @@ def case_chunked_realtime_path(lib, oracle_lib, example, goldens, n_channels=3, 
                 assert int(got[i]["hit"][name]) == int(goldens["chunk_hits"][i][f[name]]), (i, name)
 
 
+def _off_target_chunks(n_samples=11000, chunk_len=4000):
+    """one simulated off-target read (it never maps), cut to n_samples: (signal, calibration, [(offset, length)] of its chunks)"""
+    from tools.simulate_reads import simulate_reads
+    sig = simulate_reads(np.zeros(20000, np.uint8), [20000], 1, seed=9, read_bases=5200, off_target=1.0)["signal"][:n_samples]
+    assert sig.size == n_samples
+    return sig, (CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION), [(o, min(chunk_len, n_samples - o)) for o in range(0, n_samples, chunk_len)]
+
+
+def _rt_chunk(channel, read_number, flags, offset, n_samples, cal):
+    ch = np.zeros(1, dtype=capi.RT_CHUNK)
+    ch["channel"], ch["read_number"], ch["flags"], ch["offset"], ch["n_samples"] = channel, read_number, flags, offset, n_samples
+    ch["calib"] = capi.make_calib(1, *cal)[0]
+    return ch
+
+
+def _rt_flags(k, n):
+    return (capi.RT_FIRST if k == 0 else 0) | (capi.RT_LAST if k == n - 1 else 0)
+
+
+def case_chunked_rejected_call_leaves_no_trace(lib, oracle_lib, example, goldens, n_channels=2):
+    """A call that unc_rt_process_chunks rejects (UNC_ERR_ARG) changes nothing: object B gets, before the 2nd and before the 3rd
+    chunk of a read on channel 0, calls that must fail -- the read's valid next chunk first, the offending entry after it -- and
+    goes on to answer every valid call byte for byte as its undisturbed twin A, up to max_chunks = 3 on the third chunk; the final
+    record is the oracle's.  (A library that admits chunk 0 before it rejects the call counts the chunk twice: rd_len grows and
+    the read fails one chunk early.)  With two channels the three entries of the duplicate-channel call are already refused by
+    their number; with three channels the duplicate itself is."""
+    po = oracle_lib
+    dev_index = _index(lib, example)
+    p = capi.default_params(lib)
+    p.max_chunks = 3
+    chunk_len = int(p.chunk_time * p.sample_rate)
+    assert chunk_len == 4000
+    sig, cal, spans = _off_target_chunks(11000, chunk_len)
+    A, B = (capi.Realtime(dev_index, n_channels=n_channels, params=p) for _ in range(2))
+    valid = [_rt_chunk(0, 7, _rt_flags(k, len(spans)), o, n, cal) for k, (o, n) in enumerate(spans)]
+    other = _rt_chunk(1, 8, capi.RT_FIRST, 0, 1000, cal)
+    twice = ([other, other], "more chunks than channels" if n_channels == 2 else "two chunks for channel 1 in one call")
+    beyond = ([_rt_chunk(n_channels, 8, capi.RT_FIRST, 0, 1000, cal)], "chunk 1: channel %d out of range" % n_channels)
+    too_long = ([_rt_chunk(1, 8, capi.RT_FIRST, 0, chunk_len + 1, cal)], "chunk 1 longer than chunk_time \\* sample_rate")
+    bad_calls = {1: [twice, beyond], 2: [too_long, twice]}
+    last = None
+    for k, ch in enumerate(valid):
+        for extra, message in bad_calls.get(k, []):
+            with pytest.raises(capi.UncalledHipError, match=message):
+                B.process_chunks(np.concatenate([ch] + extra), raw_i16=sig)
+        a, b = A.process_chunks(ch, raw_i16=sig), B.process_chunks(ch, raw_i16=sig)
+        assert a.tobytes() == b.tobytes(), (k, a, b)
+        if k == 1:
+            assert a[0]["state"] == capi.RT_MAPPING      # the read is still open when the second round of bad calls comes
+        last = b[0]
+    assert last["state"] == capi.RT_FAILED and not last["ended"]      # max_chunks on the third chunk, not the last-chunk exit
+    oix = po.Index(example["prefix"])
+    om = po.Mapper(oix)
+    om.set_max_chunks(3)
+    want, used = om.chunk_read(po.calibrate(sig, *cal), chunk_len)
+    assert (used, om.rt_ended()) == (3, False)
+    assert capi.hit_paf_cols(last["hit"], dev_index.seq_names()) == po.hit_paf_cols(want, oix.ref_names())
+    for f in ("event_i", "n_nbr", "n_sa", "n_lf", "notes"):
+        assert int(last["hit"][f]) == int(want[f]), f
+    assert int(last["hit"]["status"]) == 0 and not want["mapped"]
+    # channel 1 never started a read: nothing of the rejected calls' entries was admitted
+    assert B.process_chunks(_rt_chunk(1, 8, 0, 0, 1000, cal), raw_i16=sig)[0]["state"] == capi.RT_IGNORED
+    A.close()
+    B.close()
+
+
+def case_chunked_ignored_chunks(lib, oracle_lib, example, goldens):
+    """UNC_RT_IGNORED: a chunk without UNC_RT_FIRST on an idle channel, and a chunk of read 6 on a channel that is mapping read 5,
+    give an empty result (hit.rid = -1) and leave read 5 to finish as on an undisturbed twin -- also when the ignored chunk comes
+    first in a call, so that the launch's first block is not the call's first chunk."""
+    dev_index = _index(lib, example)
+    sig, cal, spans = _off_target_chunks(11000, 4000)
+    R, T = (capi.Realtime(dev_index, n_channels=2) for _ in range(2))
+    ignored = np.zeros(1, dtype=capi.RT_RESULT)
+    ignored["state"], ignored["hit"]["rid"] = capi.RT_IGNORED, -1
+    valid = [_rt_chunk(0, 5, _rt_flags(k, len(spans)), o, n, cal) for k, (o, n) in enumerate(spans)]
+    idle = _rt_chunk(1, 3, 0, 0, 2000, cal)
+    assert R.process_chunks(idle, raw_i16=sig).tobytes() == ignored.tobytes()
+    first = R.process_chunks(valid[0], raw_i16=sig)
+    assert first.tobytes() == T.process_chunks(valid[0], raw_i16=sig).tobytes() and first[0]["state"] == capi.RT_MAPPING
+    assert R.process_chunks(_rt_chunk(0, 6, 0, 4000, 4000, cal), raw_i16=sig).tobytes() == ignored.tobytes()
+    both = R.process_chunks(np.concatenate([idle, valid[1]]), raw_i16=sig)
+    assert both[:1].tobytes() == ignored.tobytes()
+    assert both[1:].tobytes() == T.process_chunks(valid[1], raw_i16=sig).tobytes() and both[1]["state"] == capi.RT_MAPPING
+    both = R.process_chunks(np.concatenate([valid[2], _rt_chunk(1, 6, capi.RT_LAST, 0, 2000, cal)]), raw_i16=sig)
+    assert both[1:].tobytes() == ignored.tobytes()
+    assert both[:1].tobytes() == T.process_chunks(valid[2], raw_i16=sig).tobytes()
+    assert both[0]["state"] == capi.RT_FAILED and both[0]["ended"] and int(both[0]["hit"]["rd_len"]) > 0      # given up at its last chunk
+    R.close()
+    T.close()
+
+
 def case_cluster_overflow_remap(lib, oracle_lib, example, goldens):
     """The reference's SeedTracker is unbounded; reads that outgrow the per-slot cluster array are re-mapped on the device
     with more room until they fit.  Forced here with an absurdly small array."""

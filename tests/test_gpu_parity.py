@@ -72,6 +72,15 @@ def test_chunked_realtime_path(hip_lib, oracle_lib, example, goldens, n_channels
     pc.case_chunked_realtime_path(hip_lib, oracle_lib, example, goldens, n_channels, n_reads, max_chunks, long_read)
 
 
+@pytest.mark.parametrize("n_channels", [2, 3])
+def test_chunked_rejected_call_leaves_no_trace(hip_lib, oracle_lib, example, goldens, n_channels):
+    pc.case_chunked_rejected_call_leaves_no_trace(hip_lib, oracle_lib, example, goldens, n_channels)
+
+
+def test_chunked_ignored_chunks(hip_lib, oracle_lib, example, goldens):
+    pc.case_chunked_ignored_chunks(hip_lib, oracle_lib, example, goldens)
+
+
 def test_cluster_overflow_remap(hip_lib, oracle_lib, example, goldens):
     pc.case_cluster_overflow_remap(hip_lib, oracle_lib, example, goldens)
 

@@ -143,3 +143,38 @@ def test_failed_growth_leaves_the_mapper_usable(sim_lib, example):
     m.close()
     ix.close()
     assert _live(sim_lib) == start
+
+
+def test_chunk_after_a_failed_round_of_the_last_allowed_chunk(sim_lib, example):
+    """The one way to Mapper::add_chunk's chunks_maxed() exit (mapper.cpp:289-296) in unc_rt_process_chunks: every call that maps a
+    read's max_chunks-th chunk fails the read itself, unless the call dies on the device after the chunk was admitted -- here its
+    growth of the raw-signal buffer fails.  The read's next chunk is then dropped: the read fails without being given up (not
+    ENDED), its length is that of the chunks admitted so far, and the channel is free for a new read."""
+    gc.collect()
+    start = _live(sim_lib)
+    ix = capi.Index(example["prefix"], lib=sim_lib)
+    p = capi.default_params(sim_lib)
+    p.max_chunks = 2
+    rt = capi.Realtime(ix, n_channels=1, params=p)
+    sig = np.ascontiguousarray(example["signal"], dtype=np.int16)
+    assert sig.size >= 4000
+    short = rt.process_chunks(_chunk(example, 1, 1000), raw_i16=sig)
+    assert short[0]["state"] == capi.RT_MAPPING
+    more = _chunk(example, 1, 3000)
+    more["flags"], more["offset"] = 0, 1000
+    res = np.zeros(1, dtype=capi.RT_RESULT)
+    _arm(sim_lib, 1)
+    rc = sim_lib.unc_rt_process_chunks(rt.h, 1, more.ctypes.data, sig.ctypes.data, 0, None, res.ctypes.data)
+    _arm(sim_lib, 0)
+    assert rc == UNC_ERR_HIP, (rc, sim_lib.unc_last_error())
+    more["n_samples"] = 500
+    dropped = rt.process_chunks(more, raw_i16=sig)[0]
+    assert dropped["state"] == capi.RT_FAILED and not dropped["ended"] and not dropped["hit"]["mapped"]
+    assert int(dropped["hit"]["rd_len"]) == int(np.float32(4000) * (np.float32(p.bp_per_sec) / np.float32(p.sample_rate)))
+    assert int(dropped["hit"]["event_i"]) == int(short[0]["hit"]["event_i"]) and int(dropped["hit"]["n_events"]) == 0
+    assert rt.process_chunks(more, raw_i16=sig)[0]["state"] == capi.RT_IGNORED
+    again = rt.process_chunks(_chunk(example, 2, 1000), raw_i16=sig)
+    assert again[0]["state"] == short[0]["state"] and _same(again[0]["hit"], short[0]["hit"])
+    rt.close()
+    ix.close()
+    assert _live(sim_lib) == start

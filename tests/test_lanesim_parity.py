@@ -119,6 +119,15 @@ def test_chunked_realtime_path(sim_lib, oracle_lib, example, goldens, n_channels
     pc.case_chunked_realtime_path(sim_lib, oracle_lib, example, goldens, n_channels, n_reads, max_chunks)
 
 
+@pytest.mark.parametrize("n_channels", [2, 3])
+def test_chunked_rejected_call_leaves_no_trace(sim_lib, oracle_lib, example, goldens, n_channels):
+    pc.case_chunked_rejected_call_leaves_no_trace(sim_lib, oracle_lib, example, goldens, n_channels)
+
+
+def test_chunked_ignored_chunks(sim_lib, oracle_lib, example, goldens):
+    pc.case_chunked_ignored_chunks(sim_lib, oracle_lib, example, goldens)
+
+
 @pytest.mark.parametrize("team", [2, 1])
 def test_chunked_pool_chunks_go_back(sim_lib, oracle_lib, example, goldens, monkeypatch, team):
     """A channel's chunks of the node pool go back when its read is decided or replaced: six reads in a row on ONE channel with a pool

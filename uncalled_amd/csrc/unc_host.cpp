@@ -790,6 +790,14 @@ static int ensure_batch(unc_mapper *m, uint32_t n_reads, uint64_t total_samples,
     return UNC_OK;
 }
 
+// The DevReads view of the mapper's batch buffers as stage_batch last filled them; `raw`: where the kernels find sample 0.
+static DevReads batch_reads(const unc_mapper *m, const int16_t *raw, uint32_t n_reads) {
+    DevReads rd{};       // (no ring: ring0, new_read and ring_mod stay null / 0)
+    rd.raw = raw; rd.offsets = m->d_offsets.p; rd.calib = m->d_calib.p; rd.means = m->d_means.p; rd.moff = m->d_moff.p;
+    rd.info = m->d_info.p; rd.n_reads = n_reads; rd.tgt_mean = m->ix->model_mean; rd.tgt_stdv = m->ix->model_stdv;
+    return rd;
+}
+
 // uploads metadata, returns the DevReads view.  `offsets` and `calib` are copied into the mapper first and only the copies are
 // validated and handed to hipMemcpyAsync: from page-locked caller memory, or behind work queued on the stream, the copy to the device
 // runs after the call has returned, when the caller may already have reused its arrays (include/uncalled_hip.h)
@@ -825,10 +833,7 @@ static int stage_batch(unc_mapper *m, uint32_t n_reads, const int16_t *raw, cons
         HIPCHK(hipMemcpyAsync(m->d_raw.p, raw + base, total * 2, hipMemcpyHostToDevice, st));
         d_raw = m->d_raw.p - base;   // kernels index raw[offsets[i]..]
     }
-    rd->raw = d_raw; rd->offsets = m->d_offsets.p; rd->calib = m->d_calib.p; rd->means = m->d_means.p; rd->moff = m->d_moff.p;
-    rd->info = m->d_info.p; rd->n_reads = n_reads;
-    rd->tgt_mean = m->ix->model_mean; rd->tgt_stdv = m->ix->model_stdv;
-    rd->ring0 = nullptr; rd->new_read = nullptr; rd->ring_mod = 0;
+    *rd = batch_reads(m, d_raw, n_reads);
     return UNC_OK;
 }
 
@@ -952,12 +957,15 @@ extern "C" int unc_mapper_pool_usage(const unc_mapper_t *m, uint32_t *out4) {
 constexpr size_t FW = NKMER / 32;      // words of one read's sources_added_ bitmap
 typedef std::array<uint32_t, FW> Flags;
 
-// a launch of k_map on the mapper's own index, slots, pool, result array and queue head
-static MapArgs mapper_args(const unc_mapper *m, const DevReads &rd) {
+// a launch of k_map: these reads on this index, these slots and this pool; whatever else the launch needs, its caller names
+static MapArgs map_args(const unc_index *ix, const unc_params_t &P, const DevScratch &sc, const DevPool &pool, const DevReads &rd,
+                        DevResult *results, uint32_t *next_read) {
     MapArgs a;
-    a.ix = m->ix->dev; a.sc = m->sc.v; a.rd = rd; a.P = m->P; a.pool = m->pool.v; a.results = m->d_results.p; a.next_read = m->d_next.p;
+    a.ix = ix->dev; a.sc = sc; a.rd = rd; a.P = P; a.pool = pool; a.results = results; a.next_read = next_read;
     return a;
 }
+// ... on the mapper's own index, slots, pool, result array and queue head
+static MapArgs mapper_args(const unc_mapper *m, const DevReads &rd) { return map_args(m->ix, m->P, m->sc.v, m->pool.v, rd, m->d_results.p, m->d_next.p); }
 
 // A batch in two halves: _begin stages the reads and launches the kernels on the stream and returns; _end waits for them, maps the few
 // reads again that need it, and fills the hits.  Between the two the host is free -- and so is the GPU's tail: the persistent k_map
@@ -1482,20 +1490,11 @@ extern "C" int unc_trace_begin(unc_mapper_t *m, const int16_t *raw, uint32_t n, 
     return UNC_OK;
 }
 
-static int trace_reads(unc_mapper *m, DevReads *rd) {
-    rd->raw = m->d_raw.p; rd->offsets = m->d_offsets.p; rd->calib = m->d_calib.p; rd->means = m->d_means.p; rd->moff = m->d_moff.p;
-    rd->info = m->d_info.p; rd->n_reads = 1; rd->tgt_mean = m->ix->model_mean; rd->tgt_stdv = m->ix->model_stdv;
-    rd->ring0 = nullptr; rd->new_read = nullptr; rd->ring_mod = 0;
-    return UNC_OK;
-}
-
 extern "C" int unc_trace_step(unc_mapper_t *m, uint32_t n_events, int *done) {
     if (!m || !m->trace_active) return fail(UNC_ERR_ARG, "no trace in progress");
     if (m->pend.active) return fail(UNC_ERR_ARG, "unc_trace_step: the mapper has a batch in flight (unc_map_batch_end first)");
     HIPCHK(hipSetDevice(m->ix->device));
-    DevReads rd;
-    trace_reads(m, &rd);
-    MapArgs a = mapper_args(m, rd);
+    MapArgs a = mapper_args(m, batch_reads(m, m->d_raw.p, 1));      // the read unc_trace_begin staged
     a.max_steps = n_events; a.resume = 1;       // the read parked in slot 0, for n_events events more
     launch_map(a, 1, m->stream);
     HIPCHK(hipGetLastError());
@@ -1704,6 +1703,44 @@ template <class T> static int alloc_zeroed(DevBuf<T> &buf, size_t count, size_t 
     return UNC_OK;
 }
 
+// The DevReads view of a chunk round: descriptor b's events lie in its channel's ring (moff[b] = the ring's start in d_ring).
+static DevReads rt_reads(const unc_rt *rt, uint32_t n_chunks) {
+    DevReads rd{};       // (no raw, offsets or calib: k_map reads event means only)
+    rd.means = rt->d_ring.p; rd.moff = rt->d_moff.p; rd.info = rt->d_info.p; rd.n_reads = n_chunks; rd.tgt_mean = rt->ix->model_mean; rd.tgt_stdv = rt->ix->model_stdv;
+    rd.ring0 = rt->d_ring0.p; rd.new_read = rt->d_newread.p; rd.ring_mod = NORM_LEN;
+    return rd;
+}
+
+// wavefronts per channel (k_map_team): 8 unless UNC_RT_TEAM says 1 (the one-wavefront kernel), 2 or 4.  512 channels x 8 = the
+// 4096 wavefronts the chip holds; measured on E. coli thresholds, ms per round of 512 chunks: 110 / 102 / 90 / 84 with 1 / 2 / 4 / 8
+static uint32_t rt_team_size() {
+    const char *e = getenv("UNC_RT_TEAM");
+#ifdef LANESIM
+    // the emulator suite's default (teams of 2: 512 fibers per emulated workgroup are three times the run time) is a variable only
+    // the emulator build reads, so that it cannot change what the gfx950 library does in the same process (round-4 advice)
+    if (!e) e = getenv("UNC_SIM_RT_TEAM");
+#endif
+    const long v = e ? atol(e) : 8;
+    return v >= 8 ? 8u : v >= 4 ? 4u : v >= 2 ? 2u : 1u;
+}
+
+// The channels' node pool: 16 chunks (12 288 nodes) per channel on average, 64 on references of 2^26 rows and more (a read there
+// touches tens of thousands of buckets); `override_chunks` > 0 (UNC_RT_POOL_CHUNKS) replaces the answer.  A channel's chunks go back
+// when its read is decided; a read that finds the pool dry fails with its status set (there is no second pass in chunked mode).
+struct RtPoolSize { size_t n_chunks, wanted, clamped; };      // clamped: what `wanted` was cut to for want of HBM, 0 = it was not
+static RtPoolSize rt_pool_size(uint64_t seq_len, size_t n_channels, size_t free_b, long override_chunks) {
+    const size_t wanted = n_channels * (seq_len >= (1ull << 26) ? 64 : 16);
+    RtPoolSize r{wanted, wanted, 0};
+    // never more than 60 % of the HBM that is free now (the batch path's rule): next to a dense SA, or on a smaller GPU,
+    // the pool shrinks -- with a warning, and never below four chunks per channel -- instead of failing the whole create
+    const size_t fit = free_b / 5 * 3 / POOL_CHUNK_BYTES;
+    if (r.wanted > fit) r.n_chunks = r.clamped = std::max(fit, std::max<size_t>(64, n_channels * 4));
+    r.n_chunks = std::max<size_t>(64, r.n_chunks);
+    // (the override is taken as it is, also below the floor: how the tests make a pool small enough to notice a chunk not handed back)
+    if (override_chunks > 0) r.n_chunks = (size_t)override_chunks;
+    return r;
+}
+
 extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint32_t n_channels, unc_rt_t **out) {
     if (!ix || !p || !out || n_channels == 0) return fail(UNC_ERR_ARG, "bad argument");
     *out = nullptr;
@@ -1726,18 +1763,7 @@ extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint3
     struct Guard { unc_rt *p; ~Guard() { if (p) unc_rt_free(p); } } guard{rt};
     rt->ix = ix; rt->P = *p; rt->n_channels = n_channels;
     { const char *e = getenv("UNC_RT_PROFILE"); rt->profile = e && e[0] == '1'; }
-    // wavefronts per channel (k_map_team): 8 unless UNC_RT_TEAM says 1 (the one-wavefront kernel), 2 or 4.  512 channels x 8 = the
-    // 4096 wavefronts the chip holds; measured on E. coli thresholds, ms per round of 512 chunks: 110 / 102 / 90 / 84 with 1 / 2 / 4 / 8
-    {
-        const char *e = getenv("UNC_RT_TEAM");
-#ifdef LANESIM
-        // the emulator suite's default (teams of 2: 512 fibers per emulated workgroup are three times the run time) is a variable only
-        // the emulator build reads, so that it cannot change what the gfx950 library does in the same process (round-4 advice)
-        if (!e) e = getenv("UNC_SIM_RT_TEAM");
-#endif
-        const long v = e ? atol(e) : 8;
-        rt->team = v >= 8 ? 8u : v >= 4 ? 4u : v >= 2 ? 2u : 1u;
-    }
+    rt->team = rt_team_size();
     const size_t S = n_channels;
     size_t bytes = 0;
     {
@@ -1745,45 +1771,24 @@ extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint3
         int rc = alloc_scratch(rt->sc, *p, S, 1u << 20, 2 * p->max_paths, &bytes, ix->dev);
         if (rc) return rc;
         HIPCHK(hipMemset(rt->sc.v.base, 0, bytes));
-        // the channels' node pool: 16 chunks (12 288 nodes) per channel on average, 64 on references of 2^26 rows and more (a read
-        // there touches tens of thousands of buckets); UNC_RT_POOL_CHUNKS overrides.  A channel's chunks go back when its read is
-        // decided; a read that finds the pool dry fails with its status set (there is no second pass in chunked mode).
-        size_t per_ch = ix->seq_len >= (1ull << 26) ? 64 : 16;
-        size_t n_chunks = S * per_ch;
-        {
-            // never more than 60 % of the HBM that is free now (the batch path's rule): next to a dense SA, or on a smaller GPU,
-            // the pool shrinks -- with a warning, and never below four chunks per channel -- instead of failing the whole create
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(hipMemGetInfo(&free_b, &total_b));
-            free_b += spacer.bytes;
-            const size_t fit = free_b / 5 * 3 / POOL_CHUNK_BYTES;
-            if (n_chunks > fit) {
-                const size_t floor_chunks = std::max<size_t>(64, (size_t)S * 4);
-                const size_t clamped = std::max(fit, floor_chunks);
-                fprintf(stderr, "Warning: realtime node pool clamped from %zu to %zu chunks (%.1f GB of HBM free)\n", n_chunks, clamped, (double)free_b / 1e9);
-                n_chunks = clamped;
-            }
-        }
-        n_chunks = std::max<size_t>(64, n_chunks);
-        // (the override is taken as it is, also below the floor: how the tests make a pool small enough to notice a chunk that is not
-        // handed back)
-        if (const char *e = getenv("UNC_RT_POOL_CHUNKS")) { const long v = atol(e); if (v > 0) n_chunks = (size_t)v; }
-        rc = alloc_pool(rt->pool, (uint32_t)n_chunks, &bytes);
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        free_b += spacer.bytes;
+        const char *e = getenv("UNC_RT_POOL_CHUNKS");
+        const RtPoolSize ps = rt_pool_size(ix->seq_len, S, free_b, e ? atol(e) : 0);
+        if (ps.clamped)
+            fprintf(stderr, "Warning: realtime node pool clamped from %zu to %zu chunks (%.1f GB of HBM free)\n", ps.wanted, ps.clamped, (double)free_b / 1e9);
+        rc = alloc_pool(rt->pool, (uint32_t)ps.n_chunks, &bytes);
         if (rc) return rc;
     }
     {
         int rc = UNC_OK;
         auto zeroed = [&](auto &buf, size_t count) { if (rc == UNC_OK) rc = alloc_zeroed(buf, count, &bytes); };
-        zeroed(rt->d_chans, S);
-        zeroed(rt->d_ring, S * NORM_LEN);
-        zeroed(rt->d_desc, S);
-        zeroed(rt->d_info, S);
-        zeroed(rt->d_ring0, S);
-        zeroed(rt->d_newread, S);
-        zeroed(rt->d_slotmap, S);
-        zeroed(rt->d_next, 16);
-        zeroed(rt->d_moff, S + 1);
-        zeroed(rt->d_results, S);
+        zeroed(rt->d_chans, S);     zeroed(rt->d_ring, S * NORM_LEN);
+        zeroed(rt->d_desc, S);      zeroed(rt->d_info, S);
+        zeroed(rt->d_ring0, S);     zeroed(rt->d_newread, S);
+        zeroed(rt->d_slotmap, S);   zeroed(rt->d_next, 16);
+        zeroed(rt->d_moff, S + 1);  zeroed(rt->d_results, S);
         if (rc) return rc;
     }
     rt->device_bytes = bytes;
@@ -1825,169 +1830,164 @@ static uint32_t rt_notes(const SlotState &s, bool ended) {
     return notes;
 }
 
-static void rt_unmapped(const unc_rt *rt, const RtHostChan &hc, const SlotState &s, const unc_evt_info_t *inf, unc_hit_t *h, bool ended = true) {
-    DevResult res;
-    memset(&res, 0, sizeof res);
-    res.done = 2; res.status = s.status; res.event_i = s.event_i; res.notes = rt_notes(s, ended);
-    res.n_nbr = s.n_nbr; res.n_sa = s.n_sa; res.n_lf = s.n_lf;
-    unc_evt_info_t z;
-    memset(&z, 0, sizeof z);
-    fill_hit(rt->ix, rt->P, res, inf ? *inf : z, hc.raw_len, h);
+// The record of a channel's read from its slot state: the PAF record of a mapped read, else the unmapped one with the progress so far
+// (event_i, counters).  inf: the chunk's event counts, null for a chunk that was not launched; hit.status: the slot's | info.pad
+static void rt_hit(const unc_rt *rt, const RtHostChan &hc, const SlotState &s, const unc_evt_info_t *inf, bool mapped, bool finished, unc_hit_t *h) {
+    DevResult res{};
+    res.done = mapped ? 1 : 2; res.status = s.status | (inf ? inf->pad : 0u); res.event_i = s.event_i; res.notes = rt_notes(s, finished);
+    res.n_nbr = s.n_nbr; res.n_sa = s.n_sa; res.n_lf = s.n_lf; if (mapped) res.cluster = s.max_map;
+    fill_hit(rt->ix, rt->P, res, inf ? *inf : unc_evt_info_t{}, hc.raw_len, h);
 }
 
-// raw (int16 + per-chunk calibration) or raw_pa (floats taken as they are): exactly one of the two
-static int rt_process(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, const int16_t *raw, const float *raw_pa, int on_device,
-                      void *stream, unc_rt_result_t *results) {
-    if (!rt || !chunks || (!raw && !raw_pa) || !results) return fail(UNC_ERR_ARG, "null argument");
-    const size_t esz = raw_pa ? sizeof(float) : sizeof(int16_t);
+// step 1: everything is checked before anything is touched -- a call that fails here leaves `rt` and `results` as they were
+static int rt_check(const unc_rt *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, const void *raw, const unc_rt_result_t *results) {
+    if (!rt || !chunks || !raw || !results) return fail(UNC_ERR_ARG, "null argument");
     if (n_chunks > rt->n_channels) return fail(UNC_ERR_ARG, "more chunks than channels");
-    HIPCHK(hipSetDevice(rt->ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : rt->stream;
     const uint32_t chunk_len = (uint32_t)(rt->P.chunk_time * rt->P.sample_rate);
-
-    // ---- host decisions that the reference takes before any signal is touched (RealtimePool::add_chunk /
-    //      try_add_chunk, Mapper::add_chunk): which chunks start a read, continue one, or are dropped
-    std::vector<RtChunkDesc> desc;
-    std::vector<uint32_t> slotmap, newread, active;   // active[i] = index into chunks[]
-    std::vector<uint64_t> moff;
     std::vector<char> seen(rt->n_channels, 0);
-    uint64_t lo = ~0ull, hi = 0;
     for (uint32_t i = 0; i < n_chunks; ++i) {
         const unc_rt_chunk_t &c = chunks[i];
-        memset(&results[i], 0, sizeof results[i]);
-        results[i].hit.rid = -1;
         if (c.channel >= rt->n_channels) return fail(UNC_ERR_ARG, "chunk %u: channel %u out of range", i, c.channel);
         if (seen[c.channel]) return fail(UNC_ERR_ARG, "two chunks for channel %u in one call", c.channel);
         if (c.n_samples > chunk_len) return fail(UNC_ERR_ARG, "chunk %u longer than chunk_time * sample_rate", i);
         seen[c.channel] = 1;
+    }
+    return UNC_OK;
+}
+
+// What a call does with its chunks.  Block b of the launch maps chunks[launched[b]] with desc[b], slotmap[b], newread[b], moff[b] (+ one).
+struct RtPlan {
+    std::vector<uint32_t> launched, dropped;   // indices into chunks[]; dropped: of a read that has had its max_chunks, nothing to launch
+    std::vector<RtChunkDesc> desc;
+    std::vector<uint32_t> slotmap, newread;
+    std::vector<uint64_t> moff;
+    uint64_t lo = ~0ull, hi = 0;               // the launched chunks lie in samples [lo, hi)
+};
+
+// step 2: the host decisions that the reference takes before any signal is touched (RealtimePool::add_chunk / try_add_chunk,
+// Mapper::add_chunk), in chunk order: which chunks start a read, continue one, or are not of the read their channel is mapping
+static RtPlan rt_admit(unc_rt *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, unc_rt_result_t *results) {
+    RtPlan plan;
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const unc_rt_chunk_t &c = chunks[i];
+        const uint32_t first = (c.flags & UNC_RT_FIRST) ? 1u : 0u;
         RtHostChan &hc = rt->chans[c.channel];
-        if (c.flags & UNC_RT_FIRST) {
-            hc.state = 1; hc.number = c.read_number; hc.chunk_count = 1; hc.raw_len = c.n_samples;   // ReadBuffer(Chunk&)
-        } else if (hc.state != 1 || hc.number != c.read_number) {
-            results[i].state = UNC_RT_IGNORED;
-            continue;
-        } else if (hc.chunk_count >= rt->P.max_chunks) {
-            // Mapper::add_chunk: read_.chunks_maxed() -> set_failed(), mapper.cpp:289-296 (the chunk is dropped)
-            results[i].state = UNC_RT_FAILED;
-            hc.state = 0;
-            active.push_back(i | 0x80000000u);   // needs the slot state for the record, nothing to launch
-            continue;
-        } else {
-            hc.chunk_count++;
-            hc.raw_len += c.n_samples;
-        }
-        RtChunkDesc d;
-        d.offset = c.offset; d.n_samples = c.n_samples; d.channel = c.channel; d.new_read = (c.flags & UNC_RT_FIRST) ? 1u : 0u;
-        d.cal_range = c.calib.range; d.cal_offset = c.calib.offset; d.cal_digit = c.calib.digitisation;
-        desc.push_back(d);
-        slotmap.push_back(c.channel);
-        newread.push_back(d.new_read);
-        moff.push_back((uint64_t)c.channel * NORM_LEN);
-        active.push_back(i);
-        if (c.n_samples) { lo = c.offset < lo ? c.offset : lo; hi = c.offset + c.n_samples > hi ? c.offset + c.n_samples : hi; }
+        memset(&results[i], 0, sizeof results[i]);
+        results[i].hit.rid = -1;
+        if (!first && (hc.state != 1 || hc.number != c.read_number)) { results[i].state = UNC_RT_IGNORED; continue; }
+        // Mapper::add_chunk: read_.chunks_maxed() -> set_failed(), mapper.cpp:289-296 (the chunk is dropped).  Every read that rt_outcome
+        // leaves mapping has chunks to go: this is a read whose last call was admitted and then died on the device (UNC_ERR_HIP)
+        if (!first && hc.chunk_count >= rt->P.max_chunks) { plan.dropped.push_back(i); continue; }
+        if (first) hc = RtHostChan{1, c.read_number, 1, c.n_samples};        // ReadBuffer(Chunk&)
+        else { hc.chunk_count++; hc.raw_len += c.n_samples; }
+        plan.desc.push_back(RtChunkDesc{c.offset, c.n_samples, c.channel, first, c.calib.range, c.calib.offset, c.calib.digitisation});
+        plan.slotmap.push_back(c.channel); plan.newread.push_back(first);
+        plan.moff.push_back((uint64_t)c.channel * NORM_LEN); plan.launched.push_back(i);
+        if (c.n_samples) { plan.lo = std::min(plan.lo, c.offset); plan.hi = std::max(plan.hi, c.offset + c.n_samples); }
     }
-    const uint32_t n_act = (uint32_t)desc.size();
-    rt->ms_events = rt->ms_map = 0;
-    if (n_act) {
-        const char *d_base = raw_pa ? reinterpret_cast<const char *>(raw_pa) : reinterpret_cast<const char *>(raw);
-        if (!on_device) {
-            const uint64_t span = hi > lo ? hi - lo : 0;
-            HIPCHK(rt->d_raw.reserve(span * 2, 64));
-            if (span) HIPCHK(hipMemcpyAsync(rt->d_raw.p, d_base + lo * esz, span * esz, hipMemcpyHostToDevice, st));
-            d_base = reinterpret_cast<const char *>(rt->d_raw.p) - lo * esz;
-        }
-        const int16_t *d_raw = raw_pa ? nullptr : reinterpret_cast<const int16_t *>(d_base);
-        const float *d_pa = raw_pa ? reinterpret_cast<const float *>(d_base) : nullptr;
-        moff.push_back(0);
-        HIPCHK(hipMemcpyAsync(rt->d_desc.p, desc.data(), n_act * sizeof(RtChunkDesc), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(rt->d_slotmap.p, slotmap.data(), n_act * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(rt->d_newread.p, newread.data(), n_act * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(rt->d_moff.p, moff.data(), (n_act + 1) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(rt->ev[0], st));
-        launch_rt_events(d_raw, d_pa, rt->d_desc.p, n_act, rt->d_chans.p, rt->d_ring.p, rt->P, rt->ix->model_mean, rt->ix->model_stdv, rt->d_info.p,
-                         rt->d_ring0.p, st);
-        HIPCHK(hipEventRecord(rt->ev[1], st));
-        MapArgs a;
-        a.ix = rt->ix->dev; a.sc = rt->sc.v; a.P = rt->P; a.pool = rt->pool.v; a.results = rt->d_results.p; a.next_read = rt->d_next.p;
-        DevReads &rd = a.rd;
-        memset(&rd, 0, sizeof rd);
-        rd.means = rt->d_ring.p; rd.moff = rt->d_moff.p; rd.info = rt->d_info.p; rd.n_reads = n_act;
-        rd.tgt_mean = rt->ix->model_mean; rd.tgt_stdv = rt->ix->model_stdv;
-        rd.ring0 = rt->d_ring0.p; rd.new_read = rt->d_newread.p; rd.ring_mod = NORM_LEN;
-        a.resume = 1; a.slot_map = rt->d_slotmap.p;      // block b goes on with the read of channel slot_map[b], from the channel's ring
-        launch_map(a, n_act, st, rt->profile, rt->team);
-        HIPCHK(hipEventRecord(rt->ev[2], st));
-        HIPCHK(hipGetLastError());
-        rt->h_info.resize(n_act);
-        HIPCHK(hipMemcpyAsync(rt->h_info.data(), rt->d_info.p, n_act * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
+    plan.moff.push_back(0);
+    return plan;
+}
+
+// step 3: signal and metadata go up, the event kernel, k_map on teams, the event counts come back (queued).  raw (int16 + per-chunk
+// calibration) or raw_pa (floats taken as they are): exactly one of the two
+static int rt_launch(unc_rt *rt, const RtPlan &plan, const int16_t *raw, const float *raw_pa, int on_device, hipStream_t st) {
+    const uint32_t n = (uint32_t)plan.launched.size();
+    const size_t esz = raw_pa ? sizeof(float) : sizeof(int16_t);
+    const char *d_base = raw_pa ? reinterpret_cast<const char *>(raw_pa) : reinterpret_cast<const char *>(raw);
+    if (!on_device) {
+        const uint64_t span = plan.hi > plan.lo ? plan.hi - plan.lo : 0;
+        HIPCHK(rt->d_raw.reserve(span * 2, 64));
+        if (span) HIPCHK(hipMemcpyAsync(rt->d_raw.p, d_base + plan.lo * esz, span * esz, hipMemcpyHostToDevice, st));
+        d_base = reinterpret_cast<const char *>(rt->d_raw.p) - plan.lo * esz;
     }
+    const int16_t *d_raw = raw_pa ? nullptr : reinterpret_cast<const int16_t *>(d_base);
+    const float *d_pa = raw_pa ? reinterpret_cast<const float *>(d_base) : nullptr;
+    HIPCHK(hipMemcpyAsync(rt->d_desc.p, plan.desc.data(), n * sizeof(RtChunkDesc), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rt->d_slotmap.p, plan.slotmap.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rt->d_newread.p, plan.newread.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rt->d_moff.p, plan.moff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(rt->ev[0], st));
+    launch_rt_events(d_raw, d_pa, rt->d_desc.p, n, rt->d_chans.p, rt->d_ring.p, rt->P, rt->ix->model_mean, rt->ix->model_stdv, rt->d_info.p,
+                     rt->d_ring0.p, st);
+    HIPCHK(hipEventRecord(rt->ev[1], st));
+    MapArgs a = map_args(rt->ix, rt->P, rt->sc.v, rt->pool.v, rt_reads(rt, n), rt->d_results.p, rt->d_next.p);
+    a.resume = 1; a.slot_map = rt->d_slotmap.p;      // block b goes on with the read of channel slot_map[b], from the channel's ring
+    launch_map(a, n, st, rt->profile, rt->team);
+    HIPCHK(hipEventRecord(rt->ev[2], st));
+    HIPCHK(hipGetLastError());
+    rt->h_info.resize(n);
+    HIPCHK(hipMemcpyAsync(rt->h_info.data(), rt->d_info.p, n * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
+    return UNC_OK;
+}
+
+// step 4: every channel's slot state on the host, the device done, the kernels' times
+static int rt_collect(unc_rt *rt, bool launched, hipStream_t st) {
     rt->h_state.resize(rt->n_channels);
     HIPCHK(hipMemcpy2DAsync(rt->h_state.data(), sizeof(SlotState), rt->sc.v.base + rt->sc.v.off_state, rt->sc.v.slot_bytes, sizeof(SlotState), rt->n_channels,
                              hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (n_act) {
+    rt->ms_events = rt->ms_map = 0;
+    if (launched) {
         HIPCHK(hipEventElapsedTime(&rt->ms_events, rt->ev[0], rt->ev[1]));
         HIPCHK(hipEventElapsedTime(&rt->ms_map, rt->ev[1], rt->ev[2]));
     }
-
-    // ---- outcome per chunk (Mapper::map_chunk's exits, mapper.cpp:381-431)
-    int worst = UNC_OK;
-    uint32_t di = 0;
-    for (uint32_t a : active) {
-        const bool dropped = a & 0x80000000u;
-        const uint32_t i = a & 0x7FFFFFFFu;
-        const unc_rt_chunk_t &c = chunks[i];
-        RtHostChan &hc = rt->chans[c.channel];
-        const SlotState &s = rt->h_state[c.channel];
-        if (dropped) { rt_unmapped(rt, hc, s, nullptr, &results[i].hit); continue; }
-        const unc_evt_info_t &inf = rt->h_info[di++];
-        if (inf.pad || s.status) {   // RtChan status travels in info.pad
-            results[i].state = UNC_RT_FAILED;
-            rt_unmapped(rt, hc, s, &inf, &results[i].hit);
-            results[i].hit.status = s.status | inf.pad;
-            hc.state = 0;
-            worst = UNC_ERR_OVERFLOW;
-        } else if (s.done == 1) {
-            DevResult res;
-            memset(&res, 0, sizeof res);
-            res.done = 1; res.event_i = s.event_i; res.cluster = s.max_map; res.n_nbr = s.n_nbr; res.n_sa = s.n_sa; res.n_lf = s.n_lf;
-            res.notes = rt_notes(s, true);
-            fill_hit(rt->ix, rt->P, res, inf, hc.raw_len, &results[i].hit);
-            results[i].state = UNC_RT_MAPPED;
-            hc.state = 0;
-        } else if (s.done == 2 || s.event_i >= rt->P.max_events) {
-            results[i].state = UNC_RT_FAILED; results[i].ended = 1;        // event_i_ >= max_events: set_failed + set_ended
-            rt_unmapped(rt, hc, s, &inf, &results[i].hit);
-            hc.state = 0;
-        } else if (hc.chunk_count >= rt->P.max_chunks) {
-            results[i].state = UNC_RT_FAILED;                               // norm_.empty() && chunks_maxed(), :392-405
-            rt_unmapped(rt, hc, s, &inf, &results[i].hit);
-            hc.state = 0;
-        } else if (c.flags & UNC_RT_LAST) {
-            results[i].state = UNC_RT_FAILED; results[i].ended = 1;        // request_reset -> set_failed + set_ended
-            rt_unmapped(rt, hc, s, &inf, &results[i].hit);
-            hc.state = 0;
-        } else {
-            results[i].state = UNC_RT_MAPPING;
-            rt_unmapped(rt, hc, s, &inf, &results[i].hit, false);           // progress so far (event_i, counters)
-        }
-        if (rt->profile && hc.state == 0) for (int k = 0; k < 12; ++k) rt->cyc_sum[k] += s.cyc[k];
-    }
-    if (worst) return fail(worst, "device scratch overflow on at least one channel (see hit.status)");
     return UNC_OK;
 }
 
-extern "C" int unc_rt_process_chunks(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, const int16_t *raw, int on_device,
-                                     void *stream, unc_rt_result_t *results) {
-    if (!raw) return fail(UNC_ERR_ARG, "null argument");
-    return rt_process(rt, n_chunks, chunks, raw, nullptr, on_device, stream, results);
+// step 5: what a mapped chunk means for its read -- Mapper::map_chunk's exits (mapper.cpp:381-431), tested in this order
+struct RtOutcome { int32_t state, ended; bool finished; };      // finished: the channel's read is over, by whoever's decision
+static RtOutcome rt_outcome(const unc_evt_info_t &inf, const SlotState &s, const RtHostChan &hc, uint32_t chunk_flags, const unc_params_t &P) {
+    if (inf.pad || s.status) return {UNC_RT_FAILED, 0, true};                             // a scratch overflow (RtChan status travels in info.pad)
+    if (s.done == 1) return {UNC_RT_MAPPED, 0, true};
+    if (s.done == 2 || s.event_i >= P.max_events) return {UNC_RT_FAILED, 1, true};      // event_i_ >= max_events: set_failed + set_ended
+    // norm_.empty() && chunks_maxed(), :392-405.  This is also where the reference's Mapper::add_chunk would refuse the NEXT chunk
+    // (chunks_maxed() -> set_failed(), mapper.cpp:289-296): a call maps each chunk completely, so the read fails here, one call earlier
+    if (hc.chunk_count >= P.max_chunks) return {UNC_RT_FAILED, 0, true};
+    if (chunk_flags & UNC_RT_LAST) return {UNC_RT_FAILED, 1, true};                       // request_reset -> set_failed + set_ended
+    return {UNC_RT_MAPPING, 0, false};
 }
 
-extern "C" int unc_rt_process_chunks_f32(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, const float *signal, int on_device,
-                                         void *stream, unc_rt_result_t *results) {
-    if (!signal) return fail(UNC_ERR_ARG, "null argument");
-    return rt_process(rt, n_chunks, chunks, nullptr, signal, on_device, stream, results);
+static int rt_report(unc_rt *rt, const RtPlan &plan, const unc_rt_chunk_t *chunks, unc_rt_result_t *results) {
+    bool overflow = false;
+    for (size_t b = 0; b < plan.launched.size(); ++b) {
+        const uint32_t i = plan.launched[b];
+        RtHostChan &hc = rt->chans[chunks[i].channel];
+        const SlotState &s = rt->h_state[chunks[i].channel];
+        const unc_evt_info_t &inf = rt->h_info[b];
+        const RtOutcome o = rt_outcome(inf, s, hc, chunks[i].flags, rt->P);
+        results[i].state = o.state; results[i].ended = o.ended;
+        rt_hit(rt, hc, s, &inf, o.state == UNC_RT_MAPPED, o.finished, &results[i].hit);
+        overflow |= results[i].hit.status != 0;
+        if (o.finished) hc.state = 0;
+        if (o.finished && rt->profile) for (int k = 0; k < 12; ++k) rt->cyc_sum[k] += s.cyc[k];
+    }
+    for (uint32_t i : plan.dropped) {
+        RtHostChan &hc = rt->chans[chunks[i].channel];
+        results[i].state = UNC_RT_FAILED;
+        rt_hit(rt, hc, rt->h_state[chunks[i].channel], nullptr, false, true, &results[i].hit);
+        hc.state = 0;
+    }
+    if (overflow) return fail(UNC_ERR_OVERFLOW, "device scratch overflow on at least one channel (see hit.status)");
+    return UNC_OK;
 }
+
+static int rt_process(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, const int16_t *raw, const float *raw_pa, int on_device,
+                      void *stream, unc_rt_result_t *results) {
+    int rc = rt_check(rt, n_chunks, chunks, raw ? (const void *)raw : (const void *)raw_pa, results);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(rt->ix->device));
+    hipStream_t st = stream ? (hipStream_t)stream : rt->stream;
+    const RtPlan plan = rt_admit(rt, n_chunks, chunks, results);
+    if (!plan.launched.empty() && (rc = rt_launch(rt, plan, raw, raw_pa, on_device, st)) != UNC_OK) return rc;
+    if ((rc = rt_collect(rt, !plan.launched.empty(), st)) != UNC_OK) return rc;
+    return rt_report(rt, plan, chunks, results);
+}
+
+extern "C" int unc_rt_process_chunks(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, const int16_t *raw, int on_device,
+                                     void *stream, unc_rt_result_t *results) { return rt_process(rt, n_chunks, chunks, raw, nullptr, on_device, stream, results); }
+extern "C" int unc_rt_process_chunks_f32(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chunks, const float *signal, int on_device,
+                                         void *stream, unc_rt_result_t *results) { return rt_process(rt, n_chunks, chunks, nullptr, signal, on_device, stream, results); }
 
 // ------------------------------------------------------------------ uncalled index: self alignment
 extern "C" int unc_self_align(const unc_index_t *ix, const char *bwa_prefix, uint32_t sample_dist, uint32_t cap, uint64_t *lens,
