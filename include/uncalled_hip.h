@@ -471,6 +471,43 @@ int unc_align_last_timing(float *ms4);
  * UNC_ALIGN_TARGET_MODEL */
 void unc_align_model_target(float *mean, float *stdv);
 
+/* ---- the packed reference on the device: replaces BwaIndex::load_pacseq (bwa_index.hpp: bns_restore's .pac read into pacseq_, once) and
+ * BwaIndex::get_kmers (bwa_index.hpp:247-255) for a batch of stretches.  unc_refseq_load reads <prefix>.pac once, keeps it on the host
+ * and uploads it to the device of `ix`: the file's base bytes, followed by zeroed padding so that a kernel reading whole aligned words
+ * around any stretch stays inside the allocation.  The file must be what bwa writes for the index: l_pac = unc_index_size(ix) / 2
+ * bases, l_pac / 4 + 2 bytes, the last of them l_pac % 4; anything else is UNC_ERR_IO with the file's name.  The offsets of the
+ * sequences in the packed text (bntann1_t::offset) are computed here, once.  The object is immutable after load: calls on it from
+ * several threads at once are allowed.  It must be freed BEFORE the index it was loaded for. */
+typedef struct unc_refseq unc_refseq_t;
+/* BwaIndex::load_pacseq, bwa_index.hpp */
+int unc_refseq_load(const unc_index_t *ix, const char *bwa_prefix, unc_refseq_t **out);
+void unc_refseq_free(unc_refseq_t *rs);
+uint64_t unc_refseq_device_bytes(const unc_refseq_t *rs);
+/* bases [st, en) of sequence rid; fwd == 0: the minus strand (kmers_revcomp, bp.hpp:82-99) */
+typedef struct { int32_t rid; uint32_t fwd; uint64_t st, en; } unc_ref_stretch_t;
+/* BwaIndex::get_kmers (bwa_index.hpp:247-255) = seq_to_kmers (bp.hpp:125-146) and kmers_revcomp (bp.hpp:82-99) on the device, for n
+ * stretches in one launch of k_ref_kmers: what unc_ref_kmers gives for each.  The n_a = en - st - 4 k-mers of stretch a (0 below five
+ * bases: legal, nothing is written) go to out[out_off[a] .. out_off[a] + n_a); out_off (n + 1, ascending) must leave room; out is
+ * host memory, and nothing outside the counts is written.  UNC_ERR_ARG before the device is touched, and with `out` untouched, for a
+ * rid out of range, st > en, en past the sequence, room smaller than the count, descending offsets.  n == 0: UNC_OK. */
+int unc_refseq_kmers_batch(const unc_refseq_t *rs, uint32_t n, const unc_ref_stretch_t *stretches, uint16_t *out,
+                           const uint64_t *out_off, void *stream);
+/* unc_align_batch with coordinates in place of k-mer arrays (dtw_test.cpp:94-105: get_kmers per query, here for the batch on the
+ * device): query q's rows are the k-mers of stretches[q], made by k_ref_kmers on the stream ahead of the other stages; they reach the
+ * host only when kmers_out is given (may be NULL; then query q's go to kmers_out[kmers_off[q] ..], and kmers_off, n_queries + 1 and
+ * ascending, must leave room for them).  The device is the index's.  Every other argument as in unc_align_batch, and for the same
+ * reads, queries and options every result, level, path and status equals, bit for bit, what unc_align_batch gives when fed
+ * unc_ref_kmers' output for the same stretches.  UNC_ERR_ARG before the device is touched for what unc_align_batch refuses, for a
+ * stretch that unc_refseq_kmers_batch refuses, and for a stretch of fewer than five bases (the query has no k-mers). */
+int unc_align_ref_batch(const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
+                        const int16_t *raw, const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
+                        const unc_align_query_t *queries, const unc_ref_stretch_t *stretches, uint64_t workspace_bytes,
+                        unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint16_t *kmers_out,
+                        const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off, void *stream);
+/* kernel milliseconds of k_ref_kmers in the calling thread's last unc_align_ref_batch (HIP events on the stream);
+ * unc_align_last_timing keeps its four spans */
+int unc_align_ref_last_timing(float *ms_kmers);
+
 /* ---- measurement aid: `reps` launches that write, then `reps` that read, n_records (made odd) scattered 64-byte records with
  * one lane per record and four 16-byte accesses per lane -- k_map's access shape with an exactly known byte count, for
  * calibrating the HBM traffic counters of rocprofv3 (tools/dev/pmc_calib.py, profiles/r02_pmc_k_map.json) */

@@ -339,6 +339,39 @@ def load_dtw_queries(fname):
     return queries
 
 
+def load_paf_queries(fname):
+    """The queries of `dtw --paf`: one per mapped PAF line (read id column 1, strand column 5, reference name column 6, stretch
+    [column 8, column 9)); a later line for the same read replaces the earlier one.  Unmapped lines (`*` in column 6) are skipped
+    silently, a line whose stretch has fewer than five bases (no k-mer) with a word on stderr.  PAF read coordinates are bases at
+    bp_per_sec / sample_rate = 450 / 4000 a sample: smp_st = column 3 * 80 // 9, smp_en = column 4 * 80 / 9 rounded up (clip_paf_queries
+    cuts it to the read's samples once they are known)."""
+    queries = {}
+    with open(fname) as fh:
+        for no, line in enumerate(fh, 1):
+            f = line.rstrip("\n").split("\t")
+            if not f or not f[0] or f[0].startswith("#"):
+                continue
+            if len(f) >= 6 and f[5] == "*":
+                continue
+            if len(f) < 9 or f[4] not in ("+", "-"):
+                sys.stderr.write("Error: %s:%d: expected a PAF line of at least nine columns\n" % (fname, no))
+                sys.exit(1)
+            ref_st, ref_en = int(f[7]), int(f[8])
+            if ref_en - ref_st < 5:
+                sys.stderr.write("Skipping %s: %s:%d: a stretch of fewer than five bases has no k-mer\n" % (f[0], fname, no))
+                continue
+            queries[f[0]] = dict(smp_st=int(f[2]) * 80 // 9, smp_en=-(-int(f[3]) * 80 // 9), ref=f[5], ref_st=ref_st, ref_en=ref_en,
+                                 fwd=f[4] == "+")
+    return queries
+
+
+def clip_paf_queries(queries, reads):
+    """smp_en = min(read length in samples, what the PAF's column 4 gives)"""
+    for rid, samples, _ in reads:
+        q = queries[rid]
+        q["smp_en"] = min(len(samples), q["smp_en"])
+
+
 KMER_BASES = "ACGT"
 
 
@@ -348,16 +381,19 @@ def kmer_str(k, klen=5):
 
 def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False, band=0):
     """The batches behind `dtw`: reads = [(id, int16 samples, (range, offset, digitisation))], queries as load_dtw_queries gives
-    them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels or None, path or None), in the order of `reads`."""
+    them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels, path: the last three None without want_paths), in the
+    order of `reads`.  The rows of every alignment are made on the device from the queries' coordinates (capi.align_ref_batch); `device`
+    is the index's."""
     import numpy as np
     from . import capi
     names = index.seq_names()
+    refseq = capi.RefSeq(index, prefix)         # the packed reference: read and uploaded once per run
     for b0 in range(0, len(reads), batch):
         part = reads[b0:b0 + batch]
         raw = np.concatenate([np.asarray(r[1], np.int16) for r in part]) if part else np.zeros(0, np.int16)
         offsets = np.cumsum([0] + [len(r[1]) for r in part]).astype(np.uint64)
         calib = capi.make_calib(len(part), 0, 0, 1)
-        qs, kms = [], []
+        qs, stretches = [], []
         for i, (rid, _, cal) in enumerate(part):
             calib[i] = cal
             q = queries[rid]
@@ -365,12 +401,12 @@ def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, devic
                 sys.stderr.write("Error: no sequence '%s' in the index\n" % q["ref"])
                 sys.exit(1)
             qs.append((i, q["smp_st"], q["smp_en"]))
-            kms.append(capi.ref_kmers(index, prefix, names.index(q["ref"]), q["ref_st"], q["ref_en"], q["fwd"]))
+            stretches.append((names.index(q["ref"]), q["ref_st"], q["ref_en"], q["fwd"]))
         t0 = time.time()
-        out = capi.align_batch(raw, offsets, calib, qs, kms, opts=capi.align_opts(max_events=max_events, band=band), levels=want_paths,
-                               paths=want_paths, device=device)
+        out = capi.align_ref_batch(refseq, raw, offsets, calib, qs, stretches, opts=capi.align_opts(max_events=max_events, band=band),
+                                   levels=want_paths, paths=want_paths, kmers=want_paths)
         sec = (time.time() - t0) / max(1, len(part))
-        res, levs, paths = out if want_paths else (out, [None] * len(part), [None] * len(part))
+        res, levs, paths, kms = out if want_paths else (out, [None] * len(part), [None] * len(part), [None] * len(part))
         for i, (rid, _, _) in enumerate(part):
             yield rid, res[i], sec, kms[i], levs[i], paths[i]
 
@@ -383,7 +419,7 @@ def dtw_cmd(args):
     _assert_exists(args.index_prefix + ".pac")
     _assert_exists(args.fast5)
     _assert_exists(args.queries)
-    queries = load_dtw_queries(args.queries)
+    queries = load_paf_queries(args.queries) if args.paf else load_dtw_queries(args.queries)
     reader = unc.Fast5Reader("", "", 0, max(100, len(queries)))
     reader.add_fast5(os.path.abspath(args.fast5))
     for rid in queries:
@@ -393,6 +429,8 @@ def dtw_cmd(args):
         r = reader.pop_read()
         if r.id in queries:
             reads.append((r.id, r.raw_i16, r.calibration))
+    if args.paf:
+        clip_paf_queries(queries, reads)
     index = capi.Index(args.index_prefix, device=args.device)
     for rid, r, sec, km, lev, path in dtw_align(index, args.index_prefix, reads, queries, max_events=args.max_events, batch=args.batch_queries,
                                                 device=args.device, want_paths=args.out_prefix is not None, band=args.band):
@@ -484,7 +522,13 @@ def get_parser():
                       "read past both; that is not reproduced.)")
     p.add_argument("index_prefix", type=str, help="BWA prefix of the reference (needs the .pac)")
     p.add_argument("fast5", type=str, help="fast5 file that holds the reads")
-    p.add_argument("queries", type=str, help="Query file, one line per read")
+    p.add_argument("queries", type=str, help="Query file, one line per read (with --paf: a PAF file)")
+    p.add_argument("--paf", action="store_true", help="QUERIES is a PAF file, such as `map` writes: one alignment per mapped line, of the read in "
+                   "column 1 on the strand of column 5 against bases [column 8, column 9) of the sequence named in column 6. The sample range "
+                   "comes from the read coordinates, which are bases at 450 / 4000 a sample: smp_st = column 3 * 80 // 9, smp_en = column 4 * 80 / 9 "
+                   "rounded up, at most the read's samples. Unmapped lines (`*` in column 6) are skipped silently, a line whose stretch has "
+                   "fewer than five bases is reported on stderr and skipped; of several lines for one read the last one counts. May be "
+                   "combined with --band or not")
     p.add_argument("-o", "--out-prefix", type=str, default=None, help="Write the path of read ID to OUT_PREFIX + ID + .txt")
     p.add_argument("--max-events", type=int, default=50000, help="Skip reads with more events than this (the reference's 50000; 0: no limit -- "
                    "2 bits per cell make alignments affordable here that the reference skips)")

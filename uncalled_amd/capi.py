@@ -146,6 +146,7 @@ ALIGN_QUERY = np.dtype([("read", "<u4"), ("pad", "<u4"), ("smp_st", "<u8"), ("sm
 ALIGN_RESULT = np.dtype([("dtw", DTW_RESULT), ("n_events", "<u4"), ("n_kept", "<u4"), ("tgt_mean", "<f4"), ("tgt_stdv", "<f4"),
                          ("scale", "<f4"), ("shift", "<f4"), ("status", "<u4"), ("pad", "<u4")])
 
+REF_STRETCH = np.dtype([("rid", "<i4"), ("fwd", "<u4"), ("st", "<u8"), ("en", "<u8")])      # unc_ref_stretch_t
 _libs = {}
 
 
@@ -247,6 +248,14 @@ def load(path=None):
         L.unc_align_last_timing.argtypes = [vp]
         L.unc_align_model_target.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.unc_align_model_target.restype = None
+    if hasattr(L, "unc_refseq_load"):
+        L.unc_refseq_load.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
+        L.unc_refseq_free.argtypes = [vp]; L.unc_refseq_free.restype = None
+        L.unc_refseq_device_bytes.argtypes = [vp]; L.unc_refseq_device_bytes.restype = u64
+        L.unc_refseq_kmers_batch.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.unc_align_ref_batch.argtypes = [vp, C.POINTER(Params), C.POINTER(AlignOpts), u32, vp, vp, vp, C.c_int, u32, vp, vp, u64, vp,
+                                          vp, vp, vp, vp, vp, vp, vp]
+        L.unc_align_ref_last_timing.argtypes = [C.POINTER(C.c_float)]
     _libs[key] = L
     return L
 
@@ -492,6 +501,113 @@ def ref_kmers(index, prefix, rid, st, en, fwd=True):
     if n.value:
         _check(L, L.unc_ref_kmers(index.h, str(prefix).encode(), int(rid), int(st), int(en), 1 if fwd else 0, out.ctypes.data, out.size, C.byref(n)))
     return out
+
+
+class RefSeq:
+    """unc_refseq_t: the packed reference <prefix>.pac, read once, kept on the host and in HBM beside the index
+    (BwaIndex::load_pacseq).  Close it before the index it was loaded for (it keeps a reference to the index, so garbage collection
+    takes them in that order)."""
+
+    def __init__(self, index, prefix):
+        self.index = index
+        self.L = index.L
+        h = C.c_void_p()
+        _check(self.L, self.L.unc_refseq_load(index.h, str(prefix).encode(), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.unc_refseq_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def device_bytes(self):
+        return self.L.unc_refseq_device_bytes(self.h)
+
+
+def _stretches(stretches):
+    """(rid, st, en, fwd) tuples -> REF_STRETCH records"""
+    out = np.zeros(len(stretches), dtype=REF_STRETCH)
+    for i, (rid, st, en, fwd) in enumerate(stretches):
+        out[i]["rid"], out[i]["st"], out[i]["en"], out[i]["fwd"] = rid, st, en, 1 if fwd else 0
+    return out
+
+
+def ref_kmers_batch(refseq, stretches, stream=None):
+    """unc_refseq_kmers_batch: BwaIndex::get_kmers for a batch of (rid, st, en, fwd) stretches in one kernel launch on the GPU
+    -> a list of uint16 arrays, what ref_kmers gives for each (empty below five bases)."""
+    L = refseq.L
+    ss = _stretches(stretches)
+    counts = [max(0, int(en) - int(st) - 4) for _, st, en, _ in stretches]
+    off = np.cumsum([0] + counts).astype(np.uint64)
+    out = np.empty(max(1, int(off[-1])), dtype=np.uint16)
+    _check(L, L.unc_refseq_kmers_batch(refseq.h, len(stretches), ss.ctypes.data, out.ctypes.data, off.ctypes.data, stream))
+    return [out[int(off[a]):int(off[a + 1])].copy() for a in range(len(stretches))]
+
+
+def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
+                    kmers=False, on_device=False, stream=None):
+    """unc_align_ref_batch: align_batch with coordinates in place of k-mer arrays.  stretches[q] = (rid, st, en, fwd) names the bases
+    whose k-mers are query q's rows; they are made on the GPU (the index's) and reach the host only with kmers=True.  Everything else
+    as align_batch, and so are the results, bit for bit, for the k-mers ref_kmers gives for the same stretches.  -> ALIGN_RESULT
+    records, then, as asked for, the lists of levels, of paths and of k-mers per query."""
+    L = refseq.L
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    calib = np.ascontiguousarray(calib, dtype=CALIB)
+    n_reads, n = offsets.size - 1, len(queries)
+    if n != len(stretches):
+        raise ValueError("as many stretches as queries are needed")
+    qs = np.zeros(n, dtype=ALIGN_QUERY)
+    for i, (r, st, en) in enumerate(queries):
+        qs[i]["read"], qs[i]["smp_st"], qs[i]["smp_en"] = r, st, en
+    ss = _stretches(stretches)
+    counts = [max(0, int(en) - int(st) - 4) for _, st, en, _ in stretches]
+    if on_device:
+        raw_ptr = int(raw)
+    else:
+        raw = np.ascontiguousarray(raw, dtype=np.int16)
+        raw_ptr = raw.ctypes.data
+    res = np.zeros(n, dtype=ALIGN_RESULT)
+    room = []       # (as in align_batch)
+    for r, st, en in queries:
+        ln = int(offsets[r + 1] - offsets[r]) if 0 <= r < n_reads else 0
+        ns = max(0, (int(en) if en else ln) - int(st))
+        room.append(ns if opts is not None and opts.flags & ALIGN_RAW else ns // 2 + 16)
+    lev = lev_off = path = path_off = km = km_off = None
+    if levels:
+        lev_off = np.cumsum([0] + room).astype(np.uint64)
+        lev = np.empty(max(1, int(lev_off[-1])), dtype=np.float32)
+    if paths:
+        path_off = np.cumsum([0] + [max(0, c + k - 1) for c, k in zip(room, counts)]).astype(np.uint64)
+        path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
+    if kmers:
+        km_off = np.cumsum([0] + counts).astype(np.uint64)
+        km = np.empty(max(1, int(km_off[-1])), dtype=np.uint16)
+    _check(L, L.unc_align_ref_batch(refseq.h, C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
+                                    n_reads, raw_ptr, offsets.ctypes.data, calib.ctypes.data, 1 if on_device else 0, n, qs.ctypes.data,
+                                    ss.ctypes.data, int(workspace_bytes), res.ctypes.data,
+                                    lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None,
+                                    km.ctypes.data if kmers else None, km_off.ctypes.data if kmers else None,
+                                    path.ctypes.data if paths else None, path_off.ctypes.data if paths else None, stream))
+    out = [res]
+    if levels:
+        out.append([lev[int(lev_off[q]):int(lev_off[q]) + int(res["n_kept"][q])].copy() for q in range(n)])
+    if paths:
+        done = (DTW_OK, DTW_PATH_TRUNCATED, DTW_LEFT_BAND)
+        out.append([path[int(path_off[q]):int(path_off[q]) + int(res["dtw"]["path_len"][q])].copy() if res["status"][q] in done else None
+                    for q in range(n)])
+    if kmers:
+        out.append([km[int(km_off[q]):int(km_off[q + 1])].copy() for q in range(n)])
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def align_ref_last_timing(lib=None):
+    """kernel milliseconds of k_ref_kmers in the calling thread's last align_ref_batch"""
+    L = lib or load()
+    ms = C.c_float()
+    L.unc_align_ref_last_timing(C.byref(ms))
+    return ms.value
 
 
 def make_calib(n, rng, offset, digitisation):

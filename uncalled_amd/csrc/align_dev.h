@@ -42,4 +42,22 @@ struct AlignPrep {
 // calibrated samples themselves, query q from col_off on
 void launch_align_gather(const int16_t *raw, const AlignQuery *queries, uint32_t n_queries, int16_t *gathered, float *calibrated, hipStream_t st);
 void launch_align_prep(const AlignPrep &p, hipStream_t st);
+
+// Where the rows of a batch's queries come from.  align_run (unc_align.cpp) is the one pipeline; its callers differ in this alone:
+// unc_align_batch uploads the caller's k-mers, unc_align_ref_batch (unc_refseq.cpp) has k_ref_kmers make them from coordinates.
+struct AlignRows {
+    virtual ~AlignRows() = default;
+    // among the checks of query q, in their order: fails with a message, or says where the query's rows lie on the device (in
+    // elements from the start of the array that queue() returns) and how many they are
+    virtual int rows(uint32_t q, uint64_t *at, uint32_t *n) = 0;
+    // after every query's checks, the last thing before the device is touched: whatever is checked over the batch as a whole
+    virtual int check() = 0;
+    // on the device: allocates the array and queues on `st` whatever fills it.  The array lives as long as the object
+    virtual int queue(hipStream_t st, const uint16_t **d_kmers) = 0;
+};
+// who: the entry point's name, for the messages
+int align_run(const char *who, int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
+              const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries, const unc_align_query_t *queries,
+              AlignRows &rows, uint64_t workspace_bytes, unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path,
+              const uint64_t *path_off, void *stream);
 }  // namespace unc

@@ -166,3 +166,7 @@ void launch_align_prep(const AlignPrep &p, hipStream_t st) {
 }
 
 }  // namespace unc
+
+// k_ref_kmers, which makes a batch's rows from the packed reference, is compiled as part of this translation unit, so that every
+// build of the alignment sources holds it
+#include "k_refseq.hip"

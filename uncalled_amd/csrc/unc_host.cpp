@@ -397,6 +397,7 @@ extern "C" uint64_t unc_index_seq_len(const unc_index_t *ix, int32_t rid) {
     return (rid >= 0 && (size_t)rid < ix->seqs.size()) ? ix->seqs[rid].len : 0;
 }
 extern "C" uint64_t unc_index_device_bytes(const unc_index_t *ix) { return ix->device_bytes; }
+int unc::index_device(const unc_index_t *ix) { return ix->device; }
 
 // bns_pos2rid behind BwaIndex::translate_loc, bwa_index.hpp:213-220
 extern "C" uint64_t unc_index_translate_loc(const unc_index_t *ix, uint64_t sa_loc, int32_t *rid, uint64_t *ref_loc) {

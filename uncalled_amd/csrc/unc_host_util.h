@@ -9,6 +9,8 @@
 namespace unc {
 // stores the message unc_last_error() returns to the calling thread and returns `code` (defined in unc_host.cpp)
 int fail(int code, const char *fmt, ...);
+// the HIP device an index was loaded to (defined in unc_host.cpp, which owns the struct)
+int index_device(const unc_index_t *ix);
 }  // namespace unc
 
 #define HIPCHK(expr)                                                                                         \
