@@ -508,6 +508,64 @@ int unc_align_ref_batch(const unc_refseq_t *rs, const unc_params_t *params, cons
  * unc_align_last_timing keeps its four spans */
 int unc_align_ref_last_timing(float *ms_kmers);
 
+/* ---- alignments in sample coordinates: what a caller of the reference's dtw_test (src/dtw_test.cpp:162-176 prints DTW::get_path() and
+ * stops) still has to work out by hand -- which samples of the read belong to which reference k-mer.  The path is pairs (column,
+ * row); a column is an event that survived the detector's min_mean / max_mean test (event_detector.cpp:107-108) and the stall mask
+ * (EventProfiler::get_full_mask, event_profiler.hpp:129-151).  The calls below keep every event's boundaries on the device and
+ * collapse the path there to one record per k-mer (row) on it. */
+/* Event (event_detector.hpp; create_event, event_detector.cpp:296-319): mean and stdv in pA, the event's first sample in the
+ * query's slice and its samples.  With UNC_ALIGN_RAW a column is a sample: start = its index, length 1, stdv 0, mean the sample. */
+typedef struct { float mean, stdv; uint32_t start, length; } unc_event_t;
+/* one k-mer (row) of an alignment's path, over the row's columns c in ascending order (m, d, l: mean, stdv, length of the column's
+ * event), all in double, one rounding per operation:  S += m * l;  Q += l * (d * d + m * m);  N += l;  M = S / N;
+ * mean = (float)M;  stdv = (float)sqrt(fmax(Q / N - M * M, 0)) */
+typedef struct {
+    uint64_t smp_st;            /* first sample of the row's first event, in the READ's samples: the query's smp_st + that event's start */
+    uint32_t smp_span;          /* from smp_st to the end of the row's last event; samples of events dropped in between are included */
+    uint32_t smp_n;             /* sum of the lengths of the row's events (<= smp_span) */
+    uint32_t col_first, n_cols; /* the row's columns on the path: [col_first, col_first + n_cols) */
+    float mean, stdv;           /* pA, over the row's events, as above */
+    float level;                /* Normalizer::at of mean (normalizer.cpp:114-118): scale * mean + shift, unfused, the query's scale and shift */
+    uint32_t shared;            /* 1: col_first is also the previous row's last column (a vertical move: several k-mers on one event) */
+} unc_segment_t;
+#define UNC_SEG_OK 0u
+#define UNC_SEG_TRUNCATED 1u    /* the caller's room is smaller than n_rows: the first records are written, as many as the room holds */
+#define UNC_SEG_NONE 2u         /* the query's status is neither UNC_DTW_OK nor UNC_DTW_PATH_TRUNCATED: no path, no records, n_rows 0 */
+/* the rows on a query's path are [row_first, row_first + n_rows) (DTW::get_path(), dtw.hpp:100-119: rows and columns fall by at
+ * most one per pair); record s is row row_first + s */
+typedef struct { uint32_t row_first, n_rows, status, pad; } unc_seg_info_t;
+/* all host memory.  seg (may be NULL) receives query q's records from seg[seg_off[q]] on, at most seg_off[q+1] - seg_off[q] of them
+ * (the query's k-mer count always suffices); info (may be NULL, n_queries) the rows and UNC_SEG_* (without seg the rows are counted
+ * all the same and the status is UNC_SEG_OK: no record is missing where none was asked for); events (may be NULL), the tap:
+ * query q's columns as events, in column order, from events[evt_off[q]] on, at most evt_off[q+1] - evt_off[q] (n_kept of the result
+ * says how many there are).  Offsets ascend; nothing outside a query's room is written. */
+typedef struct {
+    unc_segment_t *seg;
+    const uint64_t *seg_off;
+    unc_seg_info_t *info;
+    unc_event_t *events;
+    const uint64_t *evt_off;
+} unc_align_segments_t;
+/* unc_align_batch / unc_align_ref_batch with `out` filled as well (k_align_segments runs on every round's paths while they are on the
+ * device).  results, levels, path and the statuses -- UNC_DTW_PATH_TRUNCATED among them, which goes by the caller's room in path --
+ * are those of the call without `out`, bit for bit; the records do not depend on the room in path.  UNC_ERR_ARG before the device
+ * is touched, besides what those calls refuse: out NULL, seg without seg_off, events without evt_off, descending offsets. */
+int unc_align_segments_batch(int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
+                             const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
+                             const unc_align_query_t *queries, const uint16_t *kmers, const uint64_t *km_off, uint64_t workspace_bytes,
+                             unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path, const uint64_t *path_off,
+                             const unc_align_segments_t *out, void *stream);
+int unc_align_ref_segments_batch(const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
+                                 const int16_t *raw, const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
+                                 const unc_align_query_t *queries, const unc_ref_stretch_t *stretches, uint64_t workspace_bytes,
+                                 unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint16_t *kmers_out,
+                                 const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off, const unc_align_segments_t *out,
+                                 void *stream);
+/* kernel milliseconds of k_align_segments in the calling thread's last alignment call (HIP events on the stream, summed over the
+ * DTW's rounds; 0 for a call without segments); unc_align_last_timing keeps its four spans, of which [1] is then the event
+ * kernel's variant that writes whole Events (create_event, event_detector.cpp:296-319) */
+int unc_align_segments_last_timing(float *ms);
+
 /* ---- measurement aid: `reps` launches that write, then `reps` that read, n_records (made odd) scattered 64-byte records with
  * one lane per record and four 16-byte accesses per lane -- k_map's access shape with an exactly known byte count, for
  * calibrating the HBM traffic counters of rocprofv3 (tools/dev/pmc_calib.py, profiles/r02_pmc_k_map.json) */

@@ -379,11 +379,33 @@ def kmer_str(k, klen=5):
     return "".join(KMER_BASES[(int(k) >> (2 * (klen - 1 - i))) & 3] for i in range(klen))
 
 
-def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False, band=0):
+def segment_ref_pos(ref_st, ref_en, fwd, row, klen=5):
+    """forward-strand position of the first base of the k-mer that is row `row` of a query over bases [ref_st, ref_en).  The minus
+    strand's rows are the forward k-mers in reverse order, each reverse-complemented (kmers_revcomp, bp.hpp:82-99): row r is the
+    forward k-mer (count - 1 - r), whose first forward base is its own last base."""
+    n = ref_en - ref_st - (klen - 1)
+    return ref_st + row if fwd else ref_st + (n - 1 - row)
+
+
+SEGMENT_COLUMNS = ("ref_name", "ref_pos", "strand", "kmer", "smp_st", "smp_span", "smp_n", "n_cols", "shared", "mean", "stdv", "level", "model_mean")
+
+
+def write_segments(out, q, row_first, segs, km, model_means):
+    """one line per record: the k-mer as the query's strand reads it, at its forward-strand position"""
+    out.write("\t".join(SEGMENT_COLUMNS) + "\n")
+    for s, r in enumerate(segs):
+        row = row_first + s
+        out.write("%s\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%.6g\t%.6g\t%.6g\t%.6g\n" % (
+            q["ref"], segment_ref_pos(q["ref_st"], q["ref_en"], q["fwd"], row), "+" if q["fwd"] else "-", kmer_str(km[row]), int(r["smp_st"]),
+            int(r["smp_span"]), int(r["smp_n"]), int(r["n_cols"]), int(r["shared"]), float(r["mean"]), float(r["stdv"]), float(r["level"]),
+            float(model_means[km[row]])))
+
+
+def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False, band=0, segments=False):
     """The batches behind `dtw`: reads = [(id, int16 samples, (range, offset, digitisation))], queries as load_dtw_queries gives
-    them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels, path: the last three None without want_paths), in the
-    order of `reads`.  The rows of every alignment are made on the device from the queries' coordinates (capi.align_ref_batch); `device`
-    is the index's."""
+    them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels, path, SEGMENT records, SEG_INFO record), in the order of
+    `reads`: k-mers, levels and path are None without want_paths, the last two None without segments.  The rows of every alignment
+    are made on the device from the queries' coordinates (capi.align_ref_batch); `device` is the index's."""
     import numpy as np
     from . import capi
     names = index.seq_names()
@@ -404,11 +426,15 @@ def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, devic
             stretches.append((names.index(q["ref"]), q["ref_st"], q["ref_en"], q["fwd"]))
         t0 = time.time()
         out = capi.align_ref_batch(refseq, raw, offsets, calib, qs, stretches, opts=capi.align_opts(max_events=max_events, band=band),
-                                   levels=want_paths, paths=want_paths, kmers=want_paths)
+                                   levels=want_paths, paths=want_paths, kmers=want_paths, segments=segments)
         sec = (time.time() - t0) / max(1, len(part))
-        res, levs, paths, kms = out if want_paths else (out, [None] * len(part), [None] * len(part), [None] * len(part))
+        none = [None] * len(part)
+        out = list(out) if isinstance(out, tuple) else [out]         # results, then what was asked for, in this order
+        res = out.pop(0)
+        levs, paths, kms = (out.pop(0), out.pop(0), out.pop(0)) if want_paths else (none, none, none)
+        segs, infos = (out.pop(0), out.pop(0)) if segments else (none, none)
         for i, (rid, _, _) in enumerate(part):
-            yield rid, res[i], sec, kms[i], levs[i], paths[i]
+            yield rid, res[i], sec, kms[i], levs[i], paths[i], segs[i], infos[i]
 
 
 def dtw_cmd(args):
@@ -419,6 +445,9 @@ def dtw_cmd(args):
     _assert_exists(args.index_prefix + ".pac")
     _assert_exists(args.fast5)
     _assert_exists(args.queries)
+    if args.segments and args.out_prefix is None:
+        sys.stderr.write("Error: --segments needs -o\n")
+        sys.exit(1)
     queries = load_paf_queries(args.queries) if args.paf else load_dtw_queries(args.queries)
     reader = unc.Fast5Reader("", "", 0, max(100, len(queries)))
     reader.add_fast5(os.path.abspath(args.fast5))
@@ -432,8 +461,9 @@ def dtw_cmd(args):
     if args.paf:
         clip_paf_queries(queries, reads)
     index = capi.Index(args.index_prefix, device=args.device)
-    for rid, r, sec, km, lev, path in dtw_align(index, args.index_prefix, reads, queries, max_events=args.max_events, batch=args.batch_queries,
-                                                device=args.device, want_paths=args.out_prefix is not None, band=args.band):
+    for rid, r, sec, km, lev, path, segs, seg_info in dtw_align(index, args.index_prefix, reads, queries, max_events=args.max_events,
+                                                      batch=args.batch_queries, device=args.device, want_paths=args.out_prefix is not None,
+                                                      band=args.band, segments=args.segments):
         st = int(r["status"])
         if st == capi.ALIGN_TOO_MANY:
             sys.stderr.write("Skipping %s\n" % rid)            # dtw_test.cpp:156-159
@@ -450,6 +480,9 @@ def dtw_cmd(args):
             with open(args.out_prefix + rid + ".txt", "w") as out:
                 for j, i in path[::-1]:                          # from the start of the alignment to its end
                     out.write("%d\t%d\t%s\t%.6g\t%.6g\n" % (j, i, kmer_str(km[i]), lev[j], abs(float(lev[j]) - float(means[km[i]]))))
+            if args.segments and st == capi.DTW_OK:              # (a path that left the band has no start: no records)
+                with open(args.out_prefix + rid + ".segments.tsv", "w") as out:
+                    write_segments(out, queries[rid], int(seg_info["row_first"]), segs, km, means)
         sys.stdout.write("%s\t%.6g\t%.6g%s\n" % (rid, float(r["dtw"]["mean_score"]), sec, "\tstatus %d" % st if st else ""))
         sys.stdout.flush()
 
@@ -530,6 +563,11 @@ def get_parser():
                    "fewer than five bases is reported on stderr and skipped; of several lines for one read the last one counts. May be "
                    "combined with --band or not")
     p.add_argument("-o", "--out-prefix", type=str, default=None, help="Write the path of read ID to OUT_PREFIX + ID + .txt")
+    p.add_argument("--segments", action="store_true", help="With -o: also write OUT_PREFIX + ID + .segments.tsv, the alignment in the read's "
+                   "sample coordinates, one line per reference k-mer on the path: ref_name, ref_pos (forward-strand position of the k-mer's "
+                   "first base), strand, kmer, smp_st (first sample), smp_span (samples to the end of its last event), smp_n (samples of its "
+                   "events), n_cols (events), shared (1: its first event is also the previous k-mer's last), mean, stdv (pA over its samples), "
+                   "level (mean, normalised), model_mean")
     p.add_argument("--max-events", type=int, default=50000, help="Skip reads with more events than this (the reference's 50000; 0: no limit -- "
                    "2 bits per cell make alignments affordable here that the reference skips)")
     p.add_argument("--band", type=int, default=0, help="Align within a band of this half-width (in k-mers) around the diagonal: work and memory "

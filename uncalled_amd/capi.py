@@ -146,6 +146,19 @@ ALIGN_QUERY = np.dtype([("read", "<u4"), ("pad", "<u4"), ("smp_st", "<u8"), ("sm
 ALIGN_RESULT = np.dtype([("dtw", DTW_RESULT), ("n_events", "<u4"), ("n_kept", "<u4"), ("tgt_mean", "<f4"), ("tgt_stdv", "<f4"),
                          ("scale", "<f4"), ("shift", "<f4"), ("status", "<u4"), ("pad", "<u4")])
 
+# unc_event_t (the reference's Event), unc_segment_t, unc_seg_info_t
+EVENT = np.dtype([("mean", "<f4"), ("stdv", "<f4"), ("start", "<u4"), ("length", "<u4")])
+SEGMENT = np.dtype([("smp_st", "<u8"), ("smp_span", "<u4"), ("smp_n", "<u4"), ("col_first", "<u4"), ("n_cols", "<u4"), ("mean", "<f4"),
+                    ("stdv", "<f4"), ("level", "<f4"), ("shared", "<u4")])
+SEG_INFO = np.dtype([("row_first", "<u4"), ("n_rows", "<u4"), ("status", "<u4"), ("pad", "<u4")])
+SEG_OK, SEG_TRUNCATED, SEG_NONE = 0, 1, 2
+
+
+class AlignSegments(C.Structure):
+    """unc_align_segments_t: where the records, the rows' counts and the tapped events go (host addresses; 0 = not wanted)"""
+    _fields_ = [("seg", C.c_void_p), ("seg_off", C.c_void_p), ("info", C.c_void_p), ("events", C.c_void_p), ("evt_off", C.c_void_p)]
+
+
 REF_STRETCH = np.dtype([("rid", "<i4"), ("fwd", "<u4"), ("st", "<u8"), ("en", "<u8")])      # unc_ref_stretch_t
 _libs = {}
 
@@ -248,6 +261,9 @@ def load(path=None):
         L.unc_align_last_timing.argtypes = [vp]
         L.unc_align_model_target.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.unc_align_model_target.restype = None
+    if hasattr(L, "unc_align_segments_batch"):
+        L.unc_align_segments_batch.argtypes = L.unc_align_batch.argtypes[:-1] + [C.POINTER(AlignSegments), vp]
+        L.unc_align_segments_last_timing.argtypes = [C.POINTER(C.c_float)]
     if hasattr(L, "unc_refseq_load"):
         L.unc_refseq_load.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
         L.unc_refseq_free.argtypes = [vp]; L.unc_refseq_free.restype = None
@@ -256,6 +272,8 @@ def load(path=None):
         L.unc_align_ref_batch.argtypes = [vp, C.POINTER(Params), C.POINTER(AlignOpts), u32, vp, vp, vp, C.c_int, u32, vp, vp, u64, vp,
                                           vp, vp, vp, vp, vp, vp, vp]
         L.unc_align_ref_last_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "unc_align_ref_segments_batch"):
+            L.unc_align_ref_segments_batch.argtypes = L.unc_align_ref_batch.argtypes[:-1] + [C.POINTER(AlignSegments), vp]
     _libs[key] = L
     return L
 
@@ -419,14 +437,46 @@ def align_opts(dtw=None, mask=True, create_events=True, target="kmers", max_even
     return o
 
 
+class _SegOut:
+    """the buffers behind segments=True / events=True of align_batch and align_ref_batch: room for every k-mer of a query and for every
+    column it can have"""
+
+    def __init__(self, n_kmers, col_room, segments, events):
+        n = len(n_kmers)
+        self.segments, self.events = segments, events
+        self.arg = AlignSegments()
+        if segments:
+            self.seg_off = np.cumsum([0] + list(n_kmers)).astype(np.uint64)
+            self.seg = np.zeros(max(1, int(self.seg_off[-1])), dtype=SEGMENT)
+            self.info = np.zeros(n, dtype=SEG_INFO)
+            self.arg.seg, self.arg.seg_off, self.arg.info = self.seg.ctypes.data, self.seg_off.ctypes.data, self.info.ctypes.data
+        if events:
+            self.evt_off = np.cumsum([0] + list(col_room)).astype(np.uint64)
+            self.evt = np.zeros(max(1, int(self.evt_off[-1])), dtype=EVENT)
+            self.arg.events, self.arg.evt_off = self.evt.ctypes.data, self.evt_off.ctypes.data
+
+    def results(self, res):
+        """what the call returns after its other outputs: with segments a list of SEGMENT arrays per query and the SEG_INFO records
+        (row_first, n_rows, status), with events a list of EVENT arrays (a query's columns)"""
+        out = []
+        if self.segments:
+            out.append([self.seg[int(self.seg_off[q]):int(self.seg_off[q]) + int(self.info["n_rows"][q])].copy() for q in range(len(res))])
+            out.append(self.info)
+        if self.events:
+            out.append([self.evt[int(self.evt_off[q]):int(self.evt_off[q]) + int(res["n_kept"][q])].copy() for q in range(len(res))])
+        return out
+
+
 def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
-                on_device=False, device=0, stream=None, lib=None):
+                on_device=False, device=0, stream=None, lib=None, segments=False, events=False):
     """unc_align_batch: the pipeline of the reference's dtw_test (slice -> events -> stall mask -> normalisation to the k-mers'
     levels -> DTW) for a batch of queries on the GPU.  raw / offsets / calib: the reads as Mapper.map_batch takes them (raw: an int16
     array, or with on_device=True a device address).  queries: (read index, smp_st, smp_en) triples, smp_en == 0 = to the read's end;
     kmers_list[q]: query q's reference k-mers.  -> ALIGN_RESULT records (dtw.score, dtw.mean_score, dtw.path_len, n_events, n_kept,
     tgt_mean, tgt_stdv, scale, shift, status); with levels=True and / or paths=True also a list of the normalised columns per query and
-    a list of paths as dtw_batch returns them (None for a query that was not aligned)."""
+    a list of paths as dtw_batch returns them (None for a query that was not aligned).  segments=True (unc_align_segments_batch): then
+    also a list of SEGMENT arrays -- per query one record per k-mer on its path, in the read's sample coordinates -- and the SEG_INFO
+    records (row_first, n_rows, status); events=True: then also a list of EVENT arrays, the query's columns as events."""
     L = lib or load()
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     calib = np.ascontiguousarray(calib, dtype=CALIB)
@@ -460,11 +510,17 @@ def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None
     if paths:
         path_off = np.cumsum([0] + [c + k.size - 1 for c, k in zip(room, kms)]).astype(np.uint64)
         path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
-    _check(L, L.unc_align_batch(int(device), C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
-                                n_reads, raw_ptr, offsets.ctypes.data, calib.ctypes.data, 1 if on_device else 0, n, qs.ctypes.data,
-                                km.ctypes.data, km_off.ctypes.data, int(workspace_bytes), res.ctypes.data,
-                                lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None,
-                                path.ctypes.data if paths else None, path_off.ctypes.data if paths else None, stream))
+    args = (int(device), C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
+            n_reads, raw_ptr, offsets.ctypes.data, calib.ctypes.data, 1 if on_device else 0, n, qs.ctypes.data,
+            km.ctypes.data, km_off.ctypes.data, int(workspace_bytes), res.ctypes.data,
+            lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None,
+            path.ctypes.data if paths else None, path_off.ctypes.data if paths else None)
+    so = None
+    if segments or events:
+        so = _SegOut([k.size for k in kms], room, segments, events)
+        _check(L, L.unc_align_segments_batch(*args, C.byref(so.arg), stream))
+    else:
+        _check(L, L.unc_align_batch(*args, stream))
     out = [res]
     if levels:
         out.append([lev[int(lev_off[q]):int(lev_off[q]) + int(res["n_kept"][q])].copy() for q in range(n)])
@@ -472,7 +528,17 @@ def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None
         done = (DTW_OK, DTW_PATH_TRUNCATED, DTW_LEFT_BAND)
         out.append([path[int(path_off[q]):int(path_off[q]) + int(res["dtw"]["path_len"][q])].copy() if res["status"][q] in done else None
                     for q in range(n)])
+    if so is not None:
+        out += so.results(res)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def align_segments_last_timing(lib=None):
+    """kernel milliseconds of k_align_segments in the calling thread's last alignment call, summed over the DTW's rounds"""
+    L = lib or load()
+    ms = C.c_float()
+    L.unc_align_segments_last_timing(C.byref(ms))
+    return ms.value
 
 
 def align_last_timing(lib=None):
@@ -547,11 +613,12 @@ def ref_kmers_batch(refseq, stretches, stream=None):
 
 
 def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
-                    kmers=False, on_device=False, stream=None):
+                    kmers=False, on_device=False, stream=None, segments=False, events=False):
     """unc_align_ref_batch: align_batch with coordinates in place of k-mer arrays.  stretches[q] = (rid, st, en, fwd) names the bases
     whose k-mers are query q's rows; they are made on the GPU (the index's) and reach the host only with kmers=True.  Everything else
     as align_batch, and so are the results, bit for bit, for the k-mers ref_kmers gives for the same stretches.  -> ALIGN_RESULT
-    records, then, as asked for, the lists of levels, of paths and of k-mers per query."""
+    records, then, as asked for, the lists of levels, of paths and of k-mers per query, and what segments=True / events=True add
+    (unc_align_ref_segments_batch; as in align_batch, after everything else)."""
     L = refseq.L
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     calib = np.ascontiguousarray(calib, dtype=CALIB)
@@ -584,12 +651,18 @@ def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, 
     if kmers:
         km_off = np.cumsum([0] + counts).astype(np.uint64)
         km = np.empty(max(1, int(km_off[-1])), dtype=np.uint16)
-    _check(L, L.unc_align_ref_batch(refseq.h, C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
-                                    n_reads, raw_ptr, offsets.ctypes.data, calib.ctypes.data, 1 if on_device else 0, n, qs.ctypes.data,
-                                    ss.ctypes.data, int(workspace_bytes), res.ctypes.data,
-                                    lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None,
-                                    km.ctypes.data if kmers else None, km_off.ctypes.data if kmers else None,
-                                    path.ctypes.data if paths else None, path_off.ctypes.data if paths else None, stream))
+    args = (refseq.h, C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
+            n_reads, raw_ptr, offsets.ctypes.data, calib.ctypes.data, 1 if on_device else 0, n, qs.ctypes.data,
+            ss.ctypes.data, int(workspace_bytes), res.ctypes.data,
+            lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None,
+            km.ctypes.data if kmers else None, km_off.ctypes.data if kmers else None,
+            path.ctypes.data if paths else None, path_off.ctypes.data if paths else None)
+    so = None
+    if segments or events:
+        so = _SegOut(counts, room, segments, events)
+        _check(L, L.unc_align_ref_segments_batch(*args, C.byref(so.arg), stream))
+    else:
+        _check(L, L.unc_align_ref_batch(*args, stream))
     out = [res]
     if levels:
         out.append([lev[int(lev_off[q]):int(lev_off[q]) + int(res["n_kept"][q])].copy() for q in range(n)])
@@ -599,6 +672,8 @@ def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, 
                     for q in range(n)])
     if kmers:
         out.append([km[int(km_off[q]):int(km_off[q + 1])].copy() for q in range(n)])
+    if so is not None:
+        out += so.results(res)
     return out[0] if len(out) == 1 else tuple(out)
 
 

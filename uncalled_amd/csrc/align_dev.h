@@ -36,7 +36,28 @@ struct AlignPrep {
     const float *model;           // [3][1024] of the template model; the means are the first 1024
     float model_mean, model_stdv; // the target of UNC_ALIGN_TARGET_MODEL
     AlignRecord *rec;
+    uint32_t *col_evt;            // out, may be null: col_evt[col_off + c] = the kept event that became column c (not written with UNC_ALIGN_RAW)
 };
+
+struct DtwJob;
+// k_align_segments (k_segments.hip): a round's paths, collapsed to one record per row while they lie on the device
+struct SegArgs {
+    const DtwJob *jobs;           // the round's; path_cap is the room of the job's path on the device, rows + cols - 1
+    uint32_t n_jobs;
+    uint32_t raw;                 // UNC_ALIGN_RAW: column c is sample c (events and col_evt are null, means holds the calibrated samples)
+    const uint32_t *path;         // the round's pairs (column, row), a job's from path_off on, end cell first
+    const unc_dtw_result_t *res;  // by job.out: path_len and status as k_dtw left them
+    const AlignQuery *queries;    // by job.out, as everything below
+    const AlignRecord *rec;       // scale and shift
+    const unc_event_t *events;    // kept events, query q from col_off on
+    const float *means;
+    const uint32_t *col_evt;
+    const uint64_t *smp_st;       // the slice's first sample in its read
+    const uint64_t *seg_off;      // n_queries + 1, from 0
+    unc_segment_t *seg;
+    unc_seg_info_t *info;
+};
+void launch_align_segments(const SegArgs &a, hipStream_t st);
 
 // slices -> one contiguous run of samples (k_events then takes every slice as a read of its own), or with `calibrated` != null the
 // calibrated samples themselves, query q from col_off on
@@ -55,9 +76,9 @@ struct AlignRows {
     // on the device: allocates the array and queues on `st` whatever fills it.  The array lives as long as the object
     virtual int queue(hipStream_t st, const uint16_t **d_kmers) = 0;
 };
-// who: the entry point's name, for the messages
+// who: the entry point's name, for the messages.  segs (null: none): the outputs of unc_align_segments_batch
 int align_run(const char *who, int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
               const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries, const unc_align_query_t *queries,
               AlignRows &rows, uint64_t workspace_bytes, unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path,
-              const uint64_t *path_off, void *stream);
+              const uint64_t *path_off, void *stream, const unc_align_segments_t *segs = nullptr);
 }  // namespace unc

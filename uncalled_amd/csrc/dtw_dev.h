@@ -88,9 +88,17 @@ void launch_dtw(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st)
 // here).  skip (may be null): alignments with skip[a] != 0 are left out and res[a] is not written.  The arguments are the caller's
 // to check.  band: 0 = the full matrix, else the half-width: back-pointers, rounds, UNC_DTW_TOO_LARGE and the queue (descending steps)
 // go by the banded layout, and an alignment whose band is too narrow gets UNC_DTW_BAND_TOO_NARROW.  unc_align.cpp hands over the levels its own kernels have written: they never visit the host.
+// hook (may be null): every alignment's path is then kept whole on the device (rows + cols - 1 pairs of room, whatever the caller's),
+// and after each round's kernel, before anything is copied out and the next round reuses the buffers, the hook is handed the round.
+// What the caller gets is as without it: path_cap pairs at most, and UNC_DTW_PATH_TRUNCATED by path_cap.
+struct DtwRoundHook {
+    virtual ~DtwRoundHook() = default;
+    // d_jobs: the round's jobs as the kernel saw them (path_cap = rows + cols - 1); d_res is indexed by DtwJob::out
+    virtual int round(const DtwJob *d_jobs, uint32_t n_jobs, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) = 0;
+};
 int dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
                    const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                   const uint64_t *path_off, hipStream_t st);
+                   const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook = nullptr);
 // the template model's 3 x 1024 floats on `device` (uploaded once per device) and on the host
 int dtw_model_device(int device, const float **out);
 const float *dtw_model_host();

@@ -7,6 +7,7 @@
 //                    writes the calibrated samples instead (read_buffer.cpp:239-241), and they are the columns.
 //   k_align_prep     EventProfiler::get_full_mask (event_profiler.hpp:71-104,129-151), the target of dtw_test.cpp:106-116,
 //                    Normalizer::set_signal and pop (normalizer.cpp:31-44,114-128).  The levels go where k_dtw reads its columns.
+//                    On request it also says which kept event became which column (col_evt), for k_align_segments (k_segments.hip).
 // What is sequential and why.  The profiler's window is a Normalizer ring of 25 means: Welford's update until it is full, then the
 // rolling update, both recurrences in double whose every step rounds; the decision for event n needs the window's state after
 // event n + 24.  The target is a float running sum over the k-mers, the normaliser's two sums are double running sums over the
@@ -45,8 +46,9 @@ __global__ void __launch_bounds__(256) k_align_gather(const int16_t *raw, const 
     }
 }
 
-// EventProfiler::get_full_mask over means[0 .. n): the kept means, in order, to out[0 ..); returns how many
-__device__ __forceinline__ uint32_t stall_mask(const float *means, uint32_t n, float *out) {
+// EventProfiler::get_full_mask over means[0 .. n): the kept means, in order, to out[0 ..); returns how many.  col_evt (may be null):
+// which event each of them is
+__device__ __forceinline__ uint32_t stall_mask(const float *means, uint32_t n, float *out, uint32_t *col_evt) {
     double mean = 0.0, varsum = 0.0;                 // window_: Normalizer::reset
     uint32_t wn = 0, rd = 0, wr = 0, full = 0;
     uint32_t to_mask = 0, is_full = 0;
@@ -80,13 +82,18 @@ __device__ __forceinline__ uint32_t stall_mask(const float *means, uint32_t n, f
             }
         }
         if (is_full) {
-            if (to_mask == 0) out[kept++] = means[decided];
+            if (to_mask == 0) {
+                if (col_evt) col_evt[kept] = decided;
+                out[kept++] = means[decided];
+            }
             decided++;
         }
     }
     for (; decided < n; ++decided) {                 // the tail loop, event_profiler.hpp:141-148
-        if (to_mask == 0) out[kept++] = means[decided];
-        else to_mask--;
+        if (to_mask == 0) {
+            if (col_evt) col_evt[kept] = decided;
+            out[kept++] = means[decided];
+        } else to_mask--;
     }
     return kept;
 }
@@ -106,8 +113,10 @@ __global__ void __launch_bounds__(64) k_align_prep(AlignPrep A, uint32_t queries
     const float *src = means;
     uint32_t m = n;
     if (!raw_mode && !(A.flags & UNC_ALIGN_NO_MASK)) {
-        m = stall_mask(means, n, lev);
+        m = stall_mask(means, n, lev, A.col_evt ? A.col_evt + Q.col_off : nullptr);
         src = lev;
+    } else if (A.col_evt && !raw_mode) {
+        for (uint32_t i = 0; i < n; ++i) A.col_evt[Q.col_off + i] = i;       // every event is a column
     }
 
     // ---- c. the target, dtw_test.cpp:106-116: `read_mean += get_mean(k)` is a float sum and `/= kmers.size()` a float division;
@@ -170,3 +179,5 @@ void launch_align_prep(const AlignPrep &p, hipStream_t st) {
 // k_ref_kmers, which makes a batch's rows from the packed reference, is compiled as part of this translation unit, so that every
 // build of the alignment sources holds it
 #include "k_refseq.hip"
+// and so is k_align_segments, which collapses a round's paths to one record per k-mer
+#include "k_segments.hip"

@@ -176,17 +176,31 @@ struct EvRun {                        // what EventDetector carries from sample 
     uint32_t t, evt_st, total_events, n_kept, over;      // over: an event found the read's room in `means` full (reported, never silent)
     double evt_st_sum, mean_sum;
     float len_sum;
+    double evt_st_sumsq;              // (FULL only)
 };
 
-// both peak detectors on one sample's t-statistics, then create_event (event_detector.cpp:101-110,296-319); csum = C[evt_en]
-__device__ __forceinline__ void fsm_step(EvRun &E, const unc_params_t &P, float t1, float t2, uint32_t buf_mid, double csum, float *means,
-                                         uint32_t mcap) {
+// both peak detectors on one sample's t-statistics, then create_event (event_detector.cpp:101-110,296-319); csum = C[evt_en].
+// FULL: the whole Event, not its mean alone -- csq = Q[evt_en], and `events` receives start, length and stdv beside the mean
+template <bool FULL>
+__device__ __forceinline__ void fsm_step(EvRun &E, const unc_params_t &P, float t1, float t2, uint32_t buf_mid, double csum, double csq,
+                                         float *means, unc_event_t *events, uint32_t mcap) {
     const bool p1 = peak_detect(E.sd, &E.ld, t1, buf_mid, P.peak_height);
     const bool p2 = peak_detect(E.ld, nullptr, t2, buf_mid, P.peak_height);
     if (p1 || p2) {
         const uint32_t evt_en = buf_mid - UNC_WINDOW1 + 1;
         const uint32_t length = (uint32_t)(float)(evt_en - E.evt_st);
         float mean = (float)((csum - E.evt_st_sum) / (double)length);
+        unc_event_t ev;
+        if constexpr (FULL) {
+            // event_detector.cpp:304-306,309: a double difference rounded to float, the variance in float (the mean as it is before
+            // calibrate), the correctly rounded root (sqrt_rn above), calibrate last
+            const float deltasqr = (float)(csq - E.evt_st_sumsq);
+            const float var = __fsub_rn(__fdiv_rn(deltasqr, (float)length), __fmul_rn(mean, mean));
+            ev.stdv = __fmul_rn(__fadd_rn(sqrt_rn(fmaxf(var, 0.0f)), 0.0f), 1.0f);
+            ev.start = E.evt_st;
+            ev.length = length;
+            E.evt_st_sumsq = csq;
+        }
         E.evt_st = evt_en;
         E.evt_st_sum = csum;
         E.len_sum = __fadd_rn(E.len_sum, (float)length);
@@ -194,6 +208,10 @@ __device__ __forceinline__ void fsm_step(EvRun &E, const unc_params_t &P, float 
         mean = __fmul_rn(__fadd_rn(mean, 0.0f), 1.0f);   // calibrate(): cal_offset_=0, cal_coef_=1
         if (mean >= P.min_mean && mean <= P.max_mean) {
             if (E.n_kept < mcap) {
+                if constexpr (FULL) {
+                    ev.mean = mean;
+                    events[E.n_kept] = ev;
+                }
                 means[E.n_kept++] = mean;
                 E.mean_sum += (double)mean;              // Normalizer::set_signal's first sum, in index order
             } else E.over = 1u;
@@ -201,7 +219,17 @@ __device__ __forceinline__ void fsm_step(EvRun &E, const unc_params_t &P, float 
     }
 }
 
-__global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint32_t reads_per_wave) {
+// What the FULL variant takes beside the mapper's arguments: where every kept event goes whole (the same layout as R.means: read r
+// from moff[r] on)
+struct EvtFullArgs { unc_event_t *events; };
+__device__ __forceinline__ unc_event_t *events_of(EvtFullArgs a) { return a.events; }
+// The mapper's instantiation is k_events<false>: the pack is empty, so it has the three arguments and the code it always had.
+// k_events<true, EvtFullArgs> is the alignment path's.  (One kernel body with an optional trailing argument, and not a second
+// __global__ around a shared device function: with the body behind a call the mapper's kernel came out 134 instructions longer,
+// and it is the mapper's kernel that must not move.)
+template <bool FULL, class... Full>
+__global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint32_t reads_per_wave, Full... full) {
+    static_assert(sizeof...(Full) == (FULL ? 1 : 0), "k_events<true> takes EvtFullArgs, k_events<false> nothing more");
     const int lane = lane_id();
     const uint32_t r = blockIdx.x * reads_per_wave + (uint32_t)lane;
     const bool active = (uint32_t)lane < reads_per_wave && r < R.n_reads;
@@ -212,12 +240,15 @@ __global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint3
     const float cal_range = R.calib[r].range, cal_offset = R.calib[r].offset, cal_digit = R.calib[r].digitisation;
     const int16_t *raw = R.raw + off;
     float *means = R.means + moff;
+    unc_event_t *events = nullptr;
+    if constexpr (FULL) events = events_of(full...) + moff;
 
     // EventDetector::reset, event_detector.cpp:47-77
     EvRun E;
     E.sd = Detector{P.threshold1, P.window_length1, 0u, -1, FLT_MAX, false};
     E.ld = Detector{P.threshold2, P.window_length2, 0u, -1, FLT_MAX, false};
     E.t = 1; E.evt_st = 0; E.total_events = 0; E.n_kept = 0; E.over = 0; E.evt_st_sum = 0.0; E.mean_sum = 0.0; E.len_sum = 0.0f;
+    if constexpr (FULL) E.evt_st_sumsq = 0.0;
     double C[WIN], Q[WIN];            // C[i] = cumulative sum at position (next sample's position) - 12 + i
 #pragma unroll
     for (int i = 0; i < WIN; ++i) { C[i] = 0.0; Q[i] = 0.0; }
@@ -236,7 +267,7 @@ __global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint3
         bool bad = false;      // (head and tail samples: the division itself)
         const float t1 = E.t <= 2 * UNC_WINDOW1 ? 0.0f : tstat_win<UNC_WINDOW1, false>(C, Q, 12, buf_mid >= UNC_WINDOW1 ? 6 - UNC_WINDOW1 : 12, bad);
         const float t2 = E.t <= 2 * UNC_WINDOW2 ? 0.0f : tstat_win<UNC_WINDOW2, false>(C, Q, 12, buf_mid >= UNC_WINDOW2 ? 6 - UNC_WINDOW2 : 12, bad);
-        fsm_step(E, P, t1, t2, buf_mid, C[4], means, mcap);
+        fsm_step<FULL>(E, P, t1, t2, buf_mid, C[4], Q[4], means, events, mcap);
 #pragma unroll
         for (int i = 0; i < 12; ++i) { C[i] = C[i + 1]; Q[i] = Q[i + 1]; }
     };
@@ -274,7 +305,7 @@ __global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint3
 #pragma unroll
         for (int j = 0; j < EB; ++j) {
             E.t++;
-            fsm_step(E, P, t1[j], t2[j], E.t - 7, C[4 + j], means, mcap);
+            fsm_step<FULL>(E, P, t1[j], t2[j], E.t - 7, C[4 + j], Q[4 + j], means, events, mcap);
         }
 #pragma unroll
         for (int i = 0; i < 12; ++i) { C[i] = C[i + EB]; Q[i] = Q[i + EB]; }
@@ -488,6 +519,11 @@ void launch_rt_events(const int16_t *raw, const float *raw_pa, const RtChunkDesc
 }
 void launch_events(const DevReads &rd, const unc_params_t &P, hipStream_t st, uint32_t reads_per_wave) {
     if (reads_per_wave == 0 || reads_per_wave > (uint32_t)WAVE) reads_per_wave = WAVE;
-    hipLaunchKernelGGL(k_events, dim3((rd.n_reads + reads_per_wave - 1) / reads_per_wave), dim3(WAVE), 0, st, rd, P, reads_per_wave);
+    hipLaunchKernelGGL((k_events<false>), dim3((rd.n_reads + reads_per_wave - 1) / reads_per_wave), dim3(WAVE), 0, st, rd, P, reads_per_wave);
+}
+void launch_events_full(const DevReads &rd, const unc_params_t &P, unc_event_t *events, hipStream_t st, uint32_t reads_per_wave) {
+    if (reads_per_wave == 0 || reads_per_wave > (uint32_t)WAVE) reads_per_wave = WAVE;
+    const EvtFullArgs full{events};
+    hipLaunchKernelGGL((k_events<true, EvtFullArgs>), dim3((rd.n_reads + reads_per_wave - 1) / reads_per_wave), dim3(WAVE), 0, st, rd, P, reads_per_wave, full);
 }
 }  // namespace unc

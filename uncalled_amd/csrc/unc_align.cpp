@@ -18,6 +18,13 @@
 using namespace unc;
 
 static thread_local float g_align_ms[4] = {0, 0, 0, 0};
+static thread_local float g_seg_ms = 0;
+
+extern "C" int unc_align_segments_last_timing(float *ms) {
+    if (!ms) return fail(UNC_ERR_ARG, "unc_align_segments_last_timing: null argument");
+    *ms = g_seg_ms;
+    return UNC_OK;
+}
 
 extern "C" int unc_align_last_timing(float *ms4) {
     if (!ms4) return fail(UNC_ERR_ARG, "unc_align_last_timing: null argument");
@@ -46,17 +53,48 @@ struct HipEvents {       // (timing only)
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     ~HipEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
 };
+
+// k_align_segments on every round of the DTW, while the round's paths are on the device (the next round reuses their buffer)
+struct SegmentsHook : DtwRoundHook {
+    SegArgs args{};
+    std::vector<hipEvent_t> ev;       // (timing only) two per round
+    ~SegmentsHook() override { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+    int round(const DtwJob *d_jobs, uint32_t n_jobs, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) override {
+        hipEvent_t a = nullptr, b = nullptr;
+        HIPCHK(hipEventCreate(&a)); ev.push_back(a);
+        HIPCHK(hipEventCreate(&b)); ev.push_back(b);
+        args.jobs = d_jobs; args.n_jobs = n_jobs; args.path = d_path; args.res = d_res;
+        HIPCHK(hipEventRecord(a, st));
+        launch_align_segments(args, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(b, st));
+        return UNC_OK;
+    }
+    // after the stream has been waited for
+    int total_ms(float *ms) {
+        *ms = 0;
+        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+            float t = 0;
+            HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+            *ms += t;
+        }
+        return UNC_OK;
+    }
+};
 }  // namespace
 
 // The pipeline, from the arguments' checks to the results.  The queries' rows are `rows`' business (align_dev.h).
 int unc::align_run(const char *who, int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
                    const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries, const unc_align_query_t *queries,
                    AlignRows &rows, uint64_t workspace_bytes, unc_align_result_t *results, float *levels, const uint64_t *lev_off,
-                   uint32_t *path, const uint64_t *path_off, void *stream) {
+                   uint32_t *path, const uint64_t *path_off, void *stream, const unc_align_segments_t *segs) {
     // ---- arguments: everything is checked before the device is touched
     if (!raw || !offsets || !calib || !queries || !results) return fail(UNC_ERR_ARG, "%s: null argument", who);
     if (path && !path_off) return fail(UNC_ERR_ARG, "%s: path without path_off", who);
     if (levels && !lev_off) return fail(UNC_ERR_ARG, "%s: levels without lev_off", who);
+    if (segs && segs->seg && !segs->seg_off) return fail(UNC_ERR_ARG, "%s: seg without seg_off", who);
+    if (segs && segs->events && !segs->evt_off) return fail(UNC_ERR_ARG, "%s: events without evt_off", who);
+    const bool want_seg = segs && (segs->seg || segs->info), want_tap = segs && segs->events;
     if (device < 0 || device >= DTW_MAX_DEVICES) return fail(UNC_ERR_ARG, "%s: device %d", who, device);
     unc_align_opts_t O;
     memset(&O, 0, sizeof O);
@@ -74,6 +112,7 @@ int unc::align_run(const char *who, int device, const unc_params_t *params, cons
     if (P.window_length1 != UNC_WINDOW1 || P.window_length2 != UNC_WINDOW2)
         return fail(UNC_ERR_ARG, "%s: the event detector's windows must be %d and %d", who, UNC_WINDOW1, UNC_WINDOW2);
     memset(g_align_ms, 0, sizeof g_align_ms);
+    g_seg_ms = 0;
     if (n_queries == 0) return UNC_OK;
     for (uint32_t i = 0; i < n_reads; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(UNC_ERR_ARG, "%s: offsets must ascend", who);
@@ -95,6 +134,8 @@ int unc::align_run(const char *who, int device, const unc_params_t *params, cons
         if (int rc = rows.rows(q, &km_at, &km_n)) return rc;
         if (path && path_off[q + 1] < path_off[q]) return fail(UNC_ERR_ARG, "%s: path_off must ascend", who);
         if (levels && lev_off[q + 1] < lev_off[q]) return fail(UNC_ERR_ARG, "%s: lev_off must ascend", who);
+        if (segs && segs->seg && segs->seg_off[q + 1] < segs->seg_off[q]) return fail(UNC_ERR_ARG, "%s: seg_off must ascend", who);
+        if (want_tap && segs->evt_off[q + 1] < segs->evt_off[q]) return fail(UNC_ERR_ARG, "%s: evt_off must ascend", who);
         AlignQuery &a = hq[q];
         memset(&a, 0, sizeof a);
         a.src_off = offsets[u.read] - offsets[0] + u.smp_st;
@@ -125,6 +166,9 @@ int unc::align_run(const char *who, int device, const unc_params_t *params, cons
     DevBuf<uint64_t> d_goff, d_moff;
     DevBuf<unc_calib_t> d_calib;
     DevBuf<unc_evt_info_t> d_info;
+    DevBuf<unc_event_t> d_events;          // with segments or the event tap only: the kept events whole, and which became which column
+    DevBuf<uint32_t> d_col_evt;
+    const bool whole_events = (want_seg || want_tap) && !raw_mode;
     const int16_t *d_raw = raw + offsets[0];
     if (!on_device) {
         const uint64_t n_smp = offsets[n_reads] - offsets[0];
@@ -164,7 +208,10 @@ int unc::align_run(const char *who, int device, const unc_params_t *params, cons
     if (!raw_mode) {
         // as few slices per wavefront as a grid of 2048 wavefronts allows (the kernel is sequential per slice)
         const uint32_t rpw = std::min<uint32_t>(64u, std::max<uint32_t>(1u, (n_queries + 2047u) / 2048u));
-        launch_events(rd, P, st, rpw);
+        if (whole_events) {
+            HIPCHK(d_events.alloc(n_cols)); HIPCHK(d_col_evt.alloc(n_cols));
+            launch_events_full(rd, P, d_events.p, st, rpw);
+        } else launch_events(rd, P, st, rpw);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ev.e[2], st));
@@ -178,6 +225,7 @@ int unc::align_run(const char *who, int device, const unc_params_t *params, cons
     ap.kmers = d_kmers; ap.model = d_model;
     unc_align_model_target(&ap.model_mean, &ap.model_stdv);
     ap.rec = d_rec.p;
+    ap.col_evt = whole_events ? d_col_evt.p : nullptr;
     launch_align_prep(ap, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev.e[3], st));
@@ -210,14 +258,77 @@ int unc::align_run(const char *who, int device, const unc_params_t *params, cons
         const uint64_t room = path ? path_off[q + 1] - path_off[q] : 0;
         j.path_cap = skip[q] ? 0 : (uint32_t)std::min<uint64_t>(room, (uint64_t)j.rows + j.cols - 1);
     }
+    // f. (with segments) k_align_segments on every round's paths
+    SegmentsHook hook;
+    DevBuf<unc_segment_t> d_seg;
+    DevBuf<unc_seg_info_t> d_seginfo;
+    DevBuf<uint64_t> d_seg_off, d_smp_st;
+    // the records' layout on the device, from 0: a query's room there is the caller's, or its k-mers if those are fewer (a path has
+    // no more rows); without seg no room at all, and info alone is filled
+    std::vector<uint64_t> seg_off((size_t)n_queries + 1, 0);
+    std::vector<uint64_t> smp_st(want_seg ? n_queries : 0);
+    if (want_seg) {
+        for (uint32_t q = 0; q < n_queries; ++q) {
+            smp_st[q] = queries[q].smp_st;
+            seg_off[q + 1] = seg_off[q] + (segs->seg ? std::min<uint64_t>(segs->seg_off[q + 1] - segs->seg_off[q], hq[q].n_km) : 0);
+        }
+        HIPCHK(d_seg.alloc(seg_off[n_queries])); HIPCHK(d_seginfo.alloc(n_queries));
+        HIPCHK(d_seg_off.alloc(seg_off.size())); HIPCHK(d_smp_st.alloc(n_queries));
+        HIPCHK(hipMemcpyAsync(d_seg_off.p, seg_off.data(), seg_off.size() * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_smp_st.p, smp_st.data(), smp_st.size() * 8, hipMemcpyHostToDevice, st));
+        SegArgs &sa = hook.args;
+        sa.raw = raw_mode ? 1u : 0u;
+        sa.queries = d_q.p; sa.rec = d_rec.p;
+        sa.events = d_events.p; sa.means = d_means.p; sa.col_evt = d_col_evt.p;
+        sa.smp_st = d_smp_st.p; sa.seg_off = d_seg_off.p; sa.seg = d_seg.p; sa.info = d_seginfo.p;
+    }
     if (int rc = dtw_run_device(device, n_queries, d_levels.p, d_kmers, jobs.data(), skip.data(), &prm, O.band, workspace_bytes, dres.data(),
-                                path, path_off, st))
+                                path, path_off, st, want_seg ? &hook : nullptr))
         return rc;
     (void)unc_dtw_last_timing(&g_align_ms[3], nullptr, nullptr);
+    if (int rc = hook.total_ms(&g_seg_ms)) return rc;
     for (uint32_t q = 0; q < n_queries; ++q) {
         if (skip[q]) continue;
         results[q].dtw = dres[q];
         results[q].status = dres[q].status;
+    }
+    if (want_seg) {     // one copy of the records and of the rows' counts, dealt out on the host: nothing outside a query's count is written
+        std::vector<unc_seg_info_t> hinfo(n_queries);
+        std::vector<unc_segment_t> hseg((size_t)seg_off[n_queries]);
+        HIPCHK(hipMemcpyAsync(hinfo.data(), d_seginfo.p, (size_t)n_queries * sizeof(unc_seg_info_t), hipMemcpyDeviceToHost, st));
+        if (!hseg.empty()) HIPCHK(hipMemcpyAsync(hseg.data(), d_seg.p, hseg.size() * sizeof(unc_segment_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (uint32_t q = 0; q < n_queries; ++q) {
+            const uint32_t s = results[q].status;
+            unc_seg_info_t inf = hinfo[q];
+            // (a query that was in no round, or whose path has no start, has no rows: its record on the device may never have been written)
+            if (skip[q] || (s != UNC_DTW_OK && s != UNC_DTW_PATH_TRUNCATED)) { inf.row_first = 0; inf.n_rows = 0; inf.status = UNC_SEG_NONE; inf.pad = 0; }
+            if (!segs->seg && inf.status == UNC_SEG_TRUNCATED) inf.status = UNC_SEG_OK;       // (no records were asked for: none is missing)
+            if (segs->info) segs->info[q] = inf;
+            if (segs->seg) {
+                const uint64_t got = std::min<uint64_t>(inf.n_rows, seg_off[q + 1] - seg_off[q]);
+                memcpy(segs->seg + segs->seg_off[q], hseg.data() + seg_off[q], got * sizeof(unc_segment_t));
+            }
+        }
+    }
+    if (want_tap) {     // the tap: the columns as events, one copy of all of them, dealt out on the host
+        std::vector<unc_event_t> hev(raw_mode ? 0 : (size_t)n_cols);
+        std::vector<uint32_t> hce(raw_mode ? 0 : (size_t)n_cols);
+        std::vector<float> hsm(raw_mode ? (size_t)n_cols : 0);
+        if (raw_mode) HIPCHK(hipMemcpyAsync(hsm.data(), d_means.p, (size_t)n_cols * sizeof(float), hipMemcpyDeviceToHost, st));
+        else {
+            HIPCHK(hipMemcpyAsync(hev.data(), d_events.p, (size_t)n_cols * sizeof(unc_event_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(hce.data(), d_col_evt.p, (size_t)n_cols * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        for (uint32_t q = 0; q < n_queries; ++q) {
+            const uint64_t got = std::min<uint64_t>(results[q].n_kept, segs->evt_off[q + 1] - segs->evt_off[q]);
+            unc_event_t *out = segs->events + segs->evt_off[q];
+            for (uint64_t c = 0; c < got; ++c) {
+                if (raw_mode) out[c] = unc_event_t{hsm[hq[q].col_off + c], 0.0f, (uint32_t)c, 1u};
+                else out[c] = hev[hq[q].col_off + hce[hq[q].col_off + c]];
+            }
+        }
     }
     if (levels) {       // the tap: one copy of all levels, dealt out on the host
         std::vector<float> h((size_t)n_cols);
@@ -273,6 +384,18 @@ extern "C" int unc_align_batch(int device, const unc_params_t *params, const unc
     UploadedRows rows(kmers, km_off, n_queries);
     return align_run("unc_align_batch", device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, rows, workspace_bytes,
                      results, levels, lev_off, path, path_off, stream);
+}
+
+extern "C" int unc_align_segments_batch(int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
+                                        const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
+                                        const unc_align_query_t *queries, const uint16_t *kmers, const uint64_t *km_off, uint64_t workspace_bytes,
+                                        unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path,
+                                        const uint64_t *path_off, const unc_align_segments_t *out, void *stream) {
+    if (!raw || !offsets || !calib || !queries || !kmers || !km_off || !results || !out)
+        return fail(UNC_ERR_ARG, "unc_align_segments_batch: null argument");
+    UploadedRows rows(kmers, km_off, n_queries);
+    return align_run("unc_align_segments_batch", device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, rows,
+                     workspace_bytes, results, levels, lev_off, path, path_off, stream, out);
 }
 
 // unc_align_ref_batch and the packed reference: unc_refseq.cpp and k_refseq.hip are compiled as part of this translation unit, so that

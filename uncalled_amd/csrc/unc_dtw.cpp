@@ -86,7 +86,7 @@ struct HipEvent {       // (timing only)
 // The queue, the rounds and the launches over columns and k-mers that lie in device memory already (dtw_dev.h).
 int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
                         const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                        const uint64_t *path_off, hipStream_t st) {
+                        const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook) {
     g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
     std::vector<uint64_t> cells(n), words(n);
     for (uint32_t a = 0; a < n; ++a) {
@@ -134,16 +134,19 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
     HIPCHK(hipEventCreate(&t0.e)); HIPCHK(hipEventCreate(&t1.e));
 
     std::vector<DtwJob> round;
+    std::vector<uint32_t> caller_cap;       // (with a hook: what the caller's room holds of each of the round's paths)
     std::vector<uint32_t> h_path;
     std::vector<unc_dtw_result_t> h_res;
     size_t at = 0;
     while (at < todo.size()) {
         // a round: the next alignments of the queue whose back-pointers fit the workspace together
-        round.clear();
+        round.clear(); caller_cap.clear();
         uint64_t w = 0, lines = 0, pairs = 0;
         while (at < todo.size() && (round.empty() || (w + words[todo[at]]) * 4 <= workspace_bytes)) {
             DtwJob j = jobs[todo[at]];
             j.crumb_off = w; j.line_off = lines; j.path_off = pairs;
+            caller_cap.push_back(j.path_cap);
+            if (hook) j.path_cap = j.rows + j.cols - 1;          // (both below 2^31)
             w += words[todo[at]];
             lines += 2 * dtw_line_floats(j.cols);
             pairs += j.path_cap;
@@ -152,18 +155,21 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
         }
         const uint32_t nr = (uint32_t)round.size();
         HIPCHK(d_crumbs.reserve(w)); HIPCHK(d_lines.reserve(lines)); HIPCHK(d_jobs.reserve(nr));
-        if (path) HIPCHK(d_path.reserve(std::max<uint64_t>(2 * pairs, 2)));
+        const bool dev_path = path || hook;
+        if (dev_path) HIPCHK(d_path.reserve(std::max<uint64_t>(2 * pairs, 2)));
         HIPCHK(hipMemcpyAsync(d_jobs.p, round.data(), nr * sizeof(DtwJob), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(d_next.p, 0, sizeof(uint32_t), st));
         DtwBatch b{};
         b.events = d_events; b.kmers = d_kmers; b.model = d_model; b.jobs = d_jobs.p; b.n_jobs = nr;
         b.subseq = prm->subseq; b.band = band; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
-        b.crumbs = d_crumbs.p; b.lines = d_lines.p; b.path = path ? d_path.p : nullptr; b.res = d_res.p; b.next = d_next.p;
+        b.crumbs = d_crumbs.p; b.lines = d_lines.p; b.path = dev_path ? d_path.p : nullptr; b.res = d_res.p; b.next = d_next.p;
         const uint32_t grid = std::min<uint32_t>(nr, (uint32_t)n_cu * 16u);
         HIPCHK(hipEventRecord(t0.e, st));
         launch_dtw(b, prm->cost, grid, st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(t1.e, st));
+        if (hook)
+            if (int rc = hook->round(d_jobs.p, nr, d_path.p, d_res.p, st)) return rc;
         h_res.resize(n);
         h_path.resize(path ? 2 * pairs : 0);
         // (the results of this round's alignments lie scattered over d_res: the whole array is small)
@@ -175,12 +181,16 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
         g_last_ms += ms;
         g_last_rounds += 1;
         g_last_crumb_bytes = std::max<uint64_t>(g_last_crumb_bytes, w * 4);
-        for (const DtwJob &j : round) {
+        for (size_t k = 0; k < round.size(); ++k) {
+            const DtwJob &j = round[k];
             unc_dtw_result_t r = h_res[j.out];
             r.mean_score = r.score / (float)r.path_len;          // dtw.hpp:130-132
+            // (with a hook the kernel had room for every pair, or was asked for a path the caller did not want: the status it gives
+            // without one, k_dtw.hip -- UNC_DTW_LEFT_BAND first, then the caller's room)
+            if (hook && r.status == UNC_DTW_OK && path && r.path_len > caller_cap[k]) r.status = UNC_DTW_PATH_TRUNCATED;
             res[j.out] = r;
             if (path) {
-                const uint64_t got = std::min<uint64_t>(r.path_len, j.path_cap);
+                const uint64_t got = std::min<uint64_t>(r.path_len, caller_cap[k]);
                 memcpy(path + 2 * path_off[j.out], h_path.data() + 2 * j.path_off, got * 2 * sizeof(uint32_t));
             }
         }

@@ -6,6 +6,8 @@
 
 namespace unc {
 void launch_events(const DevReads &rd, const unc_params_t &P, hipStream_t st, uint32_t reads_per_wave = 0);
+// the variant that also writes every kept event whole (mean, stdv, start, length) to events[moff[r] ..]: the alignment path's, for segments
+void launch_events_full(const DevReads &rd, const unc_params_t &P, unc_event_t *events, hipStream_t st, uint32_t reads_per_wave = 0);
 void launch_rt_events(const int16_t *raw, const float *raw_pa, const RtChunkDesc *chunks, uint32_t n_chunks, RtChan *chans, float *norm_ring,
                       const unc_params_t &P, float tgt_mean, float tgt_stdv, unc_evt_info_t *info, uint32_t *ring0_out, hipStream_t st);
 void launch_map(const MapArgs &a, uint32_t grid, hipStream_t st, bool profile = false, uint32_t team = 1);   // team: chunked path only, wavefronts per channel

@@ -201,18 +201,18 @@ struct GeneratedRows : AlignRows {
 };
 }  // namespace
 
-extern "C" int unc_align_ref_batch(const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
-                                   const int16_t *raw, const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
-                                   const unc_align_query_t *queries, const unc_ref_stretch_t *stretches, uint64_t workspace_bytes,
-                                   unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint16_t *kmers_out,
-                                   const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off, void *stream) {
-    static const char *who = "unc_align_ref_batch";
+// unc_align_ref_batch, and with segs unc_align_ref_segments_batch
+static int align_ref(const char *who, const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
+                     const int16_t *raw, const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
+                     const unc_align_query_t *queries, const unc_ref_stretch_t *stretches, uint64_t workspace_bytes,
+                     unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint16_t *kmers_out, const uint64_t *kmers_off,
+                     uint32_t *path, const uint64_t *path_off, void *stream, const unc_align_segments_t *segs) {
     if (!rs || !stretches) return fail(UNC_ERR_ARG, "%s: null argument", who);
     if (kmers_out && !kmers_off) return fail(UNC_ERR_ARG, "%s: kmers_out without kmers_off", who);
     g_ref_kmers_ms = 0;
     GeneratedRows rows(rs, stretches, kmers_out ? kmers_off : nullptr);
     if (int rc = align_run(who, rs->device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, rows, workspace_bytes,
-                           results, levels, lev_off, path, path_off, stream))
+                           results, levels, lev_off, path, path_off, stream, segs))
         return rc;
     if (!rows.queued) return UNC_OK;         // (no queries)
     HIPCHK(hipEventElapsedTime(&g_ref_kmers_ms, rows.ev.e[0], rows.ev.e[1]));       // (align_run has waited for the stream)
@@ -225,4 +225,24 @@ extern "C" int unc_align_ref_batch(const unc_refseq_t *rs, const unc_params_t *p
             memcpy(kmers_out + kmers_off[q], h.data() + rows.at[q], (size_t)rows.count[q] * sizeof(uint16_t));
     }
     return UNC_OK;
+}
+
+extern "C" int unc_align_ref_batch(const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
+                                   const int16_t *raw, const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
+                                   const unc_align_query_t *queries, const unc_ref_stretch_t *stretches, uint64_t workspace_bytes,
+                                   unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint16_t *kmers_out,
+                                   const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off, void *stream) {
+    return align_ref("unc_align_ref_batch", rs, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, stretches,
+                     workspace_bytes, results, levels, lev_off, kmers_out, kmers_off, path, path_off, stream, nullptr);
+}
+
+extern "C" int unc_align_ref_segments_batch(const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
+                                            const int16_t *raw, const uint64_t *offsets, const unc_calib_t *calib, int on_device,
+                                            uint32_t n_queries, const unc_align_query_t *queries, const unc_ref_stretch_t *stretches,
+                                            uint64_t workspace_bytes, unc_align_result_t *results, float *levels, const uint64_t *lev_off,
+                                            uint16_t *kmers_out, const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off,
+                                            const unc_align_segments_t *out, void *stream) {
+    if (!out) return fail(UNC_ERR_ARG, "unc_align_ref_segments_batch: null argument");
+    return align_ref("unc_align_ref_segments_batch", rs, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, stretches,
+                     workspace_bytes, results, levels, lev_off, kmers_out, kmers_off, path, path_off, stream, out);
 }
