@@ -518,6 +518,37 @@ def check_example(chain, G, refseq, index, prefix):
     return a["segs"], kms
 
 
+def check_binding_order(G, refseq, index, prefix):
+    """the binding's two functions on check_example's two queries with every switch on: the length and the order of each returned
+    tuple as the docstrings state them (results, levels, paths, with align_ref_batch the k-mers, then segments, their info, events),
+    and every output the two routes share equal between them -- arrays byte for byte, records of floats by rec_equal"""
+    from uncalled_amd import capi
+    r = len(G.signals) - 1
+    qs = [(r, 10001, 14001), (r, 10001, 14001)]
+    stretches = [(0, 6700, 7000, True), (0, 6700, 7000, False)]
+    want = [capi.ref_kmers(index, prefix, *s) for s in stretches]
+    by_ref = capi.align_ref_batch(refseq, G.raw, G.offsets, G.calib, qs, stretches, levels=True, paths=True, kmers=True, segments=True, events=True)
+    by_km = capi.align_batch(G.raw, G.offsets, G.calib, qs, want, levels=True, paths=True, segments=True, events=True, lib=refseq.L)
+    assert isinstance(by_ref, tuple) and len(by_ref) == 7 and isinstance(by_km, tuple) and len(by_km) == 6
+    res, lev, paths, kms, segs, info, evs = by_ref
+    assert [k.dtype for k in kms] == [np.uint16] * 2 and [k.size for k in kms] == [296, 296]
+    assert all(k.tobytes() == w.tobytes() for k, w in zip(kms, want))
+    for res, lev, paths, segs, info, evs in (by_ref[:3] + by_ref[4:], by_km):      # what lies at each position
+        assert isinstance(res, np.ndarray) and res.dtype == capi.ALIGN_RESULT and res.shape == (2,)
+        assert [int(x) for x in res["status"]] == [capi.DTW_OK] * 2
+        assert [(x.dtype, x.shape) for x in lev] == [(np.float32, (int(n),)) for n in res["n_kept"]]
+        assert [(x.dtype, x.shape) for x in paths] == [(np.uint32, (int(n), 2)) for n in res["dtw"]["path_len"]]
+        assert [(x.dtype, x.shape) for x in segs] == [(capi.SEGMENT, (296,))] * 2
+        assert isinstance(info, np.ndarray) and info.dtype == capi.SEG_INFO and [int(x) for x in info["n_rows"]] == [296, 296]
+        assert [(x.dtype, x.shape) for x in evs] == [(capi.EVENT, (int(n),)) for n in res["n_kept"]]
+    a, b = by_ref[:3] + by_ref[4:], by_km
+    assert a[0].tobytes() == b[0].tobytes() and a[4].tobytes() == b[4].tobytes(), "results or info differ between the routes"
+    for i, name in ((1, "levels"), (2, "paths")):
+        assert [x.tobytes() for x in a[i]] == [x.tobytes() for x in b[i]], name
+    for i, name in ((3, "segments"), (5, "events")):
+        assert all(rec_equal(x, y) for x, y in zip(a[i], b[i])), name
+
+
 def check_goldens_unchanged(G, L):
     """every golden query through the new entry point with every output asked for: results, levels and paths byte for byte those
     of the old one"""

@@ -50,6 +50,14 @@ def test_example_read_by_coordinates_and_by_kmers(chain, hip_lib):
     rs.close()
 
 
+def test_binding_order_by_coordinates_and_by_kmers(hip_lib):
+    from uncalled_amd import capi
+    ix = capi.Index(EX_PREFIX)
+    rs = capi.RefSeq(ix, EX_PREFIX)
+    sc.check_binding_order(ac.Goldens(), rs, ix, str(EX_PREFIX))
+    rs.close()
+
+
 def test_the_stage_is_timed(hip_lib, reads):
     from uncalled_amd import capi
     capi.align_batch(reads.raw, reads.offsets, reads.calib, [(0, 0, 2000)], [reads.walk[:200]])

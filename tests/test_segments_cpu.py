@@ -139,6 +139,15 @@ def test_example_read_by_coordinates_and_by_kmers(example_segments):
 
 
 @pytest.mark.lanesim
+def test_binding_order_by_coordinates_and_by_kmers(sim_align_lib):
+    from uncalled_amd import capi
+    ix = capi.Index(EX_PREFIX, lib=sim_align_lib)
+    rs = capi.RefSeq(ix, EX_PREFIX)
+    sc.check_binding_order(ac.Goldens(), rs, ix, str(EX_PREFIX))
+    rs.close()
+
+
+@pytest.mark.lanesim
 def test_argument_errors_by_coordinates(sim_align_lib):
     from uncalled_amd import capi
     G = ac.Goldens()

@@ -467,30 +467,18 @@ class _SegOut:
         return out
 
 
-def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
-                on_device=False, device=0, stream=None, lib=None, segments=False, events=False):
-    """unc_align_batch: the pipeline of the reference's dtw_test (slice -> events -> stall mask -> normalisation to the k-mers'
-    levels -> DTW) for a batch of queries on the GPU.  raw / offsets / calib: the reads as Mapper.map_batch takes them (raw: an int16
-    array, or with on_device=True a device address).  queries: (read index, smp_st, smp_en) triples, smp_en == 0 = to the read's end;
-    kmers_list[q]: query q's reference k-mers.  -> ALIGN_RESULT records (dtw.score, dtw.mean_score, dtw.path_len, n_events, n_kept,
-    tgt_mean, tgt_stdv, scale, shift, status); with levels=True and / or paths=True also a list of the normalised columns per query and
-    a list of paths as dtw_batch returns them (None for a query that was not aligned).  segments=True (unc_align_segments_batch): then
-    also a list of SEGMENT arrays -- per query one record per k-mer on its path, in the read's sample coordinates -- and the SEG_INFO
-    records (row_first, n_rows, status); events=True: then also a list of EVENT arrays, the query's columns as events."""
-    L = lib or load()
+def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths,
+           on_device, stream, segments, events):
+    """what align_batch and align_ref_batch share: the ALIGN_QUERY records, raw on the host or the device, the room per query, the buffers
+    of levels and paths, _SegOut, the call and the tuple it returns.  entries: the entry point's name without and with segments;
+    first: its first argument; rows_args: what names the rows, after the queries; n_rows: the rows of every query; tap_args: what
+    follows lev_off; tap: None, or what makes the list that goes between the paths and the segments' outputs"""
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     calib = np.ascontiguousarray(calib, dtype=CALIB)
     n_reads, n = offsets.size - 1, len(queries)
-    if n != len(kmers_list):
-        raise ValueError("as many k-mer arrays as queries are needed")
     qs = np.zeros(n, dtype=ALIGN_QUERY)
     for i, (r, st, en) in enumerate(queries):
         qs[i]["read"], qs[i]["smp_st"], qs[i]["smp_en"] = r, st, en
-    kms = [np.ascontiguousarray(k, dtype=np.uint16).ravel() for k in kmers_list]
-    km_off = np.cumsum([0] + [k.size for k in kms]).astype(np.uint64)
-    km = np.concatenate(kms) if n else np.zeros(0, np.uint16)
-    if km.size == 0:
-        km = np.zeros(1, np.uint16)         # (a valid address for the library's own argument checks)
     if on_device:
         raw_ptr = int(raw)
     else:
@@ -508,19 +496,19 @@ def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None
         lev_off = np.cumsum([0] + room).astype(np.uint64)
         lev = np.empty(max(1, int(lev_off[-1])), dtype=np.float32)
     if paths:
-        path_off = np.cumsum([0] + [c + k.size - 1 for c, k in zip(room, kms)]).astype(np.uint64)
+        path_off = np.cumsum([0] + [max(0, c + k - 1) for c, k in zip(room, n_rows)]).astype(np.uint64)
         path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
-    args = (int(device), C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
+    args = (first, C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
             n_reads, raw_ptr, offsets.ctypes.data, calib.ctypes.data, 1 if on_device else 0, n, qs.ctypes.data,
-            km.ctypes.data, km_off.ctypes.data, int(workspace_bytes), res.ctypes.data,
-            lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None,
+            *rows_args, int(workspace_bytes), res.ctypes.data,
+            lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None, *tap_args,
             path.ctypes.data if paths else None, path_off.ctypes.data if paths else None)
     so = None
     if segments or events:
-        so = _SegOut([k.size for k in kms], room, segments, events)
-        _check(L, L.unc_align_segments_batch(*args, C.byref(so.arg), stream))
+        so = _SegOut(n_rows, room, segments, events)
+        _check(L, getattr(L, entries[1])(*args, C.byref(so.arg), stream))
     else:
-        _check(L, L.unc_align_batch(*args, stream))
+        _check(L, getattr(L, entries[0])(*args, stream))
     out = [res]
     if levels:
         out.append([lev[int(lev_off[q]):int(lev_off[q]) + int(res["n_kept"][q])].copy() for q in range(n)])
@@ -528,9 +516,31 @@ def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None
         done = (DTW_OK, DTW_PATH_TRUNCATED, DTW_LEFT_BAND)
         out.append([path[int(path_off[q]):int(path_off[q]) + int(res["dtw"]["path_len"][q])].copy() if res["status"][q] in done else None
                     for q in range(n)])
+    if tap is not None:
+        out.append(tap())
     if so is not None:
         out += so.results(res)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
+                on_device=False, device=0, stream=None, lib=None, segments=False, events=False):
+    """unc_align_batch: the pipeline of the reference's dtw_test (slice -> events -> stall mask -> normalisation to the k-mers'
+    levels -> DTW) for a batch of queries on the GPU.  raw / offsets / calib: the reads as Mapper.map_batch takes them (raw: an int16
+    array, or with on_device=True a device address).  queries: (read index, smp_st, smp_en) triples, smp_en == 0 = to the read's end;
+    kmers_list[q]: query q's reference k-mers.  -> ALIGN_RESULT records (dtw.score, dtw.mean_score, dtw.path_len, n_events, n_kept,
+    tgt_mean, tgt_stdv, scale, shift, status); with levels=True and / or paths=True also a list of the normalised columns per query and
+    a list of paths as dtw_batch returns them (None for a query that was not aligned).  segments=True (unc_align_segments_batch): then
+    also a list of SEGMENT arrays -- per query one record per k-mer on its path, in the read's sample coordinates -- and the SEG_INFO
+    records (row_first, n_rows, status); events=True: then also a list of EVENT arrays, the query's columns as events."""
+    if len(queries) != len(kmers_list):
+        raise ValueError("as many k-mer arrays as queries are needed")
+    kms = [np.ascontiguousarray(k, dtype=np.uint16).ravel() for k in kmers_list]
+    km_off = np.cumsum([0] + [k.size for k in kms]).astype(np.uint64)
+    km = np.concatenate(kms + [np.zeros(1, np.uint16)])         # (one element more: a valid address for the library's own argument checks)
+    return _align(lib or load(), ("unc_align_batch", "unc_align_segments_batch"), int(device), (km.ctypes.data, km_off.ctypes.data),
+                  [k.size for k in kms], (), None, raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths, on_device, stream,
+                  segments, events)
 
 
 def align_segments_last_timing(lib=None):
@@ -619,62 +629,16 @@ def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, 
     as align_batch, and so are the results, bit for bit, for the k-mers ref_kmers gives for the same stretches.  -> ALIGN_RESULT
     records, then, as asked for, the lists of levels, of paths and of k-mers per query, and what segments=True / events=True add
     (unc_align_ref_segments_batch; as in align_batch, after everything else)."""
-    L = refseq.L
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    calib = np.ascontiguousarray(calib, dtype=CALIB)
-    n_reads, n = offsets.size - 1, len(queries)
-    if n != len(stretches):
+    if len(queries) != len(stretches):
         raise ValueError("as many stretches as queries are needed")
-    qs = np.zeros(n, dtype=ALIGN_QUERY)
-    for i, (r, st, en) in enumerate(queries):
-        qs[i]["read"], qs[i]["smp_st"], qs[i]["smp_en"] = r, st, en
     ss = _stretches(stretches)
     counts = [max(0, int(en) - int(st) - 4) for _, st, en, _ in stretches]
-    if on_device:
-        raw_ptr = int(raw)
-    else:
-        raw = np.ascontiguousarray(raw, dtype=np.int16)
-        raw_ptr = raw.ctypes.data
-    res = np.zeros(n, dtype=ALIGN_RESULT)
-    room = []       # (as in align_batch)
-    for r, st, en in queries:
-        ln = int(offsets[r + 1] - offsets[r]) if 0 <= r < n_reads else 0
-        ns = max(0, (int(en) if en else ln) - int(st))
-        room.append(ns if opts is not None and opts.flags & ALIGN_RAW else ns // 2 + 16)
-    lev = lev_off = path = path_off = km = km_off = None
-    if levels:
-        lev_off = np.cumsum([0] + room).astype(np.uint64)
-        lev = np.empty(max(1, int(lev_off[-1])), dtype=np.float32)
-    if paths:
-        path_off = np.cumsum([0] + [max(0, c + k - 1) for c, k in zip(room, counts)]).astype(np.uint64)
-        path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
-    if kmers:
-        km_off = np.cumsum([0] + counts).astype(np.uint64)
-        km = np.empty(max(1, int(km_off[-1])), dtype=np.uint16)
-    args = (refseq.h, C.byref(params) if params is not None else None, C.byref(opts) if opts is not None else None,
-            n_reads, raw_ptr, offsets.ctypes.data, calib.ctypes.data, 1 if on_device else 0, n, qs.ctypes.data,
-            ss.ctypes.data, int(workspace_bytes), res.ctypes.data,
-            lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None,
-            km.ctypes.data if kmers else None, km_off.ctypes.data if kmers else None,
-            path.ctypes.data if paths else None, path_off.ctypes.data if paths else None)
-    so = None
-    if segments or events:
-        so = _SegOut(counts, room, segments, events)
-        _check(L, L.unc_align_ref_segments_batch(*args, C.byref(so.arg), stream))
-    else:
-        _check(L, L.unc_align_ref_batch(*args, stream))
-    out = [res]
-    if levels:
-        out.append([lev[int(lev_off[q]):int(lev_off[q]) + int(res["n_kept"][q])].copy() for q in range(n)])
-    if paths:
-        done = (DTW_OK, DTW_PATH_TRUNCATED, DTW_LEFT_BAND)
-        out.append([path[int(path_off[q]):int(path_off[q]) + int(res["dtw"]["path_len"][q])].copy() if res["status"][q] in done else None
-                    for q in range(n)])
-    if kmers:
-        out.append([km[int(km_off[q]):int(km_off[q + 1])].copy() for q in range(n)])
-    if so is not None:
-        out += so.results(res)
-    return out[0] if len(out) == 1 else tuple(out)
+    km_off = np.cumsum([0] + counts).astype(np.uint64)
+    km = np.empty(max(1, int(km_off[-1])), dtype=np.uint16) if kmers else None
+    return _align(refseq.L, ("unc_align_ref_batch", "unc_align_ref_segments_batch"), refseq.h, (ss.ctypes.data,), counts,
+                  (km.ctypes.data, km_off.ctypes.data) if kmers else (None, None),
+                  (lambda: [km[int(km_off[q]):int(km_off[q + 1])].copy() for q in range(len(counts))]) if kmers else None,
+                  raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths, on_device, stream, segments, events)
 
 
 def align_ref_last_timing(lib=None):

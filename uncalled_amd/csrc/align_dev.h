@@ -1,4 +1,5 @@
-// What unc_align.cpp (host) and k_align.hip (kernels) share: the record of one query and the launch wrappers.
+// What unc_align.cpp (host) and k_align.hip (kernels) share: the record of one query and the launch wrappers.  And what unc_align.cpp
+// and unc_refseq.cpp share: the record of one call (AlignCall) and where its queries' rows come from (AlignRows).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,9 +77,14 @@ struct AlignRows {
     // on the device: allocates the array and queues on `st` whatever fills it.  The array lives as long as the object
     virtual int queue(hipStream_t st, const uint16_t **d_kmers) = 0;
 };
-// who: the entry point's name, for the messages.  segs (null: none): the outputs of unc_align_segments_batch
-int align_run(const char *who, int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
-              const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries, const unc_align_query_t *queries,
-              AlignRows &rows, uint64_t workspace_bytes, unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path,
-              const uint64_t *path_off, void *stream, const unc_align_segments_t *segs = nullptr);
+// What the four entry points (unc_align_batch, unc_align_segments_batch, unc_align_ref_batch, unc_align_ref_segments_batch) share of
+// their parameters, under the names include/uncalled_hip.h gives them.  Each fills one, once.  who: the entry point's name, for the
+// messages.  segs (null: none): the outputs of the two _segments_ entry points
+struct AlignCall {
+    const char *who; int device; const unc_params_t *params; const unc_align_opts_t *opts;
+    uint32_t n_reads; const int16_t *raw; const uint64_t *offsets; const unc_calib_t *calib; int on_device;
+    uint32_t n_queries; const unc_align_query_t *queries; uint64_t workspace_bytes; unc_align_result_t *results;
+    float *levels; const uint64_t *lev_off; uint32_t *path; const uint64_t *path_off; void *stream; const unc_align_segments_t *segs;
+};
+int align_run(const AlignCall &c, AlignRows &rows);
 }  // namespace unc

@@ -1,5 +1,6 @@
-// Host side of unc_align_batch (include/uncalled_hip.h): argument checks, the layout of the queries' slices, means and levels in
-// device memory, the launches of the stages (k_align.hip, k_events.hip) and the hand-over to the DTW's planner (unc_dtw.cpp).
+// Host side of unc_align_batch (include/uncalled_hip.h).  An entry point fills an AlignCall (align_dev.h) from its parameters;
+// align_run is the list of steps over one AlignRun: argument checks, the layout of the queries' slices, means and levels in device
+// memory, the launches of the stages (k_align.hip, k_events.hip), the hand-over to the DTW's planner (unc_dtw.cpp), the outputs.
 // Host copies that remain: the reads' samples in (unless on_device), the queries and k-mers in, one 32-byte record per query out
 // between normalisation and DTW (the planner lays out back-pointers by column counts), results and paths out, levels out on request.
 #include <hip/hip_runtime.h>
@@ -49,225 +50,231 @@ extern "C" void unc_align_model_target(float *mean, float *stdv) {
 }
 
 namespace {
-struct HipEvents {       // (timing only)
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~HipEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 // k_align_segments on every round of the DTW, while the round's paths are on the device (the next round reuses their buffer)
 struct SegmentsHook : DtwRoundHook {
     SegArgs args{};
-    std::vector<hipEvent_t> ev;       // (timing only) two per round
-    ~SegmentsHook() override { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+    DevEvents ev;       // (timing only) two per round
     int round(const DtwJob *d_jobs, uint32_t n_jobs, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) override {
-        hipEvent_t a = nullptr, b = nullptr;
-        HIPCHK(hipEventCreate(&a)); ev.push_back(a);
-        HIPCHK(hipEventCreate(&b)); ev.push_back(b);
+        const size_t i = ev.e.size();
+        HIPCHK(ev.create(i + 2));
         args.jobs = d_jobs; args.n_jobs = n_jobs; args.path = d_path; args.res = d_res;
-        HIPCHK(hipEventRecord(a, st));
+        HIPCHK(ev.record(i, st));
         launch_align_segments(args, st);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(b, st));
-        return UNC_OK;
-    }
-    // after the stream has been waited for
-    int total_ms(float *ms) {
-        *ms = 0;
-        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-            float t = 0;
-            HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            *ms += t;
-        }
+        HIPCHK(ev.record(i + 1, st));
         return UNC_OK;
     }
 };
-}  // namespace
 
-// The pipeline, from the arguments' checks to the results.  The queries' rows are `rows`' business (align_dev.h).
-int unc::align_run(const char *who, int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
-                   const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries, const unc_align_query_t *queries,
-                   AlignRows &rows, uint64_t workspace_bytes, unc_align_result_t *results, float *levels, const uint64_t *lev_off,
-                   uint32_t *path, const uint64_t *path_off, void *stream, const unc_align_segments_t *segs) {
-    // ---- arguments: everything is checked before the device is touched
-    if (!raw || !offsets || !calib || !queries || !results) return fail(UNC_ERR_ARG, "%s: null argument", who);
-    if (path && !path_off) return fail(UNC_ERR_ARG, "%s: path without path_off", who);
-    if (levels && !lev_off) return fail(UNC_ERR_ARG, "%s: levels without lev_off", who);
-    if (segs && segs->seg && !segs->seg_off) return fail(UNC_ERR_ARG, "%s: seg without seg_off", who);
-    if (segs && segs->events && !segs->evt_off) return fail(UNC_ERR_ARG, "%s: events without evt_off", who);
-    const bool want_seg = segs && (segs->seg || segs->info), want_tap = segs && segs->events;
-    if (device < 0 || device >= DTW_MAX_DEVICES) return fail(UNC_ERR_ARG, "%s: device %d", who, device);
+// One call of the pipeline: the call's record, and what the steps hand to each other.  The host vectors that an upload reads are kept
+// here as well: they live as long as the call
+struct AlignRun : AlignCall {
+    AlignRows &rows;
+    // check_and_lay_out: the options and parameters, resolved; the queries' records and the two totals
     unc_align_opts_t O;
-    memset(&O, 0, sizeof O);
-    if (opts) O = *opts;
-    if (O.flags & ~(UNC_ALIGN_DTW_PARAMS | UNC_ALIGN_NO_MASK | UNC_ALIGN_RAW | UNC_ALIGN_TARGET_MODEL))
-        return fail(UNC_ERR_ARG, "%s: unknown flags %#x", who, O.flags);
-    unc_dtw_params_t prm = {UNC_DTW_NONE, UNC_DTW_R94D, 1.0f, 1.0f, 1.0f};        // dtw_test.cpp:76-78,162
-    if (O.flags & UNC_ALIGN_DTW_PARAMS) prm = O.dtw;
-    if (prm.subseq > UNC_DTW_COL) return fail(UNC_ERR_ARG, "%s: unknown subseq %u", who, prm.subseq);
-    if (prm.cost > UNC_DTW_R94D) return fail(UNC_ERR_ARG, "%s: unknown cost %u", who, prm.cost);
-    if (O.band && prm.subseq != UNC_DTW_NONE) return fail(UNC_ERR_ARG, "%s: the band is global only (subseq %u)", who, prm.subseq);
+    unc_dtw_params_t prm;
     unc_params_t P;
-    if (params) P = *params;
-    else unc_params_default(&P);
-    if (P.window_length1 != UNC_WINDOW1 || P.window_length2 != UNC_WINDOW2)
-        return fail(UNC_ERR_ARG, "%s: the event detector's windows must be %d and %d", who, UNC_WINDOW1, UNC_WINDOW2);
-    memset(g_align_ms, 0, sizeof g_align_ms);
-    g_seg_ms = 0;
-    if (n_queries == 0) return UNC_OK;
-    for (uint32_t i = 0; i < n_reads; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(UNC_ERR_ARG, "%s: offsets must ascend", who);
-    const bool raw_mode = (O.flags & UNC_ALIGN_RAW) != 0;
-    std::vector<AlignQuery> hq(n_queries);
+    // whole_events (with segments or the event tap): the kept events whole, and which became which column
+    bool want_seg = false, want_tap = false, raw_mode = false, whole_events = false;
+    hipStream_t st = nullptr;
+    std::vector<AlignQuery> hq;
     uint64_t n_gather = 0, n_cols = 0;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        const unc_align_query_t &u = queries[q];
-        if (u.read >= n_reads) return fail(UNC_ERR_ARG, "%s: query %u names read %u of %u", who, q, u.read, n_reads);
-        const uint64_t len = offsets[u.read + 1] - offsets[u.read];
-        const uint64_t en = u.smp_en == 0 ? len : u.smp_en;            // dtw_test.cpp:123-132
-        if (u.smp_en != 0 && u.smp_st > u.smp_en) return fail(UNC_ERR_ARG, "%s: query %u: smp_st %llu > smp_en %llu", who, q,
-                                                              (unsigned long long)u.smp_st, (unsigned long long)u.smp_en);
-        if (en > len || u.smp_st > len) return fail(UNC_ERR_ARG, "%s: query %u: [%llu, %llu) is not inside the read's %llu samples", who, q,
-                                                    (unsigned long long)u.smp_st, (unsigned long long)en, (unsigned long long)len);
-        if (en - u.smp_st >= (1ull << 31)) return fail(UNC_ERR_ARG, "%s: query %u: 2^31 or more samples", who, q);
-        uint64_t km_at = 0;
-        uint32_t km_n = 0;
-        if (int rc = rows.rows(q, &km_at, &km_n)) return rc;
-        if (path && path_off[q + 1] < path_off[q]) return fail(UNC_ERR_ARG, "%s: path_off must ascend", who);
-        if (levels && lev_off[q + 1] < lev_off[q]) return fail(UNC_ERR_ARG, "%s: lev_off must ascend", who);
-        if (segs && segs->seg && segs->seg_off[q + 1] < segs->seg_off[q]) return fail(UNC_ERR_ARG, "%s: seg_off must ascend", who);
-        if (want_tap && segs->evt_off[q + 1] < segs->evt_off[q]) return fail(UNC_ERR_ARG, "%s: evt_off must ascend", who);
-        AlignQuery &a = hq[q];
-        memset(&a, 0, sizeof a);
-        a.src_off = offsets[u.read] - offsets[0] + u.smp_st;
-        a.n_smp = (uint32_t)(en - u.smp_st);
-        a.dst_off = n_gather;
-        a.col_off = n_cols;
-        a.km_off = km_at;
-        a.n_km = km_n;
-        // (peak_detect emits a peak once it lies more than window_length / 2 samples back and then starts afresh: the short detector
-        // fires at most every third sample, the long one every fifth.  An event that finds its room full is reported below)
-        a.col_cap = raw_mode ? a.n_smp : a.n_smp / 2 + 16;
-        a.calib = calib[u.read];
-        n_gather += a.n_smp;
-        n_cols += a.col_cap;
-    }
-    if (int rc = rows.check()) return rc;
-
-    // ---- device
-    HIPCHK(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
+    // upload (d_events and d_col_evt: run_stages)
+    const int16_t *d_raw = nullptr;
+    const uint16_t *d_kmers = nullptr;
     const float *d_model = nullptr;
-    if (int rc = dtw_model_device(device, &d_model)) return rc;
     DevBuf<int16_t> d_raw_own, d_gather;
     DevBuf<float> d_means, d_levels;
-    const uint16_t *d_kmers = nullptr;
     DevBuf<AlignQuery> d_q;
     DevBuf<AlignRecord> d_rec;
-    DevBuf<uint64_t> d_goff, d_moff;
+    DevBuf<uint64_t> d_goff, d_moff, d_seg_off, d_smp_st;
     DevBuf<unc_calib_t> d_calib;
     DevBuf<unc_evt_info_t> d_info;
-    DevBuf<unc_event_t> d_events;          // with segments or the event tap only: the kept events whole, and which became which column
+    DevBuf<unc_event_t> d_events;
     DevBuf<uint32_t> d_col_evt;
-    const bool whole_events = (want_seg || want_tap) && !raw_mode;
-    const int16_t *d_raw = raw + offsets[0];
-    if (!on_device) {
-        const uint64_t n_smp = offsets[n_reads] - offsets[0];
-        HIPCHK(d_raw_own.alloc(n_smp));
-        HIPCHK(hipMemcpyAsync(d_raw_own.p, raw + offsets[0], n_smp * sizeof(int16_t), hipMemcpyHostToDevice, st));
-        d_raw = d_raw_own.p;
-    }
-    HIPCHK(d_q.alloc(n_queries)); HIPCHK(d_rec.alloc(n_queries));
-    HIPCHK(d_means.alloc(n_cols)); HIPCHK(d_levels.alloc(n_cols));
-    HIPCHK(hipMemcpyAsync(d_q.p, hq.data(), (size_t)n_queries * sizeof(AlignQuery), hipMemcpyHostToDevice, st));
-    if (int rc = rows.queue(st, &d_kmers)) return rc;
-    std::vector<uint64_t> goff, moff;
+    std::vector<uint64_t> goff, moff, seg_off, smp_st;
     std::vector<unc_calib_t> qcal;
     DevReads rd{};
-    if (!raw_mode) {       // every slice is a read of its own to k_events
-        HIPCHK(d_gather.alloc(n_gather, 64));
-        goff.resize((size_t)n_queries + 1); moff.resize((size_t)n_queries + 1); qcal.resize(n_queries);
-        for (uint32_t q = 0; q < n_queries; ++q) { goff[q] = hq[q].dst_off; moff[q] = hq[q].col_off; qcal[q] = hq[q].calib; }
-        goff[n_queries] = n_gather; moff[n_queries] = n_cols;
-        HIPCHK(d_goff.alloc((size_t)n_queries + 1)); HIPCHK(d_moff.alloc((size_t)n_queries + 1)); HIPCHK(d_calib.alloc(n_queries));
-        HIPCHK(d_info.alloc(n_queries));
-        HIPCHK(hipMemcpyAsync(d_goff.p, goff.data(), goff.size() * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_moff.p, moff.data(), moff.size() * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_calib.p, qcal.data(), qcal.size() * sizeof(unc_calib_t), hipMemcpyHostToDevice, st));
-        rd.raw = d_gather.p; rd.offsets = d_goff.p; rd.calib = d_calib.p; rd.means = d_means.p; rd.moff = d_moff.p; rd.info = d_info.p;
-        rd.n_reads = n_queries;
-        unc_align_model_target(&rd.tgt_mean, &rd.tgt_stdv);       // (k_events' own scale and shift are not used here)
-    }
-    HipEvents ev;       // (all allocations and uploads are queued above, so that the spans between the events hold kernels only)
-    for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
-
-    // a. the slices, then event detection on each
-    HIPCHK(hipEventRecord(ev.e[0], st));
-    launch_align_gather(d_raw, d_q.p, n_queries, raw_mode ? nullptr : d_gather.p, raw_mode ? d_means.p : nullptr, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.e[1], st));
-    if (!raw_mode) {
-        // as few slices per wavefront as a grid of 2048 wavefronts allows (the kernel is sequential per slice)
-        const uint32_t rpw = std::min<uint32_t>(64u, std::max<uint32_t>(1u, (n_queries + 2047u) / 2048u));
-        if (whole_events) {
-            HIPCHK(d_events.alloc(n_cols)); HIPCHK(d_col_evt.alloc(n_cols));
-            launch_events_full(rd, P, d_events.p, st, rpw);
-        } else launch_events(rd, P, st, rpw);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(ev.e[2], st));
-
-    // b. - d. mask, target, normalisation
-    AlignPrep ap{};
-    ap.queries = d_q.p; ap.n_queries = n_queries; ap.flags = O.flags;
-    ap.info = raw_mode ? nullptr : d_info.p;
-    ap.means = d_means.p;
-    ap.levels = d_levels.p;
-    ap.kmers = d_kmers; ap.model = d_model;
-    unc_align_model_target(&ap.model_mean, &ap.model_stdv);
-    ap.rec = d_rec.p;
-    ap.col_evt = whole_events ? d_col_evt.p : nullptr;
-    launch_align_prep(ap, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.e[3], st));
-    std::vector<AlignRecord> rec(n_queries);
-    std::vector<unc_evt_info_t> info(raw_mode ? 0 : n_queries);
-    HIPCHK(hipMemcpyAsync(rec.data(), d_rec.p, (size_t)n_queries * sizeof(AlignRecord), hipMemcpyDeviceToHost, st));
-    if (!raw_mode) HIPCHK(hipMemcpyAsync(info.data(), d_info.p, (size_t)n_queries * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(&g_align_ms[i], ev.e[i], ev.e[i + 1]));
-    for (uint32_t q = 0; q < n_queries && !raw_mode; ++q)
-        if (info[q].pad) return fail(UNC_ERR_OVERFLOW, "%s: query %u has more events than its room of %u", who, q, hq[q].col_cap);
-
-    // e. the DTW over the levels where they lie
-    std::vector<DtwJob> jobs(n_queries);
-    std::vector<uint8_t> skip(n_queries, 0);
-    std::vector<unc_dtw_result_t> dres(n_queries);
-    memset(dres.data(), 0, dres.size() * sizeof(unc_dtw_result_t));
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        unc_align_result_t &r = results[q];
-        memset(&r, 0, sizeof r);
-        r.n_events = rec[q].n_events; r.n_kept = rec[q].n_kept;
-        r.tgt_mean = rec[q].tgt_mean; r.tgt_stdv = rec[q].tgt_stdv; r.scale = rec[q].scale; r.shift = rec[q].shift;
-        if (r.n_kept == 0) { r.status = UNC_ALIGN_NO_COLUMNS; skip[q] = 1; }
-        else if (O.max_events && r.n_kept > O.max_events) { r.status = UNC_ALIGN_TOO_MANY; skip[q] = 1; }
-        DtwJob &j = jobs[q];
-        memset(&j, 0, sizeof j);
-        j.ev_off = hq[q].col_off; j.km_off = hq[q].km_off;
-        j.rows = hq[q].n_km; j.cols = r.n_kept;
-        j.out = q;
-        const uint64_t room = path ? path_off[q + 1] - path_off[q] : 0;
-        j.path_cap = skip[q] ? 0 : (uint32_t)std::min<uint64_t>(room, (uint64_t)j.rows + j.cols - 1);
-    }
-    // f. (with segments) k_align_segments on every round's paths
-    SegmentsHook hook;
+    DevEvents ev;                           // (timing only) around gather, event detection, mask + target + normalisation
+    std::vector<AlignRecord> rec;           // read_back
+    std::vector<DtwJob> jobs;               // plan_dtw
+    std::vector<uint8_t> skip;
+    std::vector<unc_dtw_result_t> dres;
+    SegmentsHook hook;                      // set_up_segments
     DevBuf<unc_segment_t> d_seg;
     DevBuf<unc_seg_info_t> d_seginfo;
-    DevBuf<uint64_t> d_seg_off, d_smp_st;
-    // the records' layout on the device, from 0: a query's room there is the caller's, or its k-mers if those are fewer (a path has
-    // no more rows); without seg no room at all, and info alone is filled
-    std::vector<uint64_t> seg_off((size_t)n_queries + 1, 0);
-    std::vector<uint64_t> smp_st(want_seg ? n_queries : 0);
-    if (want_seg) {
+
+    AlignRun(const AlignCall &c, AlignRows &r) : AlignCall(c), rows(r) {}
+
+    // ---- arguments: everything is checked before the device is touched: this step makes no HIP call, and every later one may.
+    // Then every query's checks in their order, and where its slice, its columns and its k-mers lie
+    int check_and_lay_out() {
+        if (!raw || !offsets || !calib || !queries || !results) return fail(UNC_ERR_ARG, "%s: null argument", who);
+        if (path && !path_off) return fail(UNC_ERR_ARG, "%s: path without path_off", who);
+        if (levels && !lev_off) return fail(UNC_ERR_ARG, "%s: levels without lev_off", who);
+        if (segs && segs->seg && !segs->seg_off) return fail(UNC_ERR_ARG, "%s: seg without seg_off", who);
+        if (segs && segs->events && !segs->evt_off) return fail(UNC_ERR_ARG, "%s: events without evt_off", who);
+        want_seg = segs && (segs->seg || segs->info);
+        want_tap = segs && segs->events;
+        if (device < 0 || device >= DTW_MAX_DEVICES) return fail(UNC_ERR_ARG, "%s: device %d", who, device);
+        memset(&O, 0, sizeof O);
+        if (opts) O = *opts;
+        if (O.flags & ~(UNC_ALIGN_DTW_PARAMS | UNC_ALIGN_NO_MASK | UNC_ALIGN_RAW | UNC_ALIGN_TARGET_MODEL))
+            return fail(UNC_ERR_ARG, "%s: unknown flags %#x", who, O.flags);
+        prm = {UNC_DTW_NONE, UNC_DTW_R94D, 1.0f, 1.0f, 1.0f};        // dtw_test.cpp:76-78,162
+        if (O.flags & UNC_ALIGN_DTW_PARAMS) prm = O.dtw;
+        if (prm.subseq > UNC_DTW_COL) return fail(UNC_ERR_ARG, "%s: unknown subseq %u", who, prm.subseq);
+        if (prm.cost > UNC_DTW_R94D) return fail(UNC_ERR_ARG, "%s: unknown cost %u", who, prm.cost);
+        if (O.band && prm.subseq != UNC_DTW_NONE) return fail(UNC_ERR_ARG, "%s: the band is global only (subseq %u)", who, prm.subseq);
+        if (params) P = *params;
+        else unc_params_default(&P);
+        if (P.window_length1 != UNC_WINDOW1 || P.window_length2 != UNC_WINDOW2)
+            return fail(UNC_ERR_ARG, "%s: the event detector's windows must be %d and %d", who, UNC_WINDOW1, UNC_WINDOW2);
+        raw_mode = (O.flags & UNC_ALIGN_RAW) != 0;
+        whole_events = (want_seg || want_tap) && !raw_mode;
+        st = (hipStream_t)stream;
+        // (the timings are zeroed here: after the options' and parameters' checks, before a batch of no queries returns)
+        memset(g_align_ms, 0, sizeof g_align_ms);
+        g_seg_ms = 0;
+        if (n_queries == 0) return UNC_OK;
+        for (uint32_t i = 0; i < n_reads; ++i)
+            if (offsets[i + 1] < offsets[i]) return fail(UNC_ERR_ARG, "%s: offsets must ascend", who);
+        hq.resize(n_queries);
+        for (uint32_t q = 0; q < n_queries; ++q) {
+            const unc_align_query_t &u = queries[q];
+            if (u.read >= n_reads) return fail(UNC_ERR_ARG, "%s: query %u names read %u of %u", who, q, u.read, n_reads);
+            const uint64_t len = offsets[u.read + 1] - offsets[u.read];
+            const uint64_t en = u.smp_en == 0 ? len : u.smp_en;            // dtw_test.cpp:123-132
+            if (u.smp_en != 0 && u.smp_st > u.smp_en) return fail(UNC_ERR_ARG, "%s: query %u: smp_st %llu > smp_en %llu", who, q,
+                                                                  (unsigned long long)u.smp_st, (unsigned long long)u.smp_en);
+            if (en > len || u.smp_st > len) return fail(UNC_ERR_ARG, "%s: query %u: [%llu, %llu) is not inside the read's %llu samples", who, q,
+                                                        (unsigned long long)u.smp_st, (unsigned long long)en, (unsigned long long)len);
+            if (en - u.smp_st >= (1ull << 31)) return fail(UNC_ERR_ARG, "%s: query %u: 2^31 or more samples", who, q);
+            AlignQuery &a = hq[q];
+            memset(&a, 0, sizeof a);
+            if (int rc = rows.rows(q, &a.km_off, &a.n_km)) return rc;
+            if (path && path_off[q + 1] < path_off[q]) return fail(UNC_ERR_ARG, "%s: path_off must ascend", who);
+            if (levels && lev_off[q + 1] < lev_off[q]) return fail(UNC_ERR_ARG, "%s: lev_off must ascend", who);
+            if (segs && segs->seg && segs->seg_off[q + 1] < segs->seg_off[q]) return fail(UNC_ERR_ARG, "%s: seg_off must ascend", who);
+            if (want_tap && segs->evt_off[q + 1] < segs->evt_off[q]) return fail(UNC_ERR_ARG, "%s: evt_off must ascend", who);
+            a.src_off = offsets[u.read] - offsets[0] + u.smp_st;
+            a.n_smp = (uint32_t)(en - u.smp_st);
+            a.dst_off = n_gather;
+            a.col_off = n_cols;
+            // (peak_detect emits a peak once it lies more than window_length / 2 samples back and then starts afresh: the short detector
+            // fires at most every third sample, the long one every fifth.  An event that finds its room full is reported by read_back)
+            a.col_cap = raw_mode ? a.n_smp : a.n_smp / 2 + 16;
+            a.calib = calib[u.read];
+            n_gather += a.n_smp;
+            n_cols += a.col_cap;
+        }
+        return rows.check();
+    }
+
+    // ---- device: every allocation and upload that the stages need is queued here, before the first timing event is recorded, so that
+    // the spans between the events hold kernels only
+    int upload() {
+        HIPCHK(hipSetDevice(device));
+        if (int rc = dtw_model_device(device, &d_model)) return rc;
+        d_raw = raw + offsets[0];
+        if (!on_device) {
+            const uint64_t n_smp = offsets[n_reads] - offsets[0];
+            HIPCHK(d_raw_own.alloc(n_smp));
+            HIPCHK(hipMemcpyAsync(d_raw_own.p, raw + offsets[0], n_smp * sizeof(int16_t), hipMemcpyHostToDevice, st));
+            d_raw = d_raw_own.p;
+        }
+        HIPCHK(d_q.alloc(n_queries)); HIPCHK(d_rec.alloc(n_queries));
+        HIPCHK(d_means.alloc(n_cols)); HIPCHK(d_levels.alloc(n_cols));
+        HIPCHK(hipMemcpyAsync(d_q.p, hq.data(), (size_t)n_queries * sizeof(AlignQuery), hipMemcpyHostToDevice, st));
+        if (int rc = rows.queue(st, &d_kmers)) return rc;
+        if (!raw_mode) {       // every slice is a read of its own to k_events
+            HIPCHK(d_gather.alloc(n_gather, 64));
+            goff.resize((size_t)n_queries + 1); moff.resize((size_t)n_queries + 1); qcal.resize(n_queries);
+            for (uint32_t q = 0; q < n_queries; ++q) { goff[q] = hq[q].dst_off; moff[q] = hq[q].col_off; qcal[q] = hq[q].calib; }
+            goff[n_queries] = n_gather; moff[n_queries] = n_cols;
+            HIPCHK(d_goff.alloc((size_t)n_queries + 1)); HIPCHK(d_moff.alloc((size_t)n_queries + 1)); HIPCHK(d_calib.alloc(n_queries));
+            HIPCHK(d_info.alloc(n_queries));
+            HIPCHK(hipMemcpyAsync(d_goff.p, goff.data(), goff.size() * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_moff.p, moff.data(), moff.size() * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_calib.p, qcal.data(), qcal.size() * sizeof(unc_calib_t), hipMemcpyHostToDevice, st));
+            rd.raw = d_gather.p; rd.offsets = d_goff.p; rd.calib = d_calib.p; rd.means = d_means.p; rd.moff = d_moff.p; rd.info = d_info.p;
+            rd.n_reads = n_queries;
+            unc_align_model_target(&rd.tgt_mean, &rd.tgt_stdv);       // (k_events' own scale and shift are not used here)
+        }
+        HIPCHK(ev.create(4));
+        return UNC_OK;
+    }
+
+    // a. the slices, then event detection on each;  b. - d. mask, target, normalisation
+    int run_stages() {
+        HIPCHK(ev.record(0, st));
+        launch_align_gather(d_raw, d_q.p, n_queries, raw_mode ? nullptr : d_gather.p, raw_mode ? d_means.p : nullptr, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(ev.record(1, st));
+        if (!raw_mode) {
+            // as few slices per wavefront as a grid of 2048 wavefronts allows (the kernel is sequential per slice)
+            const uint32_t rpw = std::min<uint32_t>(64u, std::max<uint32_t>(1u, (n_queries + 2047u) / 2048u));
+            if (whole_events) {
+                HIPCHK(d_events.alloc(n_cols)); HIPCHK(d_col_evt.alloc(n_cols));
+                launch_events_full(rd, P, d_events.p, st, rpw);
+            } else launch_events(rd, P, st, rpw);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(ev.record(2, st));
+        AlignPrep ap{};
+        ap.queries = d_q.p; ap.n_queries = n_queries; ap.flags = O.flags;
+        ap.info = raw_mode ? nullptr : d_info.p;
+        ap.means = d_means.p;
+        ap.levels = d_levels.p;
+        ap.kmers = d_kmers; ap.model = d_model;
+        unc_align_model_target(&ap.model_mean, &ap.model_stdv);
+        ap.rec = d_rec.p;
+        ap.col_evt = whole_events ? d_col_evt.p : nullptr;
+        launch_align_prep(ap, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(ev.record(3, st));
+        return UNC_OK;
+    }
+
+    // one 32-byte record per query (the planner lays out back-pointers by column counts), the stages' times, and the overflow report
+    int read_back() {
+        std::vector<unc_evt_info_t> info;
+        HIPCHK(download(rec, d_rec.p, n_queries, st));
+        if (!raw_mode) HIPCHK(download(info, d_info.p, n_queries, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < 3; ++i) HIPCHK(ev.elapsed(i, i + 1, &g_align_ms[i]));
+        for (uint32_t q = 0; q < n_queries && !raw_mode; ++q)
+            if (info[q].pad) return fail(UNC_ERR_OVERFLOW, "%s: query %u has more events than its room of %u", who, q, hq[q].col_cap);
+        return UNC_OK;
+    }
+
+    // e. the DTW over the levels where they lie: a job per query, `skip` for those that get none.  The first step that writes results
+    void plan_dtw() {
+        jobs.resize(n_queries);
+        skip.assign(n_queries, 0);
+        dres.assign(n_queries, unc_dtw_result_t{});
+        for (uint32_t q = 0; q < n_queries; ++q) {
+            unc_align_result_t &r = results[q];
+            memset(&r, 0, sizeof r);
+            r.n_events = rec[q].n_events; r.n_kept = rec[q].n_kept;
+            r.tgt_mean = rec[q].tgt_mean; r.tgt_stdv = rec[q].tgt_stdv; r.scale = rec[q].scale; r.shift = rec[q].shift;
+            if (r.n_kept == 0) { r.status = UNC_ALIGN_NO_COLUMNS; skip[q] = 1; }
+            else if (O.max_events && r.n_kept > O.max_events) { r.status = UNC_ALIGN_TOO_MANY; skip[q] = 1; }
+            DtwJob &j = jobs[q];
+            memset(&j, 0, sizeof j);
+            j.ev_off = hq[q].col_off; j.km_off = hq[q].km_off;
+            j.rows = hq[q].n_km; j.cols = r.n_kept;
+            j.out = q;
+            const uint64_t room = path ? path_off[q + 1] - path_off[q] : 0;
+            j.path_cap = skip[q] ? 0 : (uint32_t)std::min<uint64_t>(room, (uint64_t)j.rows + j.cols - 1);
+        }
+    }
+
+    // f. (with segments) what k_align_segments needs on every round's paths.  The records' layout on the device, from 0: a query's room
+    // there is the caller's, or its k-mers if those are fewer (a path has no more rows); without seg no room at all, and info alone is filled
+    int set_up_segments() {
+        seg_off.assign((size_t)n_queries + 1, 0);
+        smp_st.resize(n_queries);
         for (uint32_t q = 0; q < n_queries; ++q) {
             smp_st[q] = queries[q].smp_st;
             seg_off[q + 1] = seg_off[q] + (segs->seg ? std::min<uint64_t>(segs->seg_off[q + 1] - segs->seg_off[q], hq[q].n_km) : 0);
@@ -281,65 +288,88 @@ int unc::align_run(const char *who, int device, const unc_params_t *params, cons
         sa.queries = d_q.p; sa.rec = d_rec.p;
         sa.events = d_events.p; sa.means = d_means.p; sa.col_evt = d_col_evt.p;
         sa.smp_st = d_smp_st.p; sa.seg_off = d_seg_off.p; sa.seg = d_seg.p; sa.info = d_seginfo.p;
+        return UNC_OK;
     }
-    if (int rc = dtw_run_device(device, n_queries, d_levels.p, d_kmers, jobs.data(), skip.data(), &prm, O.band, workspace_bytes, dres.data(),
-                                path, path_off, st, want_seg ? &hook : nullptr))
-        return rc;
-    (void)unc_dtw_last_timing(&g_align_ms[3], nullptr, nullptr);
-    if (int rc = hook.total_ms(&g_seg_ms)) return rc;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        if (skip[q]) continue;
-        results[q].dtw = dres[q];
-        results[q].status = dres[q].status;
-    }
-    if (want_seg) {     // one copy of the records and of the rows' counts, dealt out on the host: nothing outside a query's count is written
-        std::vector<unc_seg_info_t> hinfo(n_queries);
-        std::vector<unc_segment_t> hseg((size_t)seg_off[n_queries]);
-        HIPCHK(hipMemcpyAsync(hinfo.data(), d_seginfo.p, (size_t)n_queries * sizeof(unc_seg_info_t), hipMemcpyDeviceToHost, st));
-        if (!hseg.empty()) HIPCHK(hipMemcpyAsync(hseg.data(), d_seg.p, hseg.size() * sizeof(unc_segment_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+
+    // the DTW's rounds (with segments: k_align_segments on each), their times, and the results of the queries that were in one
+    int run_dtw() {
+        if (int rc = dtw_run_device(device, n_queries, d_levels.p, d_kmers, jobs.data(), skip.data(), &prm, O.band, workspace_bytes, dres.data(),
+                                    path, path_off, st, want_seg ? &hook : nullptr))
+            return rc;
+        (void)unc_dtw_last_timing(&g_align_ms[3], nullptr, nullptr);
+        for (size_t i = 0; i + 1 < hook.ev.e.size(); i += 2) {       // (g_seg_ms is 0 since check_and_lay_out)
+            float t = 0;
+            HIPCHK(hook.ev.elapsed(i, i + 1, &t));
+            g_seg_ms += t;
+        }
         for (uint32_t q = 0; q < n_queries; ++q) {
-            const uint32_t s = results[q].status;
-            unc_seg_info_t inf = hinfo[q];
-            // (a query that was in no round, or whose path has no start, has no rows: its record on the device may never have been written)
-            if (skip[q] || (s != UNC_DTW_OK && s != UNC_DTW_PATH_TRUNCATED)) { inf.row_first = 0; inf.n_rows = 0; inf.status = UNC_SEG_NONE; inf.pad = 0; }
-            if (!segs->seg && inf.status == UNC_SEG_TRUNCATED) inf.status = UNC_SEG_OK;       // (no records were asked for: none is missing)
-            if (segs->info) segs->info[q] = inf;
-            if (segs->seg) {
-                const uint64_t got = std::min<uint64_t>(inf.n_rows, seg_off[q + 1] - seg_off[q]);
-                memcpy(segs->seg + segs->seg_off[q], hseg.data() + seg_off[q], got * sizeof(unc_segment_t));
+            if (skip[q]) continue;
+            results[q].dtw = dres[q];
+            results[q].status = dres[q].status;
+        }
+        return UNC_OK;
+    }
+
+    // ---- the outputs on request: one copy of a whole device array each, dealt out per query on the host (deal_out, unc_host_util.h),
+    // so that nothing outside a query's count is written
+    int hand_over() {
+        if (want_seg) {     // the rows' counts first, then the records by them
+            std::vector<unc_seg_info_t> info;
+            HIPCHK(download(info, d_seginfo.p, n_queries, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (uint32_t q = 0; q < n_queries; ++q) {
+                const uint32_t s = results[q].status;
+                unc_seg_info_t &inf = info[q];
+                // (a query that was in no round, or whose path has no start, has no rows: its record on the device may never have been written)
+                if (skip[q] || (s != UNC_DTW_OK && s != UNC_DTW_PATH_TRUNCATED)) { inf.row_first = 0; inf.n_rows = 0; inf.status = UNC_SEG_NONE; inf.pad = 0; }
+                if (!segs->seg && inf.status == UNC_SEG_TRUNCATED) inf.status = UNC_SEG_OK;       // (no records were asked for: none is missing)
+                if (segs->info) segs->info[q] = inf;
+            }
+            if (segs->seg)
+                HIPCHK(deal_out(d_seg.p, (size_t)seg_off[n_queries], st, n_queries,
+                                [&](uint32_t q) { return std::min<uint64_t>(info[q].n_rows, seg_off[q + 1] - seg_off[q]); },
+                                [&](uint32_t q) { return seg_off[q]; }, [&](uint32_t q) { return segs->seg + segs->seg_off[q]; }));
+        }
+        if (want_tap) {     // the tap: the columns as events.  It transforms what it copies, so the loop is its own
+            std::vector<unc_event_t> hev;
+            std::vector<uint32_t> hce;
+            std::vector<float> hsm;
+            if (raw_mode) HIPCHK(download(hsm, d_means.p, (size_t)n_cols, st));
+            else {
+                HIPCHK(download(hev, d_events.p, (size_t)n_cols, st));
+                HIPCHK(download(hce, d_col_evt.p, (size_t)n_cols, st));
+            }
+            HIPCHK(hipStreamSynchronize(st));
+            for (uint32_t q = 0; q < n_queries; ++q) {
+                const uint64_t got = std::min<uint64_t>(results[q].n_kept, segs->evt_off[q + 1] - segs->evt_off[q]);
+                unc_event_t *out = segs->events + segs->evt_off[q];
+                for (uint64_t c = 0; c < got; ++c) {
+                    if (raw_mode) out[c] = unc_event_t{hsm[hq[q].col_off + c], 0.0f, (uint32_t)c, 1u};
+                    else out[c] = hev[hq[q].col_off + hce[hq[q].col_off + c]];
+                }
             }
         }
+        if (levels)         // the tap: the columns the DTW read
+            HIPCHK(deal_out(d_levels.p, (size_t)n_cols, st, n_queries,
+                            [&](uint32_t q) { return std::min<uint64_t>(results[q].n_kept, lev_off[q + 1] - lev_off[q]); },
+                            [&](uint32_t q) { return hq[q].col_off; }, [&](uint32_t q) { return levels + lev_off[q]; }));
+        return UNC_OK;
     }
-    if (want_tap) {     // the tap: the columns as events, one copy of all of them, dealt out on the host
-        std::vector<unc_event_t> hev(raw_mode ? 0 : (size_t)n_cols);
-        std::vector<uint32_t> hce(raw_mode ? 0 : (size_t)n_cols);
-        std::vector<float> hsm(raw_mode ? (size_t)n_cols : 0);
-        if (raw_mode) HIPCHK(hipMemcpyAsync(hsm.data(), d_means.p, (size_t)n_cols * sizeof(float), hipMemcpyDeviceToHost, st));
-        else {
-            HIPCHK(hipMemcpyAsync(hev.data(), d_events.p, (size_t)n_cols * sizeof(unc_event_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(hce.data(), d_col_evt.p, (size_t)n_cols * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        for (uint32_t q = 0; q < n_queries; ++q) {
-            const uint64_t got = std::min<uint64_t>(results[q].n_kept, segs->evt_off[q + 1] - segs->evt_off[q]);
-            unc_event_t *out = segs->events + segs->evt_off[q];
-            for (uint64_t c = 0; c < got; ++c) {
-                if (raw_mode) out[c] = unc_event_t{hsm[hq[q].col_off + c], 0.0f, (uint32_t)c, 1u};
-                else out[c] = hev[hq[q].col_off + hce[hq[q].col_off + c]];
-            }
-        }
-    }
-    if (levels) {       // the tap: one copy of all levels, dealt out on the host
-        std::vector<float> h((size_t)n_cols);
-        HIPCHK(hipMemcpyAsync(h.data(), d_levels.p, (size_t)n_cols * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (uint32_t q = 0; q < n_queries; ++q) {
-            const uint64_t got = std::min<uint64_t>(results[q].n_kept, lev_off[q + 1] - lev_off[q]);
-            memcpy(levels + lev_off[q], h.data() + hq[q].col_off, got * sizeof(float));
-        }
-    }
-    return UNC_OK;
+};
+}  // namespace
+
+// The pipeline, from the arguments' checks to the results.  The queries' rows are `rows`' business (align_dev.h).
+int unc::align_run(const AlignCall &c, AlignRows &rows) {
+    AlignRun s(c, rows);
+    if (int rc = s.check_and_lay_out()) return rc;
+    if (c.n_queries == 0) return UNC_OK;
+    if (int rc = s.upload()) return rc;
+    if (int rc = s.run_stages()) return rc;
+    if (int rc = s.read_back()) return rc;
+    s.plan_dtw();
+    if (int rc = s.want_seg ? s.set_up_segments() : UNC_OK) return rc;
+    if (int rc = s.run_dtw()) return rc;
+    return s.hand_over();
 }
 
 // ------------------------------------------------------------------ unc_align_batch: the caller's k-mers, uploaded
@@ -380,10 +410,11 @@ extern "C" int unc_align_batch(int device, const unc_params_t *params, const unc
                                const unc_align_query_t *queries, const uint16_t *kmers, const uint64_t *km_off, uint64_t workspace_bytes,
                                unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path, const uint64_t *path_off,
                                void *stream) {
-    if (!raw || !offsets || !calib || !queries || !kmers || !km_off || !results) return fail(UNC_ERR_ARG, "unc_align_batch: null argument");
+    const AlignCall c{"unc_align_batch", device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, workspace_bytes,
+                      results, levels, lev_off, path, path_off, stream, nullptr};
+    if (!raw || !offsets || !calib || !queries || !kmers || !km_off || !results) return fail(UNC_ERR_ARG, "%s: null argument", c.who);
     UploadedRows rows(kmers, km_off, n_queries);
-    return align_run("unc_align_batch", device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, rows, workspace_bytes,
-                     results, levels, lev_off, path, path_off, stream);
+    return align_run(c, rows);
 }
 
 extern "C" int unc_align_segments_batch(int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
@@ -391,11 +422,11 @@ extern "C" int unc_align_segments_batch(int device, const unc_params_t *params, 
                                         const unc_align_query_t *queries, const uint16_t *kmers, const uint64_t *km_off, uint64_t workspace_bytes,
                                         unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path,
                                         const uint64_t *path_off, const unc_align_segments_t *out, void *stream) {
-    if (!raw || !offsets || !calib || !queries || !kmers || !km_off || !results || !out)
-        return fail(UNC_ERR_ARG, "unc_align_segments_batch: null argument");
+    const AlignCall c{"unc_align_segments_batch", device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries,
+                      workspace_bytes, results, levels, lev_off, path, path_off, stream, out};
+    if (!raw || !offsets || !calib || !queries || !kmers || !km_off || !results || !out) return fail(UNC_ERR_ARG, "%s: null argument", c.who);
     UploadedRows rows(kmers, km_off, n_queries);
-    return align_run("unc_align_segments_batch", device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, rows,
-                     workspace_bytes, results, levels, lev_off, path, path_off, stream, out);
+    return align_run(c, rows);
 }
 
 // unc_align_ref_batch and the packed reference: unc_refseq.cpp and k_refseq.hip are compiled as part of this translation unit, so that

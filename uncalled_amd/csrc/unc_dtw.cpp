@@ -76,13 +76,6 @@ extern "C" int unc_dtw_last_timing(float *ms_kernel, uint32_t *rounds, uint64_t 
     return UNC_OK;
 }
 
-namespace {
-struct HipEvent {       // (timing only)
-    hipEvent_t e = nullptr;
-    ~HipEvent() { if (e) (void)hipEventDestroy(e); }
-};
-}  // namespace
-
 // The queue, the rounds and the launches over columns and k-mers that lie in device memory already (dtw_dev.h).
 int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
                         const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
@@ -130,8 +123,8 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
-    HipEvent t0, t1;
-    HIPCHK(hipEventCreate(&t0.e)); HIPCHK(hipEventCreate(&t1.e));
+    DevEvents ev;       // (timing only) around a round's kernel
+    HIPCHK(ev.create(2));
 
     std::vector<DtwJob> round;
     std::vector<uint32_t> caller_cap;       // (with a hook: what the caller's room holds of each of the round's paths)
@@ -164,10 +157,10 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
         b.subseq = prm->subseq; b.band = band; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
         b.crumbs = d_crumbs.p; b.lines = d_lines.p; b.path = dev_path ? d_path.p : nullptr; b.res = d_res.p; b.next = d_next.p;
         const uint32_t grid = std::min<uint32_t>(nr, (uint32_t)n_cu * 16u);
-        HIPCHK(hipEventRecord(t0.e, st));
+        HIPCHK(ev.record(0, st));
         launch_dtw(b, prm->cost, grid, st);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(t1.e, st));
+        HIPCHK(ev.record(1, st));
         if (hook)
             if (int rc = hook->round(d_jobs.p, nr, d_path.p, d_res.p, st)) return rc;
         h_res.resize(n);
@@ -177,7 +170,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
         if (path && pairs) HIPCHK(hipMemcpyAsync(h_path.data(), d_path.p, 2 * pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, t0.e, t1.e));
+        HIPCHK(ev.elapsed(0, 1, &ms));
         g_last_ms += ms;
         g_last_rounds += 1;
         g_last_crumb_bytes = std::max<uint64_t>(g_last_crumb_bytes, w * 4);

@@ -1,8 +1,13 @@
-// Host-side helpers shared by the translation units behind the C ABI (unc_host.cpp, unc_dtw.cpp): the error message of the calling
-// thread and the one owner of device memory.
+// Host-side helpers shared by the translation units behind the C ABI (unc_host.cpp, unc_dtw.cpp, unc_align.cpp with unc_refseq.cpp):
+// the error message of the calling thread, the one owner of device memory, the one owner of timing events and the hand-over of a
+// per-query output to the host.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
 
 #include "../../include/uncalled_hip.h"
 
@@ -50,3 +55,38 @@ template <class T> struct DevBuf {
     // allocates again
     hipError_t reserve(size_t n, size_t slack = 0) { return n <= cap ? hipSuccess : alloc(n, slack); }
 };
+
+// The one owner of timing events outside unc_host.cpp.  create(n) makes events until there are n: a fixed set is made once, a growing
+// one as it grows.  The hipError_t of every member goes through HIPCHK at the call, as DevBuf's do.
+struct DevEvents {
+    std::vector<hipEvent_t> e;
+    DevEvents() = default;
+    DevEvents(const DevEvents &) = delete;
+    DevEvents &operator=(const DevEvents &) = delete;
+    ~DevEvents() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
+    hipError_t create(size_t n) {
+        for (hipEvent_t x = nullptr; e.size() < n; e.push_back(x))
+            if (hipError_t rc = hipEventCreate(&x)) return rc;
+        return hipSuccess;
+    }
+    hipError_t record(size_t i, hipStream_t st) { return hipEventRecord(e[i], st); }
+    // milliseconds from event i to event j, once the stream has been waited for
+    hipError_t elapsed(size_t i, size_t j, float *ms) { return hipEventElapsedTime(ms, e[i], e[j]); }
+};
+
+// n elements of a device array into h, queued on the stream and not waited for
+template <class T> hipError_t download(std::vector<T> &h, const T *d, size_t n, hipStream_t st) {
+    h.resize(n);
+    return n ? hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+// The hand-over of a per-query output: one copy of the whole device array, waited for, then count(q) elements from element src(q)
+// of it to dst(q) for every query.  Nothing outside a query's count is written
+template <class T, class Count, class Src, class Dst>
+hipError_t deal_out(const T *d, size_t n, hipStream_t st, uint32_t n_queries, Count count, Src src, Dst dst) {
+    std::vector<T> h;
+    if (hipError_t rc = download(h, d, n, st)) return rc;
+    if (hipError_t rc = hipStreamSynchronize(st)) return rc;
+    for (uint32_t q = 0; q < n_queries; ++q) memcpy(dst(q), h.data() + src(q), (size_t)count(q) * sizeof(T));
+    return hipSuccess;
+}

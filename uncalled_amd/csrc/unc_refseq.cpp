@@ -1,6 +1,7 @@
 // Host side of the packed reference (include/uncalled_hip.h: unc_refseq_*, unc_align_ref_batch): BwaIndex::load_pacseq
 // (bwa_index.hpp) once per run, the checks of a batch of stretches, their cut into runs for k_ref_kmers (k_refseq.hip) and
-// unc_align_ref_batch, the second caller of align_run (unc_align.cpp).  Compiled as part of unc_align.cpp, which includes this file.
+// unc_align_ref_batch, the second caller of align_run (unc_align.cpp): the call's record (AlignCall, align_dev.h) as unc_align_batch
+// fills it, and rows that k_ref_kmers makes from coordinates.  Compiled as part of unc_align.cpp, which includes this file.
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
@@ -106,11 +107,6 @@ void cut_runs(std::vector<RefKmerRun> &runs, uint64_t base, uint64_t n, bool fwd
         lo = hi;
     }
 }
-
-struct RefEvents {       // (timing only)
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~RefEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
 }  // namespace
 
 extern "C" int unc_refseq_kmers_batch(const unc_refseq_t *rs, uint32_t n, const unc_ref_stretch_t *stretches, uint16_t *out,
@@ -142,11 +138,9 @@ extern "C" int unc_refseq_kmers_batch(const unc_refseq_t *rs, uint32_t n, const 
     HIPCHK(hipMemcpyAsync(d_runs.p, runs.data(), runs.size() * sizeof(RefKmerRun), hipMemcpyHostToDevice, st));
     launch_ref_kmers(rs->d_pac.p, d_runs.p, (uint32_t)runs.size(), d_out.p, rs->max_blocks, st);
     HIPCHK(hipGetLastError());
-    std::vector<uint16_t> h((size_t)total);
-    HIPCHK(hipMemcpyAsync(h.data(), d_out.p, (size_t)total * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (uint32_t a = 0; a < n; ++a)      // (what lies between the stretches on the device was never written: only the counts are dealt out)
-        memcpy(out + out_off[a], h.data() + (out_off[a] - out_off[0]), (size_t)count[a] * sizeof(uint16_t));
+    // (what lies between the stretches on the device was never written: only the counts are dealt out)
+    HIPCHK(deal_out(d_out.p, (size_t)total, st, n, [&](uint32_t a) { return count[a]; }, [&](uint32_t a) { return out_off[a] - out_off[0]; },
+                    [&](uint32_t a) { return out + out_off[a]; }));
     return UNC_OK;
 }
 
@@ -162,8 +156,7 @@ struct GeneratedRows : AlignRows {
     uint64_t total = 0;
     DevBuf<uint16_t> d_kmers;
     DevBuf<RefKmerRun> d_runs;
-    RefEvents ev;
-    bool queued = false;
+    DevEvents ev;                        // (timing only) around k_ref_kmers
     GeneratedRows(const unc_refseq *r, const unc_ref_stretch_t *s, const uint64_t *off) : rs(r), stretches(s), kmers_off(off) {}
     int rows(uint32_t q, uint64_t *where, uint32_t *n) override {
         static const char *who = "unc_align_ref_batch";
@@ -188,42 +181,31 @@ struct GeneratedRows : AlignRows {
     }
     int queue(hipStream_t st, const uint16_t **out) override {
         HIPCHK(d_kmers.alloc(total)); HIPCHK(d_runs.alloc(runs.size()));
-        for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+        HIPCHK(ev.create(2));
         HIPCHK(hipMemcpyAsync(d_runs.p, runs.data(), runs.size() * sizeof(RefKmerRun), hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(ev.e[0], st));
+        HIPCHK(ev.record(0, st));
         launch_ref_kmers(rs->d_pac.p, d_runs.p, (uint32_t)runs.size(), d_kmers.p, rs->max_blocks, st);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.e[1], st));
-        queued = true;
+        HIPCHK(ev.record(1, st));
         *out = d_kmers.p;
         return UNC_OK;
     }
 };
 }  // namespace
 
-// unc_align_ref_batch, and with segs unc_align_ref_segments_batch
-static int align_ref(const char *who, const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
-                     const int16_t *raw, const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
-                     const unc_align_query_t *queries, const unc_ref_stretch_t *stretches, uint64_t workspace_bytes,
-                     unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint16_t *kmers_out, const uint64_t *kmers_off,
-                     uint32_t *path, const uint64_t *path_off, void *stream, const unc_align_segments_t *segs) {
-    if (!rs || !stretches) return fail(UNC_ERR_ARG, "%s: null argument", who);
-    if (kmers_out && !kmers_off) return fail(UNC_ERR_ARG, "%s: kmers_out without kmers_off", who);
+// unc_align_ref_batch, and with c.segs unc_align_ref_segments_batch: the call's record, and what is this route's own
+static int align_ref(AlignCall c, const unc_refseq_t *rs, const unc_ref_stretch_t *stretches, uint16_t *kmers_out, const uint64_t *kmers_off) {
+    if (!rs || !stretches) return fail(UNC_ERR_ARG, "%s: null argument", c.who);
+    if (kmers_out && !kmers_off) return fail(UNC_ERR_ARG, "%s: kmers_out without kmers_off", c.who);
     g_ref_kmers_ms = 0;
+    c.device = rs->device;
     GeneratedRows rows(rs, stretches, kmers_out ? kmers_off : nullptr);
-    if (int rc = align_run(who, rs->device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, rows, workspace_bytes,
-                           results, levels, lev_off, path, path_off, stream, segs))
-        return rc;
-    if (!rows.queued) return UNC_OK;         // (no queries)
-    HIPCHK(hipEventElapsedTime(&g_ref_kmers_ms, rows.ev.e[0], rows.ev.e[1]));       // (align_run has waited for the stream)
-    if (kmers_out) {         // the tap: one copy of all rows, dealt out on the host
-        hipStream_t st = (hipStream_t)stream;
-        std::vector<uint16_t> h((size_t)rows.total);
-        HIPCHK(hipMemcpyAsync(h.data(), rows.d_kmers.p, (size_t)rows.total * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (uint32_t q = 0; q < n_queries; ++q)
-            memcpy(kmers_out + kmers_off[q], h.data() + rows.at[q], (size_t)rows.count[q] * sizeof(uint16_t));
-    }
+    if (int rc = align_run(c, rows)) return rc;
+    if (rows.ev.e.empty()) return UNC_OK;    // (no queries: nothing was queued)
+    HIPCHK(rows.ev.elapsed(0, 1, &g_ref_kmers_ms));       // (align_run has waited for the stream)
+    if (kmers_out)           // the tap: the rows as they lie on the device, dealt out on the host
+        HIPCHK(deal_out(rows.d_kmers.p, (size_t)rows.total, (hipStream_t)c.stream, c.n_queries, [&](uint32_t q) { return rows.count[q]; },
+                        [&](uint32_t q) { return rows.at[q]; }, [&](uint32_t q) { return kmers_out + kmers_off[q]; }));
     return UNC_OK;
 }
 
@@ -232,8 +214,10 @@ extern "C" int unc_align_ref_batch(const unc_refseq_t *rs, const unc_params_t *p
                                    const unc_align_query_t *queries, const unc_ref_stretch_t *stretches, uint64_t workspace_bytes,
                                    unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint16_t *kmers_out,
                                    const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off, void *stream) {
-    return align_ref("unc_align_ref_batch", rs, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, stretches,
-                     workspace_bytes, results, levels, lev_off, kmers_out, kmers_off, path, path_off, stream, nullptr);
+    // (the device is the reference's: align_ref sets it once rs is known not to be null)
+    const AlignCall c{"unc_align_ref_batch", 0, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, workspace_bytes,
+                      results, levels, lev_off, path, path_off, stream, nullptr};
+    return align_ref(c, rs, stretches, kmers_out, kmers_off);
 }
 
 extern "C" int unc_align_ref_segments_batch(const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
@@ -242,7 +226,8 @@ extern "C" int unc_align_ref_segments_batch(const unc_refseq_t *rs, const unc_pa
                                             uint64_t workspace_bytes, unc_align_result_t *results, float *levels, const uint64_t *lev_off,
                                             uint16_t *kmers_out, const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off,
                                             const unc_align_segments_t *out, void *stream) {
-    if (!out) return fail(UNC_ERR_ARG, "unc_align_ref_segments_batch: null argument");
-    return align_ref("unc_align_ref_segments_batch", rs, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, stretches,
-                     workspace_bytes, results, levels, lev_off, kmers_out, kmers_off, path, path_off, stream, out);
+    const AlignCall c{"unc_align_ref_segments_batch", 0, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries,
+                      workspace_bytes, results, levels, lev_off, path, path_off, stream, out};
+    if (!out) return fail(UNC_ERR_ARG, "%s: null argument", c.who);
+    return align_ref(c, rs, stretches, kmers_out, kmers_off);
 }
