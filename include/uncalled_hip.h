@@ -143,6 +143,10 @@ void unc_params_default(unc_params_t *p);
  * Parses <prefix>.{bwt,sa,ann,amb,uncl} on the host and uploads BWT/Occ blocks, sampled SA, k-mer
  * ranges, thresholds and the 1024x3 model table to HBM of `device`. */
 int unc_index_load(const char *bwa_prefix, const char *idx_preset, int device, unc_index_t **out);
+/* the same with UNC_INDEX_* flags.  UNC_INDEX_NO_DENSE_SA: the dense suffix array (six bytes a row) is not built, SA look-ups walk to the
+ * BWA-sampled rows as bwt_sa does -- for callers that only step through the BWT (unc_mask_external).  Unknown flags: UNC_ERR_ARG. */
+#define UNC_INDEX_NO_DENSE_SA 1u
+int unc_index_load_flags(const char *bwa_prefix, const char *idx_preset, int device, uint32_t flags, unc_index_t **out);
 void unc_index_free(unc_index_t *ix);
 uint64_t unc_index_size(const unc_index_t *ix);                      /* BwaIndex::size, bwa_index.hpp:180-182 */
 int32_t unc_index_n_seqs(const unc_index_t *ix);
@@ -565,6 +569,55 @@ int unc_align_ref_segments_batch(const unc_refseq_t *rs, const unc_params_t *par
  * DTW's rounds; 0 for a call without segments); unc_align_last_timing keeps its four spans, of which [1] is then the event
  * kernel's variant that writes whole Events (create_event, event_detector.cpp:296-319) */
 int unc_align_segments_last_timing(float *ms);
+
+/* ---- repeat masking: replaces masking/mask_internal.sh + masking/mask_kmers.py (jellyfish) and masking/mask_external.sh (bowtie,
+ * bedtools, samtools), which the reference's masking/README.md recommends for references with intergenic eukaryotic DNA.
+ * A reference is one byte per base: 0..3 = A C G T (either case), everything else 4 = "not a base"; a masked base becomes 4.
+ * Contigs are given by n_ctg + 1 ascending offsets from 0 to n.  A window is a run of bases inside one contig without a code >= 4.
+ * A k-mer's code has its first base most significant (bp.hpp).  All results are integers and exact.
+ *
+ * Internal masking (mask_internal.sh:46-54), k in 1..13, iters >= 1; per iteration:
+ *   1. count every window of k bases, forward strand only, overlapping ones included (jellyfish count -m k without -C, :47);
+ *   2. take the k-mer with the largest count (:48-49);
+ *   3. turn every base covered by an occurrence of it into 4 (mask_kmers.py:8-40) -- occurrences are found in the text as it stood
+ *      at the start of the iteration, overlapping ones included (`find(kmer, i + 1)`, mask_kmers.py:27).
+ * Two departures from the scripts:
+ *   - ties for the largest count go to the smallest k-mer code.  The script takes the last line of `jellyfish dump -L max` (:49),
+ *     whose order is that of jellyfish's hash table and not reproducible;
+ *   - the loop ends early, before masking, when the largest count is below 2 (the script would mask an arbitrary k-mer that occurs
+ *     once).  iters_done tells how many iterations masked something.
+ *
+ * External masking (mask_external.sh:59-84), 2 <= min_len <= 65535 (:33), min_copy >= 1 (:38): for every window of min_len bases of the
+ * target (bedtools makewindows -w min_len -s 1, full-length windows only, :61), count = the size of the window's SA interval in a
+ * loaded index = its occurrences in the index's text as BWA stores it: both strands (bowtie -v 0 searches both, :67), random bases where
+ * the FASTA had N.  A window is a repeat iff count > min_copy (`$4 > min_copy`, :77); every base a repeat window covers becomes 4
+ * (bedtools merge / maskfasta, :78-80).  The target's codes are the masker's; the index may be of a larger reference. */
+typedef struct unc_mask unc_mask_t;
+/* uploads the codes (host, n < 2^32 of them: the k-mer counters are 32 bits wide) once.  UNC_ERR_ARG before the device is touched for
+ * n >= 2^32, offsets that descend or do not run from 0 to n, null pointers. */
+int unc_mask_create(int device, const uint8_t *codes, uint64_t n, const uint64_t *ctg_off, uint32_t n_ctg, unc_mask_t **out);
+void unc_mask_free(unc_mask_t *m);
+/* parity tap: step 1 of an iteration on the text as it stands; counts_out (host) receives the 4^k counters.  k outside 1..13: UNC_ERR_ARG */
+int unc_mask_kmer_counts(unc_mask_t *m, uint32_t k, uint32_t *counts_out);
+/* mask_internal.sh:46-54, the whole loop on the device.  kmers_out / occ_out / bases_out (host, `iters` each) receive per iteration
+ * done the k-mer's code, its occurrences (mask_kmers.py:78, "masked %d occurences") and the bases newly masked; *iters_done how many.
+ * The iterations are queued in batches of 32 and the host looks at the reports between batches: a loop that ends early costs at most one
+ * batch of launches that return at once, however large iters is.  k outside 1..13 or iters == 0: UNC_ERR_ARG before the device is
+ * touched. */
+int unc_mask_internal(unc_mask_t *m, uint32_t k, uint32_t iters, uint32_t *kmers_out, uint32_t *occ_out, uint32_t *bases_out,
+                      uint32_t *iters_done);
+/* mask_external.sh:59-84 against `ix`, which must be on the masker's device.  counts_out (host, may be NULL): the count of the window
+ * that starts at every position, 0 where there is no window; with it every look-up runs to its end, without it a look-up stops once its
+ * interval holds no more than min_copy rows (intervals only shrink): the masks are the same.  *bases_masked: bases newly masked
+ * (mask_external.sh:82-84 where the target held no N inside a repeat).  min_len outside 2..65535 or min_copy == 0: UNC_ERR_ARG before
+ * the device is touched. */
+int unc_mask_external(unc_mask_t *m, const unc_index_t *ix, uint32_t min_len, uint32_t min_copy, uint64_t *counts_out,
+                      uint64_t *bases_masked);
+/* the codes as they stand, n bytes to out (host) */
+int unc_mask_codes(const unc_mask_t *m, uint8_t *out);
+/* kernel milliseconds of the calling thread's last unc_mask_kmer_counts / _internal / _external (HIP events on the stream): counting and
+ * choosing the k-mer, flagging and covering, the FM look-ups */
+int unc_mask_last_timing(float *ms_count, float *ms_cover, float *ms_fm);
 
 /* ---- measurement aid: `reps` launches that write, then `reps` that read, n_records (made odd) scattered 64-byte records with
  * one lane per record and four 16-byte accesses per lane -- k_map's access shape with an exactly known byte count, for

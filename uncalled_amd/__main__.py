@@ -1,4 +1,4 @@
-"""`python -m uncalled_amd {index,map,sim,dtw,pafstats}` -- the subcommands of the reference's `scripts/uncalled` that do not need
+"""`python -m uncalled_amd {index,map,sim,dtw,mask,pafstats}` -- the subcommands of the reference's `scripts/uncalled` that do not need
 a sequencer (index_cmd :38-78, map_cmd :126-167, realtime_cmd :170-256 fed from fast5 files, pafstats) with the same options (uncalled/args.py:90-124,244-304) on the GPU path.
 """
 import argparse
@@ -576,6 +576,14 @@ def get_parser():
     p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
 
+    p = sp.add_parser("mask", help="Mask repeats of a FASTA reference before indexing it (the reference's masking/ scripts, on the GPU)",
+                      description="`mask internal` masks the most frequent k-mer of the reference, ITERS times over (mask_internal.sh and "
+                      "mask_kmers.py); ties go to the k-mer that sorts first, and the run ends early once no k-mer occurs twice. `mask external` "
+                      "masks every stretch of the target whose windows of MIN_LEN bases occur more than MIN_COPY times in an index, both strands "
+                      "counted (mask_external.sh).")
+    from . import mask
+    mask.add_opts(p)
+
     p = sp.add_parser("pafstats", help="Computes speed and accuracy of UNCALLED mappings")
     pafstats.add_opts(p)
     return ap
@@ -591,6 +599,9 @@ def main(argv=None):
         sim_cmd(args)
     elif args.subcmd == "dtw":
         dtw_cmd(args)
+    elif args.subcmd == "mask":
+        from . import mask
+        mask.run(args)
     else:
         from . import pafstats
         pafstats.run(args)

@@ -14,6 +14,7 @@ HERE = Path(__file__).resolve().parent
 DEFAULT_LIB = HERE / "libuncalled_hip.so"
 
 UNC_OK = 0
+INDEX_NO_DENSE_SA = 1
 UNC_ERR_OVERFLOW = -5
 
 
@@ -186,6 +187,8 @@ def load(path=None):
     L.unc_host_free.argtypes = [vp]; L.unc_host_free.restype = None
     L.unc_params_default.argtypes = [C.POINTER(Params)]
     L.unc_index_load.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp)]
+    if hasattr(L, "unc_index_load_flags"):
+        L.unc_index_load_flags.argtypes = [C.c_char_p, C.c_char_p, C.c_int, u32, C.POINTER(vp)]
     L.unc_index_free.argtypes = [vp]
     L.unc_index_size.argtypes = [vp]; L.unc_index_size.restype = u64
     L.unc_index_n_seqs.argtypes = [vp]; L.unc_index_n_seqs.restype = i32
@@ -274,6 +277,14 @@ def load(path=None):
         L.unc_align_ref_last_timing.argtypes = [C.POINTER(C.c_float)]
         if hasattr(L, "unc_align_ref_segments_batch"):
             L.unc_align_ref_segments_batch.argtypes = L.unc_align_ref_batch.argtypes[:-1] + [C.POINTER(AlignSegments), vp]
+    if hasattr(L, "unc_mask_create"):                 # (the emulator builds of the other features do not hold the masking entry points)
+        L.unc_mask_create.argtypes = [C.c_int, vp, u64, vp, u32, C.POINTER(vp)]
+        L.unc_mask_free.argtypes = [vp]; L.unc_mask_free.restype = None
+        L.unc_mask_kmer_counts.argtypes = [vp, u32, vp]
+        L.unc_mask_internal.argtypes = [vp, u32, u32, vp, vp, vp, C.POINTER(u32)]
+        L.unc_mask_external.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u64)]
+        L.unc_mask_codes.argtypes = [vp, vp]
+        L.unc_mask_last_timing.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     _libs[key] = L
     return L
 
@@ -293,10 +304,14 @@ def default_params(lib=None):
 class Index:
     """Device-resident FM index + thresholds + pore model (Mapper::load_static, mapper.cpp:109-159)."""
 
-    def __init__(self, prefix, preset="default", device=0, lib=None):
+    def __init__(self, prefix, preset="default", device=0, lib=None, dense_sa=True):
+        """dense_sa=False: without the dense suffix array (UNC_INDEX_NO_DENSE_SA), for callers that only step through the BWT"""
         self.L = lib or load()
         h = C.c_void_p()
-        _check(self.L, self.L.unc_index_load(str(prefix).encode(), preset.encode(), device, C.byref(h)))
+        if dense_sa:
+            _check(self.L, self.L.unc_index_load(str(prefix).encode(), preset.encode(), device, C.byref(h)))
+        else:
+            _check(self.L, self.L.unc_index_load_flags(str(prefix).encode(), preset.encode(), device, INDEX_NO_DENSE_SA, C.byref(h)))
         self.h = h
         self.size = self.L.unc_index_size(h)
 
@@ -600,6 +615,74 @@ class RefSeq:
 
     def device_bytes(self):
         return self.L.unc_refseq_device_bytes(self.h)
+
+
+class Masker:
+    """unc_mask_t: a reference as one code per base (0..3 = ACGT, 4 = not a base) with its contig offsets, resident on the GPU, and
+    the two masking recipes of the reference's masking/ directory run on it in place (include/uncalled_hip.h).  A context manager:
+
+        with capi.Masker(codes, offsets) as m:
+            report = m.internal(10, 30)
+            masked = m.codes()
+    """
+
+    def __init__(self, codes, ctg_off, device=0, lib=None):
+        self.L = lib or load()
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        off = np.ascontiguousarray(ctg_off, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError("the contig offsets hold at least the 0 they start from")
+        self.n = int(codes.size)
+        h = C.c_void_p()
+        _check(self.L, self.L.unc_mask_create(device, codes.ctypes.data, self.n, off.ctypes.data, off.size - 1, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.unc_mask_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def kmer_counts(self, k):
+        """the count of every k-mer's windows in the text as it stands -> uint32[4^k] (UncalledHipError for k outside 1..13)"""
+        out = np.zeros(4 ** k if 1 <= k <= 13 else 1, dtype=np.uint32)
+        _check(self.L, self.L.unc_mask_kmer_counts(self.h, k, out.ctypes.data))
+        return out
+
+    def internal(self, k, iters):
+        """mask_internal.sh: -> [(k-mer code, occurrences, bases newly masked)] per iteration done (fewer than iters when no k-mer
+        is left that occurs twice)"""
+        room = max(1, int(iters))
+        km, occ, bases = (np.zeros(room, dtype=np.uint32) for _ in range(3))
+        done = C.c_uint32()
+        _check(self.L, self.L.unc_mask_internal(self.h, k, iters, km.ctypes.data, occ.ctypes.data, bases.ctypes.data, C.byref(done)))
+        return [(int(km[i]), int(occ[i]), int(bases[i])) for i in range(done.value)]
+
+    def external(self, index, min_len, min_copy, counts=False):
+        """mask_external.sh against a loaded capi.Index on the same device -> bases newly masked, and with counts=True the count of
+        the window that starts at every position (uint64, 0 where there is none) as well"""
+        tap = np.zeros(max(1, self.n), dtype=np.uint64) if counts else None
+        masked = C.c_uint64()
+        _check(self.L, self.L.unc_mask_external(self.h, index.h, min_len, min_copy, tap.ctypes.data if counts else None, C.byref(masked)))
+        return (masked.value, tap[:self.n]) if counts else masked.value
+
+    def codes(self):
+        out = np.empty(max(1, self.n), dtype=np.uint8)
+        _check(self.L, self.L.unc_mask_codes(self.h, out.ctypes.data))
+        return out[:self.n]
+
+    def last_timing(self):
+        """kernel milliseconds of the calling thread's last call: (counting and choosing, flagging and covering, FM look-ups)"""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        self.L.unc_mask_last_timing(C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
 
 
 def _stretches(stretches):

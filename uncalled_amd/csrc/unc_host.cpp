@@ -214,6 +214,11 @@ struct PlacementSpacer {
 };
 
 extern "C" int unc_index_load(const char *bwa_prefix, const char *idx_preset, int device, unc_index_t **out) {
+    return unc_index_load_flags(bwa_prefix, idx_preset, device, 0u, out);
+}
+
+extern "C" int unc_index_load_flags(const char *bwa_prefix, const char *idx_preset, int device, uint32_t flags, unc_index_t **out) {
+    if (flags & ~UNC_INDEX_NO_DENSE_SA) return fail(UNC_ERR_ARG, "unc_index_load_flags: unknown flags %#x", flags);
     if (!bwa_prefix || !out) return fail(UNC_ERR_ARG, "null argument");
     *out = nullptr;
     std::string prefix(bwa_prefix);
@@ -290,7 +295,7 @@ extern "C" int unc_index_load(const char *bwa_prefix, const char *idx_preset, in
         (void)hipMemGetInfo(&free_b, &total_b);
         free_b += spacer.bytes;
         const size_t need = ((n + 2) / 2) * 12 + 16;      // rows 0 .. n in pairs (12 bytes) + the word a load reads past the last entry
-        if (!(env && env[0] == '0') && need < free_b / 2) {
+        if (!(env && env[0] == '0') && !(flags & UNC_INDEX_NO_DENSE_SA) && need < free_b / 2) {
             HIPCHK(ix->d_sa_dense.alloc(need));
             uint64_t *const dense = reinterpret_cast<uint64_t *>(ix->d_sa_dense.p);
             launch_dense_sa(d, dense, nullptr);
@@ -398,6 +403,7 @@ extern "C" uint64_t unc_index_seq_len(const unc_index_t *ix, int32_t rid) {
 }
 extern "C" uint64_t unc_index_device_bytes(const unc_index_t *ix) { return ix->device_bytes; }
 int unc::index_device(const unc_index_t *ix) { return ix->device; }
+const unc::DevIndex &unc::index_dev(const unc_index_t *ix) { return ix->dev; }
 
 // bns_pos2rid behind BwaIndex::translate_loc, bwa_index.hpp:213-220
 extern "C" uint64_t unc_index_translate_loc(const unc_index_t *ix, uint64_t sa_loc, int32_t *rid, uint64_t *ref_loc) {

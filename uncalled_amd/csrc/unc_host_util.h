@@ -1,4 +1,4 @@
-// Host-side helpers shared by the translation units behind the C ABI (unc_host.cpp, unc_dtw.cpp, unc_align.cpp with unc_refseq.cpp):
+// Host-side helpers shared by the translation units behind the C ABI (unc_host.cpp, unc_dtw.cpp, unc_align.cpp with unc_refseq.cpp, unc_mask.cpp):
 // the error message of the calling thread, the one owner of device memory, the one owner of timing events and the hand-over of a
 // per-query output to the host.
 #pragma once
@@ -16,6 +16,9 @@ namespace unc {
 int fail(int code, const char *fmt, ...);
 // the HIP device an index was loaded to (defined in unc_host.cpp, which owns the struct)
 int index_device(const unc_index_t *ix);
+// what the kernels take of an index: pointers into its device memory, valid while the index lives (unc_dev_types.h)
+struct DevIndex;
+const DevIndex &index_dev(const unc_index_t *ix);
 }  // namespace unc
 
 #define HIPCHK(expr)                                                                                         \
