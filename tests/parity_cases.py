@@ -1455,3 +1455,45 @@ def case_match_probs_levels(lib, oracle_lib, example):
     bad = np.argwhere((got.view(np.uint32) != want.view(np.uint32)) & ~nan)
     assert bad.size == 0, "%d differ; level %r, k-mer %d: %r, oracle %r" % (
         len(bad), levels[bad[0][0]], bad[0][1], got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+# ---------------------------------------------------------------- what the creations allocate, by name
+# unc_*_device_bytes and the geometry of creations whose every size is named (no size taken from the free memory): the values of
+# e40587f (the commit before the creations became plan / allocations / builds) under the emulator; the emulator and the MI355X both give them
+CREATION_INDEX_BYTES = dict(default=173932, bwa_sa=53904, no_fm32=163884)
+CREATION_MAPPERS = (
+    (dict(n_slots=2, n_waves=2, pool_chunks=16), 7946240,
+     dict(n_waves=2, n_slots=2, slice_events=0, pool_chunks=16, max_clusters=1 << 20)),
+    (dict(n_slots=64, n_waves=2, pool_chunks=16, sched_parts=1), 156751488,
+     dict(n_waves=2, n_slots=64, slice_events=1024, pool_chunks=16, max_clusters=1 << 20)),
+    (dict(n_slots=3, n_waves=2, pool_chunks=16, max_clusters=4096, max_seed_paths=512), 8944512,
+     dict(n_waves=2, n_slots=3, slice_events=1024, pool_chunks=16, max_clusters=4096)),
+)
+CREATION_RT_BYTES = 15008436      # one channel, UNC_RT_POOL_CHUNKS=64
+
+
+def case_creation_sizes(lib, example, monkeypatch):
+    for k in ("UNC_DENSE_SA", "UNC_FM32", "UNC_WIDE_KEYS", "UNC_BUCKET_SHIFT", "UNC_RT_POOL_CHUNKS"):
+        monkeypatch.delenv(k, raising=False)
+    got = {}
+    for what, env in FM_LOADS:
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        ix = capi.Index(example["prefix"], lib=lib)
+        got[what] = ix.device_bytes()
+        ix.close()
+        for k in env:
+            monkeypatch.delenv(k)
+    print("index device_bytes:", got)
+    assert got == CREATION_INDEX_BYTES
+    dev_index = _index(lib, example)
+    for kw, want_bytes, want_geometry in CREATION_MAPPERS:
+        m = capi.Mapper(dev_index, **kw)
+        print("mapper", kw, m.device_bytes(), m.geometry())
+        assert (m.device_bytes(), m.geometry()) == (want_bytes, want_geometry), kw
+        m.close()
+    monkeypatch.setenv("UNC_RT_POOL_CHUNKS", "64")
+    rt = capi.Realtime(dev_index, n_channels=1)
+    print("realtime device_bytes:", rt.device_bytes())
+    assert rt.device_bytes() == CREATION_RT_BYTES
+    rt.close()

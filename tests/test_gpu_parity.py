@@ -246,6 +246,12 @@ def test_cluster_pool_pressure(hip_lib, oracle_lib, example, goldens, pool_chunk
     pc.case_cluster_pool_pressure(hip_lib, oracle_lib, example, goldens, pool_chunks, n_waves)
 
 
+def test_creation_sizes(hip_lib, example, monkeypatch):
+    """device_bytes of the three index loads, of three mappers and of a realtime mapper whose sizes are all named, and the mappers'
+    geometry: the constants of parity_cases.py, the same under the emulator and on the GPU."""
+    pc.case_creation_sizes(hip_lib, example, monkeypatch)
+
+
 def test_big_forests(hip_lib, oracle_lib, example, goldens, tmp_path, monkeypatch):
     pc.case_big_forests(hip_lib, oracle_lib, example, goldens, tmp_path, monkeypatch)
 

@@ -178,3 +178,69 @@ def test_chunk_after_a_failed_round_of_the_last_allowed_chunk(sim_lib, example):
     rt.close()
     ix.close()
     assert _live(sim_lib) == start
+
+
+# hipMalloc calls of each creation on the example index, counted by the loop below on e40587f (the commit before the creations
+# became plan / allocations / builds): the order and the number of a creation's allocations decide where its memory lies
+# (DESIGN.md section 5), so a change of either must be meant
+CREATION_ALLOCS = dict(index=10, index_bwa_sa=8, index_no_fm32=8, mapper=5, mapper_sliced=8, realtime=14)
+INDEX_KNOBS = dict(index={}, index_bwa_sa={"UNC_DENSE_SA": "0"}, index_no_fm32={"UNC_FM32": "0"})
+MAPPER_OPTS = dict(mapper=dict(n_slots=2, n_waves=2, pool_chunks=16),
+                   # (sched_parts is named: xcd_count, which swallows a failed allocation and keeps its answer for the process, stays out)
+                   mapper_sliced=dict(n_slots=64, n_waves=2, pool_chunks=16, sched_parts=1))
+
+
+@pytest.mark.parametrize("what", list(CREATION_ALLOCS))
+def test_creation_fails_clean_at_every_allocation(sim_lib, example, monkeypatch, what):
+    """Whichever of a creation's allocations fails, the creation returns UNC_ERR_HIP and gives back what it had allocated; the first k
+    at which it succeeds is one more than its number of allocations, which is the parent commit's.  The object then created maps the
+    example read as one created undisturbed, and when everything is closed no allocation is left."""
+    for k in ("UNC_DENSE_SA", "UNC_FM32", "UNC_WIDE_KEYS", "UNC_BUCKET_SHIFT", "UNC_RT_POOL_CHUNKS"):
+        monkeypatch.delenv(k, raising=False)
+    gc.collect()
+    start = _live(sim_lib)
+    raw, off, cal = _batch(example, 1)
+    base_ix = capi.Index(example["prefix"], lib=sim_lib)
+    want = capi.Mapper(base_ix, n_slots=2, n_waves=2, pool_chunks=16).map_batch(raw, off, cal)
+    assert want[0]["mapped"]
+    want_rt = capi.Realtime(base_ix, n_channels=1).process_chunks(_chunk(example, 1, 1000), raw_i16=example["signal"])
+    gc.collect()
+    for k, v in INDEX_KNOBS.get(what, {}).items():
+        monkeypatch.setenv(k, v)
+
+    def create():
+        if what in INDEX_KNOBS:
+            return capi.Index(example["prefix"], lib=sim_lib)
+        if what in MAPPER_OPTS:
+            return capi.Mapper(base_ix, **MAPPER_OPTS[what])
+        return capi.Realtime(base_ix, n_channels=1)
+
+    before = _live(sim_lib)
+    failed = 0
+    for k in itertools.count(1):
+        assert k < 100
+        _arm(sim_lib, k)
+        try:
+            obj = create()
+            break
+        except capi.UncalledHipError as e:
+            assert str(e).startswith("uncalled_hip error %d:" % UNC_ERR_HIP), (k, e)
+        finally:
+            _arm(sim_lib, 0)
+        failed += 1
+        assert _live(sim_lib) == before, k
+    print(what, "allocations:", failed)
+    assert failed == CREATION_ALLOCS[what]
+
+    if what in INDEX_KNOBS:
+        m = capi.Mapper(obj, n_slots=2, n_waves=2, pool_chunks=16)
+        assert _same(m.map_batch(raw, off, cal), want)
+        m.close()
+    elif what in MAPPER_OPTS:
+        assert _same(obj.map_batch(raw, off, cal), want)
+    else:
+        got = obj.process_chunks(_chunk(example, 1, 1000), raw_i16=example["signal"])
+        assert got[0]["state"] == want_rt[0]["state"] == capi.RT_MAPPING and _same(got[0]["hit"], want_rt[0]["hit"])
+    obj.close()
+    base_ix.close()
+    assert _live(sim_lib) == start

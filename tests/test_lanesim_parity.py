@@ -197,6 +197,12 @@ def test_cluster_pool_pressure(sim_lib, oracle_lib, example, goldens, pool_chunk
     pc.case_cluster_pool_pressure(sim_lib, oracle_lib, example, goldens, pool_chunks, n_waves, n_reads=4)
 
 
+def test_creation_sizes(sim_lib, example, monkeypatch):
+    """device_bytes of the three index loads, of three mappers and of a realtime mapper whose sizes are all named, and the mappers'
+    geometry: the constants of parity_cases.py, the same under the emulator and on the GPU."""
+    pc.case_creation_sizes(sim_lib, example, monkeypatch)
+
+
 def test_big_forests(sim_lib, oracle_lib, example, goldens, tmp_path, monkeypatch):
     pc.case_big_forests(sim_lib, oracle_lib, example, goldens, tmp_path, monkeypatch)
 

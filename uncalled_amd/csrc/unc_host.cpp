@@ -217,177 +217,250 @@ extern "C" int unc_index_load(const char *bwa_prefix, const char *idx_preset, in
     return unc_index_load_flags(bwa_prefix, idx_preset, device, 0u, out);
 }
 
-extern "C" int unc_index_load_flags(const char *bwa_prefix, const char *idx_preset, int device, uint32_t flags, unc_index_t **out) {
-    if (flags & ~UNC_INDEX_NO_DENSE_SA) return fail(UNC_ERR_ARG, "unc_index_load_flags: unknown flags %#x", flags);
-    if (!bwa_prefix || !out) return fail(UNC_ERR_ARG, "null argument");
-    *out = nullptr;
-    std::string prefix(bwa_prefix);
-    unc_index *ix = new unc_index();
-    ix->device = device;
-    struct Guard { unc_index *p; ~Guard() { if (p) unc_index_free(p); } } guard{ix};
+// A creation (index load, mapper, realtime mapper) is a PLAN made once (every size, no HIP call that allocates), then the ALLOCATIONS
+// in a fixed order, then the device-side BUILDS.  The order and sizes of its hipMalloc calls, the spacer's size and lifetime and the
+// points at which free memory is asked for decide where the memory lies (PlacementSpacer); DESIGN.md section 5 lists them per creation.
 
+// The load's knobs, read per call (the tests change them between two loads in one process).
+struct IndexKnobs {
+    bool dense_sa;       // UNC_DENSE_SA=0 or UNC_INDEX_NO_DENSE_SA: the BWA sampling only
+    bool fm32;           // UNC_FM32=0 (tests): no 32-bit rank table, the 64-bit arithmetic on a small reference
+    bool wide_keys;      // UNC_WIDE_KEYS=1: 128-bit sort keys where narrow ones would do
+    long bucket_shift;   // UNC_BUCKET_SHIFT (tests): narrower buckets; 0 = not named
+};
+static IndexKnobs read_index_knobs(uint32_t flags) {
+    const char *dense = getenv("UNC_DENSE_SA"), *fm32 = getenv("UNC_FM32"), *wide = getenv("UNC_WIDE_KEYS"), *shift = getenv("UNC_BUCKET_SHIFT");
+    return IndexKnobs{!(dense && dense[0] == '0') && !(flags & UNC_INDEX_NO_DENSE_SA), !(fm32 && fm32[0] == '0'), wide && wide[0] == '1',
+                      shift ? atol(shift) : 0};
+}
+
+// What the .bwt and .sa headers say and the table sizes that follow from them; the files' bytes until they are uploaded.
+struct IndexPlan {
+    uint64_t n = 0;                  // seq_len = BWT rows - 1
+    size_t n_words = 0;              // u32 words of the .bwt behind its header
+    size_t n_sa = 0, sa_bytes = 0;   // sampled SA entries, sa[0] included
+    size_t bwt_bytes = 0;            // the BWT padded to whole 64-byte blocks, so that block loads of the last (partial) block stay in bounds
+    size_t dense_sa_bytes = 0;       // the ALLOCATION: rows 0 .. n in pairs (12 bytes) + the word a load reads past the last entry
+    size_t fm32_blocks = 0, fm32_bytes = 0;      // 64-symbol blocks of the 32-bit rank table, 32 bytes each
+    size_t spacer_need = 0;          // the spacer's ESTIMATE of all of the above
+    std::vector<char> bwt, sa;
+};
+constexpr size_t N_RANGES = 2 * NKMER, N_MODEL = 3 * NKMER, N_MODEL4 = 4 * NKMER;      // elements of the three small tables
+
+// Reads and checks the index files and fills the plan and the host side of the index.  No HIP call.
+static int plan_index(const char *bwa_prefix, const char *idx_preset, unc_index *ix, IndexPlan &pl) {
+    const std::string prefix(bwa_prefix);
     // .bwt = u64 primary; u64 L2[1..4]; u32 words (Occ counts interleaved every 128 symbols)
-    std::vector<char> bwt;
-    if (!read_file(prefix + ".bwt", bwt) || bwt.size() < 40) return fail(UNC_ERR_IO, "failed to load BWA index: %s.bwt", bwa_prefix);
-    memcpy(&ix->primary, bwt.data(), 8);
-    memcpy(&ix->L2[1], bwt.data() + 8, 32);
-    ix->seq_len = ix->L2[4];
-    const size_t n_words = (bwt.size() - 40) / 4;
-    const uint64_t n = ix->seq_len;
-    if (n_words != (n + 15) / 16 + 8 * ((n + 127) / 128 + 1)) return fail(UNC_ERR_IO, "%s.bwt: size does not match seq_len", bwa_prefix);
+    if (!read_file(prefix + ".bwt", pl.bwt) || pl.bwt.size() < 40) return fail(UNC_ERR_IO, "failed to load BWA index: %s.bwt", bwa_prefix);
+    memcpy(&ix->primary, pl.bwt.data(), 8);
+    memcpy(&ix->L2[1], pl.bwt.data() + 8, 32);
+    const uint64_t n = pl.n = ix->seq_len = ix->L2[4];
+    pl.n_words = (pl.bwt.size() - 40) / 4;
+    if (pl.n_words != (n + 15) / 16 + 8 * ((n + 127) / 128 + 1)) return fail(UNC_ERR_IO, "%s.bwt: size does not match seq_len", bwa_prefix);
     if (n >= (1ull << 34)) return fail(UNC_ERR_ARG, "reference too large: seq_len %llu >= 2^34", (unsigned long long)n);
 
     // .sa = u64 primary; u64 x4; u64 intv; u64 seq_len; u64 sa[1..]
-    std::vector<char> sa;
-    if (!read_file(prefix + ".sa", sa) || sa.size() < 56) return fail(UNC_ERR_IO, "failed to load BWA index: %s.sa", bwa_prefix);
+    if (!read_file(prefix + ".sa", pl.sa) || pl.sa.size() < 56) return fail(UNC_ERR_IO, "failed to load BWA index: %s.sa", bwa_prefix);
     uint64_t sa_primary, sa_intv, sa_seq_len;
-    memcpy(&sa_primary, sa.data(), 8);
-    memcpy(&sa_intv, sa.data() + 40, 8);
-    memcpy(&sa_seq_len, sa.data() + 48, 8);
+    memcpy(&sa_primary, pl.sa.data(), 8);
+    memcpy(&sa_intv, pl.sa.data() + 40, 8);
+    memcpy(&sa_seq_len, pl.sa.data() + 48, 8);
     if (sa_primary != ix->primary || sa_seq_len != n || sa_intv != 32) return fail(UNC_ERR_IO, "%s.sa does not match the .bwt (interval must be 32)", bwa_prefix);
-    const uint64_t n_sa = (n + 32) / 32;
-    if (sa.size() != 56 + (n_sa - 1) * 8) return fail(UNC_ERR_IO, "%s.sa: unexpected size", bwa_prefix);
+    pl.n_sa = (n + 32) / 32;
+    if (pl.sa.size() != 56 + (pl.n_sa - 1) * 8) return fail(UNC_ERR_IO, "%s.sa: unexpected size", bwa_prefix);
 
-    int rc = parse_ann(prefix + ".ann", ix);
-    if (rc) return rc;
-    rc = parse_uncl(prefix + ".uncl", idx_preset ? idx_preset : "default", ix->thresholds);
-    if (rc) return rc;
+    if (int rc = parse_ann(prefix + ".ann", ix)) return rc;
+    if (int rc = parse_uncl(prefix + ".uncl", idx_preset ? idx_preset : "default", ix->thresholds)) return rc;
     build_model(ix);
 
-    HIPCHK(hipSetDevice(device));
-    // pad the BWT to whole 64-byte blocks so that block loads of the last (partial) block stay in bounds
-    const size_t bwt_bytes = ((n_words * 4 + 63) / 64 + 1) * 64;
-    // (the index's tables are read at random by every FM step: allocated behind a spacer like the mapper's slots -- PlacementSpacer)
-    PlacementSpacer spacer(bwt_bytes + n_sa * 8 + ((size_t)n_words * 16 + 2) / 2 * 12 + (size_t)n_words * 2 + (64u << 20));
-    HIPCHK(ix->d_bwt.alloc(bwt_bytes / 4));
-    HIPCHK(hipMemset(ix->d_bwt.p, 0, bwt_bytes));
-    HIPCHK(hipMemcpy(ix->d_bwt.p, bwt.data() + 40, n_words * 4, hipMemcpyHostToDevice));
-    HIPCHK(ix->d_sa.alloc(n_sa));
+    pl.bwt_bytes = ((pl.n_words * 4 + 63) / 64 + 1) * 64;
+    pl.sa_bytes = pl.n_sa * 8;
+    pl.dense_sa_bytes = ((n + 2) / 2) * 12 + 16;
+    pl.fm32_blocks = (n + 63) / 64 + 1;
+    pl.fm32_bytes = pl.fm32_blocks * 32;
+    // (the estimate takes the dense SA as n_words * 16 rows, about twice what is allocated, and the rest as n_words * 2 bytes + 64 MB:
+    // it differs from the allocations ON PURPOSE -- it decides the spacer's size, and with it where the tables lie)
+    const size_t dense_sa_estimate = (pl.n_words * 16 + 2) / 2 * 12;
+    pl.spacer_need = pl.bwt_bytes + pl.sa_bytes + dense_sa_estimate + pl.n_words * 2 + (64u << 20);
+    return UNC_OK;
+}
+
+// BWT, sampled SA, room for the k-mer ranges and the two layouts of the pore model; the view the kernels take
+static int upload_tables(unc_index *ix, const IndexPlan &pl) {
+    HIPCHK(ix->d_bwt.alloc(pl.bwt_bytes / 4));
+    HIPCHK(hipMemset(ix->d_bwt.p, 0, pl.bwt_bytes));
+    HIPCHK(hipMemcpy(ix->d_bwt.p, pl.bwt.data() + 40, pl.n_words * 4, hipMemcpyHostToDevice));
+    HIPCHK(ix->d_sa.alloc(pl.n_sa));
     {
-        std::vector<uint64_t> h(n_sa);
+        std::vector<uint64_t> h(pl.n_sa);
         h[0] = ~0ull;   // bwt_restore_sa: sa[0] = -1
-        memcpy(h.data() + 1, sa.data() + 56, (n_sa - 1) * 8);
-        HIPCHK(hipMemcpy(ix->d_sa.p, h.data(), n_sa * 8, hipMemcpyHostToDevice));
+        memcpy(h.data() + 1, pl.sa.data() + 56, (pl.n_sa - 1) * 8);
+        HIPCHK(hipMemcpy(ix->d_sa.p, h.data(), pl.sa_bytes, hipMemcpyHostToDevice));
     }
-    HIPCHK(ix->d_kmer_ranges.alloc(2 * NKMER));
-    HIPCHK(ix->d_model.alloc(3 * NKMER));
-    HIPCHK(hipMemcpy(ix->d_model.p, ix->model.data(), 3 * NKMER * 4, hipMemcpyHostToDevice));
+    HIPCHK(ix->d_kmer_ranges.alloc(N_RANGES));
+    HIPCHK(ix->d_model.alloc(N_MODEL));
+    HIPCHK(hipMemcpy(ix->d_model.p, ix->model.data(), N_MODEL * 4, hipMemcpyHostToDevice));
     {
-        std::vector<float> m4(4 * NKMER, 0.0f);
+        std::vector<float> m4(N_MODEL4, 0.0f);
         for (int k = 0; k < NKMER; ++k) { m4[4 * k] = ix->model[k]; m4[4 * k + 1] = ix->model[NKMER + k]; m4[4 * k + 2] = ix->model[2 * NKMER + k]; }
-        HIPCHK(ix->d_model4.alloc(4 * NKMER));
-        HIPCHK(hipMemcpy(ix->d_model4.p, m4.data(), 4 * NKMER * 4, hipMemcpyHostToDevice));
+        HIPCHK(ix->d_model4.alloc(N_MODEL4));
+        HIPCHK(hipMemcpy(ix->d_model4.p, m4.data(), N_MODEL4 * 4, hipMemcpyHostToDevice));
     }
-    ix->device_bytes = bwt_bytes + n_sa * 8 + 2 * NKMER * 8 + 3 * NKMER * 4;
+    // (what unc_index_device_bytes reports leaves out d_model4 and, below, d_kmer_valid -- 16.1 KB together --: kept ON PURPOSE, the
+    // number is compared between versions)
+    ix->device_bytes = pl.bwt_bytes + pl.sa_bytes + N_RANGES * 8 + N_MODEL * 4;
 
     DevIndex &d = ix->dev;
     d.bwt = ix->d_bwt.p; d.sa = ix->d_sa.p; d.kmer_ranges = ix->d_kmer_ranges.p; d.model = ix->d_model.p; d.model4 = ix->d_model4.p;
-    d.primary = ix->primary; d.seq_len = n;
+    d.primary = ix->primary; d.seq_len = pl.n;
     for (int i = 0; i < 5; ++i) d.L2[i] = ix->L2[i];
     memcpy(d.thresholds, ix->thresholds, sizeof d.thresholds);
-
     d.sa_dense = nullptr;
-    // Dense SA (6 bytes per BWT row, fm_dev.h: 56 MB for E. coli, 37 GB for GRCh38; 8 bytes in rounds 2-5): every row walks LF to
-    // its sampled row once, here, instead of on every seed.  UNC_DENSE_SA=0 keeps the BWA sampling only.
-    {
-        const char *env = getenv("UNC_DENSE_SA");
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        free_b += spacer.bytes;
-        const size_t need = ((n + 2) / 2) * 12 + 16;      // rows 0 .. n in pairs (12 bytes) + the word a load reads past the last entry
-        if (!(env && env[0] == '0') && !(flags & UNC_INDEX_NO_DENSE_SA) && need < free_b / 2) {
-            HIPCHK(ix->d_sa_dense.alloc(need));
-            uint64_t *const dense = reinterpret_cast<uint64_t *>(ix->d_sa_dense.p);
-            launch_dense_sa(d, dense, nullptr);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipDeviceSynchronize());
-            {   // self-check: 16 384 rows spread over the whole table (the last row included) against the BWA-format walk
-                DevBuf<uint32_t> d_bad;
-                uint32_t bad = 0;
-                HIPCHK(d_bad.alloc(1));
-                HIPCHK(hipMemset(d_bad.p, 0, 4));
-                launch_dense_sa_check(d, dense, 16384, d_bad.p, nullptr);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
-                if (bad) return fail(UNC_ERR_HIP, "dense SA self-check failed on %u of 16384 probe rows", bad);
-            }
-            d.sa_dense = dense;
-            ix->device_bytes += need;
-        }
-    }
-    // References of fewer than 2^32 rows (the reference's own 32-bit regime, range.hpp:37) get the 32-bit rank table k_map
-    // works on there (fm_dev.h: 32 bytes per 64 symbols, counts with L2 folded in, symbols as bit planes), checked against the
-    // BWA-format arithmetic on 16 384 pseudo-random steps.  UNC_FM32=0 (tests) leaves the table out: key_len_bits is then 0 below, and
-    // the taps and k_map run the 64-bit arithmetic of the references of 2^32 rows and more on a small one.
     d.fm32 = nullptr;
-    const char *fm32_env = getenv("UNC_FM32");
-    if (n < 0xFFFFFF00ull && !(fm32_env && fm32_env[0] == '0')) {
-        const uint32_t n_blk = (uint32_t)((n + 63) / 64 + 1);
-        HIPCHK(ix->d_fm32.alloc((size_t)n_blk * 8));
-        launch_build_fm32(d, ix->d_fm32.p, n_blk, nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-        d.fm32 = ix->d_fm32.p;
-        DevBuf<uint32_t> d_bad;
-        uint32_t bad = 0;
-        HIPCHK(d_bad.alloc(1));
-        HIPCHK(hipMemset(d_bad.p, 0, 4));
-        launch_fm32_check(d, 16384, d_bad.p, nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
-        if (bad) return fail(UNC_ERR_HIP, "32-bit rank table self-check failed on %u of 16384 probe steps", bad);
-        ix->device_bytes += (size_t)n_blk * 32;
-    }
-    // the 1024 k-mer ranges, derived on the device exactly as BwaIndex::load_index does (bwa_index.hpp:124-132)
-    launch_kmer_ranges(d, ix->d_kmer_ranges.p, nullptr);
+    return UNC_OK;
+}
+
+// The self-check of a table just built: a counter on the device, zeroed, which `launch` adds the probes that differ to; any fails the load.
+template <class Launch> static int self_check(Launch launch, const char *fail_fmt) {
+    DevBuf<uint32_t> d_bad;
+    uint32_t bad = 0;
+    HIPCHK(d_bad.alloc(1));
+    HIPCHK(hipMemset(d_bad.p, 0, 4));
+    launch(d_bad.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
+    if (bad) return fail(UNC_ERR_HIP, fail_fmt, bad);
+    return UNC_OK;
+}
+
+// Dense SA (6 bytes per BWT row, fm_dev.h: 56 MB for E. coli, 37 GB for GRCh38; 8 bytes in rounds 2-5): every row walks LF to
+// its sampled row once, here, instead of on every seed -- when it fits half of the HBM that is free (the spacer's share counted as free).
+static int build_dense_sa(unc_index *ix, const IndexPlan &pl, const IndexKnobs &knobs, size_t spacer_bytes) {
+    DevIndex &d = ix->dev;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    free_b += spacer_bytes;
+    if (!knobs.dense_sa || pl.dense_sa_bytes >= free_b / 2) return UNC_OK;
+    HIPCHK(ix->d_sa_dense.alloc(pl.dense_sa_bytes));
+    uint64_t *const dense = reinterpret_cast<uint64_t *>(ix->d_sa_dense.p);
+    launch_dense_sa(d, dense, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    ix->kmer_ranges.resize(2 * NKMER);
-    HIPCHK(hipMemcpy(ix->kmer_ranges.data(), ix->d_kmer_ranges.p, 2 * NKMER * 8, hipMemcpyDeviceToHost));
+    // 16 384 rows spread over the whole table (the last row included) against the BWA-format walk
+    int rc = self_check([&](uint32_t *bad) { launch_dense_sa_check(d, dense, 16384, bad, nullptr); },
+                        "dense SA self-check failed on %u of 16384 probe rows");
+    if (rc) return rc;
+    d.sa_dense = dense;
+    ix->device_bytes += pl.dense_sa_bytes;
+    return UNC_OK;
+}
+
+// References of fewer than 2^32 rows (the reference's own 32-bit regime, range.hpp:37) get the 32-bit rank table k_map
+// works on there (fm_dev.h: 32 bytes per 64 symbols, counts with L2 folded in, symbols as bit planes), checked against the
+// BWA-format arithmetic on 16 384 pseudo-random steps.  Without the table key_len_bits is 0 (index_key_grid), and
+// the taps and k_map run the 64-bit arithmetic of the references of 2^32 rows and more.
+static int build_fm32(unc_index *ix, const IndexPlan &pl, const IndexKnobs &knobs) {
+    DevIndex &d = ix->dev;
+    if (pl.n >= 0xFFFFFF00ull || !knobs.fm32) return UNC_OK;
+    HIPCHK(ix->d_fm32.alloc(pl.fm32_bytes / 4));
+    launch_build_fm32(d, ix->d_fm32.p, (uint32_t)pl.fm32_blocks, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    d.fm32 = ix->d_fm32.p;
+    int rc = self_check([&](uint32_t *bad) { launch_fm32_check(d, 16384, bad, nullptr); },
+                        "32-bit rank table self-check failed on %u of 16384 probe steps");
+    if (rc) return rc;
+    ix->device_bytes += pl.fm32_bytes;
+    return UNC_OK;
+}
+
+// the 1024 k-mer ranges, derived on the device exactly as BwaIndex::load_index does (bwa_index.hpp:124-132)
+static int derive_kmer_ranges(unc_index *ix) {
+    launch_kmer_ranges(ix->dev, ix->d_kmer_ranges.p, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    ix->kmer_ranges.resize(N_RANGES);
+    HIPCHK(hipMemcpy(ix->kmer_ranges.data(), ix->d_kmer_ranges.p, N_RANGES * 8, hipMemcpyDeviceToHost));
     for (int k = 0; k < NKMER; ++k) {
         uint64_t s = ix->kmer_ranges[2 * k], e = ix->kmer_ranges[2 * k + 1];
         if (s <= e && e - s + 1 >= (1ull << KEY_LEN_BITS)) return fail(UNC_ERR_ARG, "k-mer %d occurs more than 2^30 times: unsupported", k);
     }
-    {
-        // narrow sort keys: start | length | 16-bit creation index in 64 bits when the reference allows it
-        uint64_t max_len = 0;
-        for (int k = 0; k < NKMER; ++k) {
-            uint64_t s = ix->kmer_ranges[2 * k], e = ix->kmer_ranges[2 * k + 1];
-            if (s <= e && e - s > max_len) max_len = e - s;
+    return UNC_OK;
+}
+
+// Width of the sort keys and the grid of the seed clusters, from the reference's size, its longest k-mer range (end - start) and the knobs.
+struct KeyGrid { uint32_t key_len_bits, bucket_shift, n_buckets; };
+static KeyGrid index_key_grid(uint64_t n, uint64_t max_len, bool have_fm32, const IndexKnobs &knobs) {
+    KeyGrid g;
+    // narrow sort keys: start | length | 16-bit creation index in 64 bits when the reference allows it
+    uint32_t start_bits = 1, len_bits = 1;
+    while ((n >> start_bits) != 0) ++start_bits;
+    while ((max_len >> len_bits) != 0) ++len_bits;
+    // (narrow keys also mean 32-bit rows in k_map: only with the 32-bit rank table)
+    g.key_len_bits = (start_bits + len_bits + 16 <= 64 && have_fm32 && !knobs.wide_keys) ? len_bits : 0;
+    // the grid the seed clusters of a read are bucketed in (k_map.hip, add_seed): buckets of 2^shift rows, at most 2^15 per read,
+    // at least 2^12 rows wide, so that a window of 32768 rows (max_events <= 65535 is checked per mapper) spans few buckets
+    uint32_t shift = start_bits > 15 + BUCKET_SHIFT_MIN ? start_bits - 15 : BUCKET_SHIFT_MIN;
+    // UNC_BUCKET_SHIFT (tests): narrower buckets, so that the small test references have windows of many buckets
+    // (several gathers per seed) and clusters that move between buckets
+    const long v = knobs.bucket_shift;
+    if (v >= 2 && v <= 30 && (n >> v) < (1ull << 22)) shift = (uint32_t)v;
+    g.bucket_shift = shift;
+    g.n_buckets = (uint32_t)(n >> shift) + 2u;
+    return g;
+}
+
+static void set_key_grid(unc_index *ix, const IndexKnobs &knobs) {
+    uint64_t max_len = 0;
+    for (int k = 0; k < NKMER; ++k) {
+        uint64_t s = ix->kmer_ranges[2 * k], e = ix->kmer_ranges[2 * k + 1];
+        if (s <= e && e - s > max_len) max_len = e - s;
+    }
+    const KeyGrid g = index_key_grid(ix->seq_len, max_len, ix->dev.fm32 != nullptr, knobs);
+    ix->dev.key_len_bits = g.key_len_bits;
+    ix->dev.pad_ = 0;
+    ix->dev.bucket_shift = g.bucket_shift;
+    ix->dev.n_buckets = g.n_buckets;
+}
+
+// per lane, the k-mers lane + 64 j that occur in the reference at all
+static int upload_kmer_valid(unc_index *ix) {
+    uint16_t valid[WAVE];
+    for (int l = 0; l < WAVE; ++l) {
+        valid[l] = 0;
+        for (int j = 0; j < NKMER / WAVE; ++j) {
+            const int k = j * WAVE + l;
+            if (ix->kmer_ranges[2 * k] <= ix->kmer_ranges[2 * k + 1]) valid[l] |= (uint16_t)(1u << j);
         }
-        uint32_t start_bits = 1, len_bits = 1;
-        while ((n >> start_bits) != 0) ++start_bits;
-        while ((max_len >> len_bits) != 0) ++len_bits;
-        const char *wide = getenv("UNC_WIDE_KEYS");
-        // (narrow keys also mean 32-bit rows in k_map: only with the 32-bit rank table)
-        ix->dev.key_len_bits = (start_bits + len_bits + 16 <= 64 && ix->dev.fm32 && !(wide && wide[0] == '1')) ? len_bits : 0;
-        ix->dev.pad_ = 0;
     }
-    {
-        // the grid the seed clusters of a read are bucketed in (k_map.hip, add_seed): buckets of 2^shift rows, at most 2^15 per read,
-        // at least 2^12 rows wide, so that a window of 32768 rows (max_events <= 65535 is checked per mapper) spans few buckets
-        uint32_t bits = 1;
-        while ((n >> bits) != 0) ++bits;
-        uint32_t shift = bits > 15 + BUCKET_SHIFT_MIN ? bits - 15 : BUCKET_SHIFT_MIN;
-        // UNC_BUCKET_SHIFT (tests): narrower buckets, so that the small test references have windows of many buckets
-        // (several gathers per seed) and clusters that move between buckets
-        if (const char *e = getenv("UNC_BUCKET_SHIFT")) { const long v = atol(e); if (v >= 2 && v <= 30 && (n >> v) < (1ull << 22)) shift = (uint32_t)v; }
-        ix->dev.bucket_shift = shift;
-        ix->dev.n_buckets = (uint32_t)(n >> shift) + 2u;
-    }
-    {
-        uint16_t valid[WAVE];
-        for (int l = 0; l < WAVE; ++l) {
-            valid[l] = 0;
-            for (int j = 0; j < NKMER / WAVE; ++j) {
-                const int k = j * WAVE + l;
-                if (ix->kmer_ranges[2 * k] <= ix->kmer_ranges[2 * k + 1]) valid[l] |= (uint16_t)(1u << j);
-            }
-        }
-        HIPCHK(ix->d_kmer_valid.alloc(WAVE));
-        HIPCHK(hipMemcpy(ix->d_kmer_valid.p, valid, sizeof valid, hipMemcpyHostToDevice));
-        ix->dev.kmer_valid = ix->d_kmer_valid.p;
-    }
+    HIPCHK(ix->d_kmer_valid.alloc(WAVE));
+    HIPCHK(hipMemcpy(ix->d_kmer_valid.p, valid, sizeof valid, hipMemcpyHostToDevice));
+    ix->dev.kmer_valid = ix->d_kmer_valid.p;
+    return UNC_OK;
+}
+
+extern "C" int unc_index_load_flags(const char *bwa_prefix, const char *idx_preset, int device, uint32_t flags, unc_index_t **out) {
+    if (flags & ~UNC_INDEX_NO_DENSE_SA) return fail(UNC_ERR_ARG, "unc_index_load_flags: unknown flags %#x", flags);
+    if (!bwa_prefix || !out) return fail(UNC_ERR_ARG, "null argument");
+    *out = nullptr;
+    const IndexKnobs knobs = read_index_knobs(flags);
+    unc_index *ix = new unc_index();
+    ix->device = device;
+    struct Guard { unc_index *p; ~Guard() { if (p) unc_index_free(p); } } guard{ix};
+
+    IndexPlan pl;
+    int rc = plan_index(bwa_prefix, idx_preset, ix, pl);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device));
+    // (the index's tables are read at random by every FM step: allocated behind a spacer like the mapper's slots -- PlacementSpacer --,
+    // which is held until the load returns)
+    PlacementSpacer spacer(pl.spacer_need);
+    if ((rc = upload_tables(ix, pl))) return rc;                               // d_bwt, d_sa, d_kmer_ranges, d_model, d_model4
+    if ((rc = build_dense_sa(ix, pl, knobs, spacer.bytes))) return rc;         // d_sa_dense, the check's counter
+    if ((rc = build_fm32(ix, pl, knobs))) return rc;                           // d_fm32, the check's counter
+    if ((rc = derive_kmer_ranges(ix))) return rc;
+    set_key_grid(ix, knobs);
+    if ((rc = upload_kmer_valid(ix))) return rc;                               // d_kmer_valid
     guard.p = nullptr;
     *out = ix;
     return UNC_OK;
@@ -491,8 +564,6 @@ struct unc_mapper {
     Sched sched;                  // ctl != null: sliced batch scheduler (n_slots > n_waves)
     Scratch sc;
     uint64_t device_bytes = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     double win_start_ms = 0, win_end_ms = 0;      // k_map of the last batch on the process-wide time axis (unc_mapper_last_window)
     float ms_events = 0, ms_map = 0;
     double wave_busy = 0;          // mean wave lifetime / k_map duration of the last batch (1 = no queue tail)
@@ -539,6 +610,8 @@ struct unc_mapper {
     // trace state
     uint32_t trace_n = 0;
     bool trace_active = false;
+    DevStream stream;              // declared last, so destroyed first: the events, then the stream, before the device buffers are freed
+    DevEvents ev;
 };
 
 // Regions of one slot (DevScratch), each 256-byte aligned; everything below 4 GB so that kernels address a slot as
@@ -639,13 +712,31 @@ static int alloc_pool(Pool &p, uint32_t n_chunks, size_t *bytes_out) {
     return UNC_OK;
 }
 
+// The scheduler's rings of a sliced mapper (n_slots > n_waves): one pair per XCD when every XCD's share of the slots is a fair number
+// (SchedCtl): slots then never cross XCDs
+static int alloc_sched(Sched &s, const unc_mapper_opts_t *opts, uint32_t n_slots, int device, size_t *bytes_out) {
+    uint32_t parts = (opts && opts->sched_parts) ? opts->sched_parts : xcd_count(device);
+    if (parts > SCHED_MAX_PARTS || parts == 0 || n_slots % parts || n_slots / parts < 64 || (opts && opts->sched_parts > 1 && opts->sched_parts != xcd_count(device))) {
+        if (opts && opts->sched_parts > 1) return fail(UNC_ERR_ARG, "sched_parts: 0, 1 or the device's number of XCDs (%u), dividing n_slots into shares of 64 or more", xcd_count(device));
+        parts = 1;
+    }
+    uint32_t cap = 64;
+    while (cap < n_slots / parts) cap <<= 1;
+    const size_t cells = (size_t)parts * cap;
+    s.v.cap_mask = cap - 1; s.v.n_slots = n_slots; s.v.n_parts = parts;
+    HIPCHK(s.ctl.alloc(1));
+    HIPCHK(s.free_cells.alloc(cells));
+    HIPCHK(s.park_cells.alloc(cells));
+    s.v.ctl = s.ctl.p; s.v.free_cells = s.free_cells.p; s.v.park_cells = s.park_cells.p;
+    *bytes_out += sizeof(SchedCtl) + 2 * cells * sizeof(SchedCell);
+    return UNC_OK;
+}
+
 static SlotState *slot_state(const DevScratch &sc, size_t slot) { return reinterpret_cast<SlotState *>(sc.base + slot * sc.slot_bytes + sc.off_state); }
 
 extern "C" void unc_mapper_free(unc_mapper_t *m) {
     if (!m) return;
     (void)hipSetDevice(m->ix->device);
-    for (auto &e : m->ev) if (e) (void)hipEventDestroy(e);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
 }
 
@@ -662,117 +753,119 @@ static int ref_event(hipEvent_t *out) {
     *out = g_ref_event;
     return UNC_OK;
 }
-extern "C" int unc_mapper_create(const unc_index_t *ix, const unc_params_t *p, const unc_mapper_opts_t *opts, unc_mapper_t **out) {
-    if (!ix || !p || !out) return fail(UNC_ERR_ARG, "null argument");
-    *out = nullptr;
+
+// what the kernels are built for: the checks of unc_mapper_create and unc_rt_create
+static int check_params(const unc_params_t *p) {
     if (p->seed_len != UNC_SEED_LEN) return fail(UNC_ERR_ARG, "seed_len must be %d", UNC_SEED_LEN);
     if (p->window_length1 != UNC_WINDOW1 || p->window_length2 != UNC_WINDOW2) return fail(UNC_ERR_ARG, "event windows must be %d/%d", UNC_WINDOW1, UNC_WINDOW2);
     if (p->max_paths == 0 || p->max_paths > 65535) return fail(UNC_ERR_ARG, "max_paths must be in 1..65535");
     if (p->max_rep_copy > (uint32_t)MAX_REP_COPY_LIMIT) return fail(UNC_ERR_ARG, "max_rep_copy must be <= %d", MAX_REP_COPY_LIMIT);
     if (p->max_consec_stay > 255) return fail(UNC_ERR_ARG, "max_consec_stay must be <= 255");
     if (p->max_events > 65535) return fail(UNC_ERR_ARG, "max_events must be <= 65535");
+    return UNC_OK;
+}
+
+// chunks of the node pool the caller named or, per read in flight, the rule's: 8 on a bacterial reference, 24 from 2^26 index rows on
+// -- chr20: eleven out at the peak --, 32 from 2^31 on (rounds 2-5 and most of round 6: 64, for every reference past 2^26 rows -- 155 GB
+// for chr20, which left no room for a second mapper beside the first).
+// Round 6, after the ring change: GRCh38 with 12 288 reads in flight has 287 000 chunks out at the peak, the same in every
+// launch (23 per read in flight): 32 per slot = 393 000 chunks = 75 GB = 1.37 x the peak, where 64 (capped at 60 % of the
+// free HBM) had grown to 131 GB once the dense SA and the slots had shrunk.
+static size_t pool_per_slot(uint64_t seq_len) { return seq_len >= (1ull << 31) ? 32 : seq_len >= (1ull << 26) ? 24 : 8; }
+static size_t pool_chunks_wanted(const unc_mapper_opts_t *opts, uint32_t n_slots, size_t per_slot) {
+    return (opts && opts->pool_chunks) ? (size_t)opts->pool_chunks : (size_t)n_slots * per_slot;
+}
+
+// A mapper's sizes, each worked out once, from what the caller named (opts), the wavefronts the device holds (asked for when
+// n_waves is not named) and the HBM free at entry (asked for when n_slots is not named).
+struct MapperGeometry {
+    uint32_t n_slots, n_waves, slice_events, ev_rpw;
+    uint32_t max_seed_paths;      // every seed of an event is either an ended parent or a surviving child: 2 * max_paths bounds the per-event list
+    uint32_t max_clusters;        // per read: the table of bucket heads of its seed-cluster grid and the list of its pool chunks;
+                                  // max_clusters / 4 is the number of nodes a read may take from the pool (its allowance)
+    size_t pool_per_slot;
+    size_t need_after;            // what the slots and the pool will take, for the spacer (PlacementSpacer)
+};
+static MapperGeometry mapper_geometry(const unc_mapper_opts_t *opts, const unc_params_t &p, const DevIndex &dix, uint32_t device_waves, size_t free_at_entry) {
+    MapperGeometry g;
+    g.slice_events = (opts && opts->slice_events) ? opts->slice_events : 1024;
+    g.ev_rpw = (opts && opts->events_reads_per_wave) ? opts->events_reads_per_wave : 64;
+    g.max_seed_paths = (opts && opts->max_seed_paths) ? opts->max_seed_paths : 2 * p.max_paths;
+    g.max_clusters = (opts && opts->max_clusters) ? opts->max_clusters : (1u << 20);
+    g.n_slots = opts ? opts->n_slots : 0;
+    g.n_waves = (opts && opts->n_waves) ? opts->n_waves : device_waves;
+    const size_t slot_bytes = scratch_slot_bytes(p, g.max_clusters, g.max_seed_paths, dix);
+    if (g.n_slots == 0) {
+        // three times more reads in flight than wavefronts, so that the long reads of a batch are found early (DevSched); 2 - 3 MB of
+        // scratch per slot, bounded by a third of the free HBM.  (Rounds 2-5: four times.  With the rings per XCD, E. coli maps 5 - 8 %
+        // faster at 2.5 - 3 and at 4.25 - 5 reads per wavefront than at 3.5 - 4, chr20 3 % faster, GRCh38 the same, and a quarter of the
+        // slots' memory is saved: profiles/r06_ab_slots_*.log.)
+        g.n_slots = (uint32_t)std::min((size_t)g.n_waves * 3, free_at_entry / 3 / slot_bytes);
+        if (g.n_slots > 512) g.n_slots -= g.n_slots % 512;      // (whole shares of 64 slots and more for the rings of up to eight XCDs)
+        if (g.n_slots < g.n_waves) g.n_slots = g.n_waves;
+    }
+    if (g.n_slots < g.n_waves) g.n_waves = g.n_slots;
+    g.pool_per_slot = pool_per_slot(dix.seq_len);
+    g.need_after = (size_t)g.n_slots * slot_bytes + pool_chunks_wanted(opts, g.n_slots, g.pool_per_slot) * POOL_CHUNK_BYTES;
+    return g;
+}
+
+// The pool of cluster nodes: what the caller named, or pool_per_slot chunks (1.5 MB, 6144 nodes at 8) per read in flight, at most
+// 60% of what is left of the HBM (`free_b`: asked for after the slots exist, the spacer's share counted as free) and never fewer than
+// 16.  k_map stops taking up new reads while the pool is nearly empty; a read that still finds it dry is mapped again after the batch.
+// That rule sizes the pool for the FIRST batch only: after every batch pool_fit (below) may cut it to four times the
+// high-water mark of chunks out at once (never below `floor`: one chunk per slot) or double it.
+struct PoolSize { uint32_t n_chunks; bool automatic; uint32_t floor; };
+static PoolSize pool_size(const unc_mapper_opts_t *opts, uint32_t n_slots, size_t per_slot, size_t free_b) {
+    if (opts && opts->pool_chunks) return PoolSize{opts->pool_chunks, false, 16};
+    const size_t n = std::max<size_t>(16, std::min(pool_chunks_wanted(opts, n_slots, per_slot), free_b / 5 * 3 / POOL_CHUNK_BYTES));
+    return PoolSize{(uint32_t)n, true, std::max<uint32_t>(16, std::min<uint32_t>(n_slots, (uint32_t)n))};
+}
+
+// Allocation order: [spacer] slots, d_next, pool nodes / queue / cells, [spacer freed], scheduler rings
+extern "C" int unc_mapper_create(const unc_index_t *ix, const unc_params_t *p, const unc_mapper_opts_t *opts, unc_mapper_t **out) {
+    if (!ix || !p || !out) return fail(UNC_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (int rc = check_params(p)) return rc;
+    if (opts && opts->events_reads_per_wave > (uint32_t)WAVE) return fail(UNC_ERR_ARG, "events_reads_per_wave must be in 1..64");
     HIPCHK(hipSetDevice(ix->device));
     unc_mapper *m = new unc_mapper();
     struct Guard { unc_mapper *p; ~Guard() { if (p) unc_mapper_free(p); } } guard{m};
     m->ix = ix;
     m->P = *p;
-    uint32_t n_slots = opts ? opts->n_slots : 0, n_waves = opts ? opts->n_waves : 0;
-    if (n_waves == 0) {
+    uint32_t device_waves = 0;
+    size_t free_b = 0, total_b = 0;
+    if (!opts || !opts->n_waves) {
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, ix->device));
-        n_waves = (uint32_t)prop.multiProcessorCount * map_kernel_waves_per_cu();
-        if (n_slots && n_slots < n_waves) n_waves = n_slots;
+        device_waves = (uint32_t)prop.multiProcessorCount * map_kernel_waves_per_cu();
     }
-    if (n_slots == 0) {
-        // three times more reads in flight than wavefronts, so that the long reads of a batch are found early (DevSched); 2 - 3 MB of
-        // scratch per slot, bounded by a third of the free HBM.  (Rounds 2-5: four times.  With the rings per XCD, E. coli maps 5 - 8 %
-        // faster at 2.5 - 3 and at 4.25 - 5 reads per wavefront than at 3.5 - 4, chr20 3 % faster, GRCh38 the same, and a quarter of the
-        // slots' memory is saved: profiles/r06_ab_slots_*.log.)
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const uint32_t msp0 = (opts && opts->max_seed_paths) ? opts->max_seed_paths : 2 * p->max_paths;
-        const uint32_t mcl0 = (opts && opts->max_clusters) ? opts->max_clusters : (1u << 20);
-        const size_t per_slot = scratch_slot_bytes(*p, mcl0, msp0, ix->dev);
-        size_t want = (size_t)n_waves * 3, fit = free_b / 3 / per_slot;
-        n_slots = (uint32_t)(want < fit ? want : fit);
-        if (n_slots > 512) n_slots -= n_slots % 512;      // (whole shares of 64 slots and more for the rings of up to eight XCDs)
-        if (n_slots < n_waves) n_slots = n_waves;
-    }
-    if (n_slots < n_waves) n_waves = n_slots;
-    m->n_slots = n_slots;
-    m->n_waves = n_waves;
-    m->slice_events = (opts && opts->slice_events) ? opts->slice_events : 1024;
-    m->ev_rpw = (opts && opts->events_reads_per_wave) ? opts->events_reads_per_wave : 64;
-    if (m->ev_rpw > (uint32_t)WAVE) return fail(UNC_ERR_ARG, "events_reads_per_wave must be in 1..64");
+    if (!opts || !opts->n_slots) HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const MapperGeometry g = mapper_geometry(opts, *p, ix->dev, device_waves, free_b);
+    m->n_slots = g.n_slots; m->n_waves = g.n_waves; m->slice_events = g.slice_events; m->ev_rpw = g.ev_rpw;
+
     size_t bytes = 0;
-    // every seed of an event is either an ended parent or a surviving child: 2 * max_paths bounds the per-event list
-    const uint32_t msp = (opts && opts->max_seed_paths) ? opts->max_seed_paths : 2 * p->max_paths;
-    // per read: the table of bucket heads of its seed-cluster grid and the list of its pool chunks; max_clusters / 4 is the number
-    // of nodes a read may take from the pool below (its allowance)
-    const uint32_t mcl = (opts && opts->max_clusters) ? opts->max_clusters : (1u << 20);
-    // (what the slots and the pool will take, for the spacer: see PlacementSpacer)
-    const size_t pool_per_slot = ix->seq_len >= (1ull << 31) ? 32 : ix->seq_len >= (1ull << 26) ? 24 : 8;
-    const size_t pool_want = ((opts && opts->pool_chunks) ? (size_t)opts->pool_chunks : (size_t)n_slots * pool_per_slot) * POOL_CHUNK_BYTES;
-    PlacementSpacer spacer((size_t)n_slots * scratch_slot_bytes(*p, mcl, msp, ix->dev) + pool_want);
-    int rc_ = alloc_scratch(m->sc, *p, n_slots, mcl, msp, &bytes, ix->dev);
-    if (rc_) return rc_;
+    PlacementSpacer spacer(g.need_after);
+    if (int rc = alloc_scratch(m->sc, *p, g.n_slots, g.max_clusters, g.max_seed_paths, &bytes, ix->dev)) return rc;
     HIPCHK(m->d_next.alloc(16));
-    {
-        // the pool of cluster nodes: 8 chunks (1.5 MB, 6144 nodes) per read in flight on average, 64 on references of 2^26
-        // index rows and more, where a read touches thousands of buckets and off-target reads collect hundreds of thousands
-        // of clusters; at most 60% of what is left of the HBM.  k_map stops taking up new reads while the pool is nearly
-        // empty; a read that still finds it dry is mapped again after the batch (below).
-        // That rule sizes the pool for the FIRST batch only: after every batch pool_fit (below) may cut it to four times the
-        // high-water mark of chunks out at once (never below one chunk per slot) or double it.
-        uint32_t n_chunks = opts ? opts->pool_chunks : 0;
-        if (n_chunks == 0) {
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(hipMemGetInfo(&free_b, &total_b));
-            free_b += spacer.bytes;             // (held only while the pool is allocated)
-            const size_t chunk_bytes = POOL_CHUNK_BYTES;
-            // (per read in flight: 8 chunks on a bacterial reference, 24 from 2^26 index rows on -- chr20: eleven out at the peak --, 32 from
-            // 2^31 on (rounds 2-5 and most of round 6: 64, for every reference past 2^26 rows -- 155 GB for chr20, which left no room for a
-            // second mapper beside the first)
-            // Round 6, after the ring change: GRCh38 with 12 288 reads in flight has 287 000 chunks out at the peak, the same in every
-            // launch (23 per read in flight): 32 per slot = 393 000 chunks = 75 GB = 1.37 x the peak, where 64 (capped at 60 % of the
-            // free HBM) had grown to 131 GB once the dense SA and the slots had shrunk.
-            const size_t per_slot = pool_per_slot;
-            const size_t want = (size_t)n_slots * per_slot;
-            n_chunks = (uint32_t)std::max<size_t>(16, std::min<size_t>(want, free_b / 5 * 3 / chunk_bytes));
-            m->pool_auto = true;
-            m->pool_floor = std::max<uint32_t>(16, std::min<uint32_t>(n_slots, n_chunks));
-            m->pool_created = n_chunks;
-        }
-        int rc2 = alloc_pool(m->pool, n_chunks, &bytes);
-        if (rc2) return rc2;
+    if (!opts || !opts->pool_chunks) {
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        free_b += spacer.bytes;             // (held only while the pool is allocated)
     }
+    const PoolSize ps = pool_size(opts, g.n_slots, g.pool_per_slot, free_b);
+    m->pool_auto = ps.automatic; m->pool_floor = ps.floor; m->pool_created = ps.automatic ? ps.n_chunks : 0;
+    if (int rc = alloc_pool(m->pool, ps.n_chunks, &bytes)) return rc;
     spacer.release();
-    if (n_slots > n_waves) {
-        // one pair of rings per XCD when every XCD's share of the slots is a fair number (SchedCtl): slots then never cross XCDs
-        uint32_t parts = (opts && opts->sched_parts) ? opts->sched_parts : xcd_count(ix->device);
-        if (parts > SCHED_MAX_PARTS || parts == 0 || n_slots % parts || n_slots / parts < 64 || (opts && opts->sched_parts > 1 && opts->sched_parts != xcd_count(ix->device))) {
-            if (opts && opts->sched_parts > 1) return fail(UNC_ERR_ARG, "sched_parts: 0, 1 or the device's number of XCDs (%u), dividing n_slots into shares of 64 or more", xcd_count(ix->device));
-            parts = 1;
-        }
-        const uint32_t spp = n_slots / parts;
-        uint32_t cap = 64;
-        while (cap < spp) cap <<= 1;
-        m->sched.v.cap_mask = cap - 1; m->sched.v.n_slots = n_slots; m->sched.v.n_parts = parts;
-        HIPCHK(m->sched.ctl.alloc(1));
-        HIPCHK(m->sched.free_cells.alloc((size_t)parts * cap));
-        HIPCHK(m->sched.park_cells.alloc((size_t)parts * cap));
-        m->sched.v.ctl = m->sched.ctl.p; m->sched.v.free_cells = m->sched.free_cells.p; m->sched.v.park_cells = m->sched.park_cells.p;
-        bytes += sizeof(SchedCtl) + 2 * (size_t)parts * cap * sizeof(SchedCell);
-    }
+    if (g.n_slots > g.n_waves)
+        if (int rc = alloc_sched(m->sched, opts, g.n_slots, ix->device, &bytes)) return rc;
     m->device_bytes = bytes;
-    {
-        int khz = 0;
-        HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ix->device));
-        m->wall_khz = (float)khz;
-    }
-    HIPCHK(hipStreamCreate(&m->stream));
-    for (auto &e : m->ev) HIPCHK(hipEventCreate(&e));
-    { hipEvent_t ref = nullptr; int rcr = ref_event(&ref); if (rcr) return rcr; }      // (before the first batch of any mapper)
+
+    int khz = 0;
+    HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ix->device));
+    m->wall_khz = (float)khz;
+    HIPCHK(m->stream.create());
+    HIPCHK(m->ev.create(3));
+    { hipEvent_t ref = nullptr; if (int rc = ref_event(&ref)) return rc; }      // (before the first batch of any mapper)
     guard.p = nullptr;
     *out = m;
     return UNC_OK;
@@ -983,16 +1076,16 @@ extern "C" int unc_map_batch_begin(unc_mapper_t *m, uint32_t n_reads, const int1
     if (!m || !raw || !offsets || !calib) return fail(UNC_ERR_ARG, "null argument");
     if (m->pend.active) return fail(UNC_ERR_ARG, "unc_map_batch_begin: the mapper's previous batch has not been collected (unc_map_batch_end)");
     HIPCHK(hipSetDevice(m->ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+    hipStream_t st = stream ? (hipStream_t)stream : m->stream.s;
     DevReads rd;
     int rc = stage_batch(m, n_reads, raw, offsets, calib, on_device, st, &rd);
     if (rc) return rc;
     MapArgs a = mapper_args(m, rd);
     HIPCHK(hipMemsetAsync(m->d_next.p, 0, 16, st));   // [0] queue head, [2..3] wave-lifetime ticks
     a.wave_ticks = reinterpret_cast<unsigned long long *>(m->d_next.p + 2);
-    HIPCHK(hipEventRecord(m->ev[0], st));
+    HIPCHK(m->ev.record(0, st));
     launch_events(rd, m->P, st, m->ev_rpw);
-    HIPCHK(hipEventRecord(m->ev[1], st));
+    HIPCHK(m->ev.record(1, st));
     const uint32_t grid = n_reads < m->n_waves ? n_reads : m->n_waves;
     const bool sliced = m->sched.v.ctl != nullptr && n_reads > m->n_waves;
     if (sliced) { launch_sched_init(m->sched.v, st); a.sched = m->sched.v; a.max_steps = m->slice_events; }
@@ -1009,7 +1102,7 @@ extern "C" int unc_map_batch_begin(unc_mapper_t *m, uint32_t n_reads, const int1
         a.flags_in = m->d_flags_in.p; a.flags_out = m->d_flags_out.p;
     }
     launch_map(a, grid, st, m->profile);
-    HIPCHK(hipEventRecord(m->ev[2], st));
+    HIPCHK(m->ev.record(2, st));
     HIPCHK(hipGetLastError());
     m->pend.active = true; m->pend.n_reads = n_reads; m->pend.grid = grid; m->pend.st = st; m->pend.args = a; m->pend.t1 = t1;
     m->pend.lens.resize(n_reads);
@@ -1027,11 +1120,11 @@ static int collect_first_pass(unc_mapper *m) {
     HIPCHK(hipMemcpyAsync(m->h_info.data(), m->d_info.p, (size_t)n_reads * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(m->h_results.data(), m->d_results.p, (size_t)n_reads * sizeof(DevResult), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&m->ms_events, m->ev[0], m->ev[1]));
-    HIPCHK(hipEventElapsedTime(&m->ms_map, m->ev[1], m->ev[2]));
+    HIPCHK(m->ev.elapsed(0, 1, &m->ms_events));
+    HIPCHK(m->ev.elapsed(1, 2, &m->ms_map));
     hipEvent_t ref = nullptr;
     float a = 0, b = 0;
-    if (ref_event(&ref) == UNC_OK && hipEventElapsedTime(&a, ref, m->ev[1]) == hipSuccess && hipEventElapsedTime(&b, ref, m->ev[2]) == hipSuccess) {
+    if (ref_event(&ref) == UNC_OK && hipEventElapsedTime(&a, ref, m->ev.e[1]) == hipSuccess && hipEventElapsedTime(&b, ref, m->ev.e[2]) == hipSuccess) {
         m->win_start_ms = a; m->win_end_ms = b;
     } else (void)hipGetLastError();
     for (uint32_t i = 0; i < n_reads; ++i)
@@ -1313,17 +1406,17 @@ extern "C" int unc_detect_events(unc_mapper_t *m, uint32_t n_reads, const int16_
     if (!m || !raw || !offsets || !calib || !means || !means_offsets || !info) return fail(UNC_ERR_ARG, "null argument");
     if (m->pend.active) return fail(UNC_ERR_ARG, "unc_detect_events: the mapper has a batch in flight (unc_map_batch_end first)");
     HIPCHK(hipSetDevice(m->ix->device));
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.s;
     DevReads rd;
     int rc = stage_batch(m, n_reads, raw, offsets, calib, 0, st, &rd);
     if (rc) return rc;
-    HIPCHK(hipEventRecord(m->ev[0], st));
+    HIPCHK(m->ev.record(0, st));
     launch_events(rd, m->P, st, m->ev_rpw);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev[1], st));
+    HIPCHK(m->ev.record(1, st));
     HIPCHK(hipMemcpyAsync(info, m->d_info.p, (size_t)n_reads * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&m->ms_events, m->ev[0], m->ev[1]));     // unc_mapper_last_timing: k_events alone
+    HIPCHK(m->ev.elapsed(0, 1, &m->ms_events));     // unc_mapper_last_timing: k_events alone
     m->ms_map = 0;
     uint64_t tot = 0;
     for (uint32_t i = 0; i < n_reads; ++i)
@@ -1450,21 +1543,17 @@ extern "C" int unc_calib_chase(int device, const void *base, uint64_t bytes, uin
     if (!base || bytes < 16 || !ms_out) return fail(UNC_ERR_ARG, "unc_calib_chase: a region of 16 bytes or more");
     HIPCHK(hipSetDevice(device));
     DevBuf<uint32_t> sink;
-    struct Events {      // (destroyed on every way out)
-        hipEvent_t e[2] = {nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } evs;
-    hipEvent_t &e0 = evs.e[0], &e1 = evs.e[1];
+    DevEvents evs;
     HIPCHK(sink.alloc(1));
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(evs.create(2));
     float best = 1e30f;
     for (int r = 0; r < 3; ++r) {
-        HIPCHK(hipEventRecord(e0, nullptr));
+        HIPCHK(evs.record(0, nullptr));
         launch_calib_chase((const uint4 *)base, bytes / 16, waves ? waves : 4096, steps ? steps : 2000, sink.p, nullptr);
-        HIPCHK(hipEventRecord(e1, nullptr));
-        HIPCHK(hipEventSynchronize(e1));
+        HIPCHK(evs.record(1, nullptr));
+        HIPCHK(hipEventSynchronize(evs.e[1]));
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(evs.elapsed(0, 1, &ms));
         best = std::min(best, ms);
     }
     *ms_out = best;
@@ -1476,7 +1565,7 @@ extern "C" int unc_trace_begin(unc_mapper_t *m, const int16_t *raw, uint32_t n, 
     if (!m || !raw || !calib) return fail(UNC_ERR_ARG, "null argument");
     if (m->pend.active) return fail(UNC_ERR_ARG, "unc_trace_begin: the mapper has a batch in flight (unc_map_batch_end first)");
     HIPCHK(hipSetDevice(m->ix->device));
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.s;
     uint64_t offsets[2] = {0, n};
     DevReads rd;
     int rc = stage_batch(m, 1, raw, offsets, calib, 0, st, &rd);
@@ -1503,11 +1592,11 @@ extern "C" int unc_trace_step(unc_mapper_t *m, uint32_t n_events, int *done) {
     HIPCHK(hipSetDevice(m->ix->device));
     MapArgs a = mapper_args(m, batch_reads(m, m->d_raw.p, 1));      // the read unc_trace_begin staged
     a.max_steps = n_events; a.resume = 1;       // the read parked in slot 0, for n_events events more
-    launch_map(a, 1, m->stream);
+    launch_map(a, 1, m->stream.s);
     HIPCHK(hipGetLastError());
     SlotState s;
-    HIPCHK(hipMemcpyAsync(&s, slot_state(m->sc.v, 0), sizeof s, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMemcpyAsync(&s, slot_state(m->sc.v, 0), sizeof s, hipMemcpyDeviceToHost, m->stream.s));
+    HIPCHK(hipStreamSynchronize(m->stream.s));
     if (done) *done = s.done ? 1 : 0;
     return UNC_OK;
 }
@@ -1675,8 +1764,6 @@ struct unc_rt {
     DevBuf<DevResult> d_results;
     DevBuf<int16_t> d_raw;        // capacity in int16 elements (floats take two each); 64 more lie behind them
     uint64_t device_bytes = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     double win_start_ms = 0, win_end_ms = 0;      // k_map of the last batch on the process-wide time axis (unc_mapper_last_window)
     float ms_events = 0, ms_map = 0;
     std::vector<RtHostChan> chans;
@@ -1685,6 +1772,8 @@ struct unc_rt {
     // dev: UNC_RT_PROFILE=1 launches the cycle-counting instantiation of k_map and prints the phase shares of all finished reads on free
     bool profile = false;
     uint64_t cyc_sum[12] = {0};
+    DevStream stream;             // declared last, so destroyed first: the events, then the stream, before the device buffers are freed
+    DevEvents ev;
 };
 
 extern "C" void unc_rt_free(unc_rt_t *rt) {
@@ -1698,8 +1787,6 @@ extern "C" void unc_rt_free(unc_rt_t *rt) {
         fprintf(stderr, "\n");
     }
     (void)hipSetDevice(rt->ix->device);
-    for (auto &e : rt->ev) if (e) (void)hipEventDestroy(e);
-    if (rt->stream) (void)hipStreamDestroy(rt->stream);
     delete rt;
 }
 
@@ -1748,14 +1835,49 @@ static RtPoolSize rt_pool_size(uint64_t seq_len, size_t n_channels, size_t free_
     return r;
 }
 
+// A realtime mapper's sizes: a slot per channel with the batch path's defaults, and what the spacer is told the slots and the pool
+// will take -- 64 chunks per channel whatever the reference, where rt_pool_size gives 16 below 2^26 rows: an ESTIMATE, kept ON PURPOSE
+// (it decides the spacer's size, and with it where the slots lie)
+struct RtSizes { uint32_t max_clusters, max_seed_paths; size_t need_after; };
+static RtSizes rt_sizes(const unc_params_t &p, const DevIndex &dix, size_t n_channels) {
+    RtSizes z{1u << 20, 2 * p.max_paths, 0};
+    z.need_after = n_channels * scratch_slot_bytes(p, z.max_clusters, z.max_seed_paths, dix) + n_channels * 64 * (size_t)POOL_CHUNK_BYTES;
+    return z;
+}
+
+// the channels' slots (all of a slot zeroed) and their node pool, behind a spacer that is freed before anything else is allocated
+static int alloc_rt_slots_and_pool(unc_rt *rt, const RtSizes &z, size_t *bytes) {
+    PlacementSpacer spacer(z.need_after);
+    if (int rc = alloc_scratch(rt->sc, rt->P, rt->n_channels, z.max_clusters, z.max_seed_paths, bytes, rt->ix->dev)) return rc;
+    HIPCHK(hipMemset(rt->sc.v.base, 0, *bytes));
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    free_b += spacer.bytes;
+    const char *e = getenv("UNC_RT_POOL_CHUNKS");
+    const RtPoolSize ps = rt_pool_size(rt->ix->seq_len, rt->n_channels, free_b, e ? atol(e) : 0);
+    if (ps.clamped)
+        fprintf(stderr, "Warning: realtime node pool clamped from %zu to %zu chunks (%.1f GB of HBM free)\n", ps.wanted, ps.clamped, (double)free_b / 1e9);
+    return alloc_pool(rt->pool, (uint32_t)ps.n_chunks, bytes);
+}
+
+// the per-channel arrays, zeroed
+static int alloc_rt_arrays(unc_rt *rt, size_t *bytes) {
+    const size_t S = rt->n_channels;
+    int rc = UNC_OK;
+    auto zeroed = [&](auto &buf, size_t count) { if (rc == UNC_OK) rc = alloc_zeroed(buf, count, bytes); };
+    zeroed(rt->d_chans, S);     zeroed(rt->d_ring, S * NORM_LEN);
+    zeroed(rt->d_desc, S);      zeroed(rt->d_info, S);
+    zeroed(rt->d_ring0, S);     zeroed(rt->d_newread, S);
+    zeroed(rt->d_slotmap, S);   zeroed(rt->d_next, 16);
+    zeroed(rt->d_moff, S + 1);  zeroed(rt->d_results, S);
+    return rc;
+}
+
+// Allocation order: [spacer] slots, pool nodes / queue / cells, [spacer freed], the ten per-channel arrays
 extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint32_t n_channels, unc_rt_t **out) {
     if (!ix || !p || !out || n_channels == 0) return fail(UNC_ERR_ARG, "bad argument");
     *out = nullptr;
-    if (p->seed_len != UNC_SEED_LEN || p->window_length1 != UNC_WINDOW1 || p->window_length2 != UNC_WINDOW2)
-        return fail(UNC_ERR_ARG, "seed_len/window lengths must be %d/%d/%d", UNC_SEED_LEN, UNC_WINDOW1, UNC_WINDOW2);
-    if (p->max_paths == 0 || p->max_paths > 65535 || p->max_rep_copy > (uint32_t)MAX_REP_COPY_LIMIT || p->max_consec_stay > 255 ||
-        p->max_events > 65535)
-        return fail(UNC_ERR_ARG, "unsupported parameter value");
+    if (int rc = check_params(p)) return rc;
     // A chunk may hold at most 2 * NORM_LEN samples (3 s at 4 kHz; the reference's default is 1 s).  The detector never fires on two
     // consecutive samples (a peak needs a sample to be recorded and more than window / 2 further ones to be confirmed, and a short-window
     // peak above the threshold resets the long-window detector: event_detector.cpp:221-279), so such a chunk yields at most NORM_LEN events
@@ -1771,37 +1893,13 @@ extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint3
     rt->ix = ix; rt->P = *p; rt->n_channels = n_channels;
     { const char *e = getenv("UNC_RT_PROFILE"); rt->profile = e && e[0] == '1'; }
     rt->team = rt_team_size();
-    const size_t S = n_channels;
     size_t bytes = 0;
-    {
-        PlacementSpacer spacer(S * scratch_slot_bytes(*p, 1u << 20, 2 * p->max_paths, ix->dev) + S * 64 * (size_t)POOL_CHUNK_BYTES);
-        int rc = alloc_scratch(rt->sc, *p, S, 1u << 20, 2 * p->max_paths, &bytes, ix->dev);
-        if (rc) return rc;
-        HIPCHK(hipMemset(rt->sc.v.base, 0, bytes));
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        free_b += spacer.bytes;
-        const char *e = getenv("UNC_RT_POOL_CHUNKS");
-        const RtPoolSize ps = rt_pool_size(ix->seq_len, S, free_b, e ? atol(e) : 0);
-        if (ps.clamped)
-            fprintf(stderr, "Warning: realtime node pool clamped from %zu to %zu chunks (%.1f GB of HBM free)\n", ps.wanted, ps.clamped, (double)free_b / 1e9);
-        rc = alloc_pool(rt->pool, (uint32_t)ps.n_chunks, &bytes);
-        if (rc) return rc;
-    }
-    {
-        int rc = UNC_OK;
-        auto zeroed = [&](auto &buf, size_t count) { if (rc == UNC_OK) rc = alloc_zeroed(buf, count, &bytes); };
-        zeroed(rt->d_chans, S);     zeroed(rt->d_ring, S * NORM_LEN);
-        zeroed(rt->d_desc, S);      zeroed(rt->d_info, S);
-        zeroed(rt->d_ring0, S);     zeroed(rt->d_newread, S);
-        zeroed(rt->d_slotmap, S);   zeroed(rt->d_next, 16);
-        zeroed(rt->d_moff, S + 1);  zeroed(rt->d_results, S);
-        if (rc) return rc;
-    }
+    if (int rc = alloc_rt_slots_and_pool(rt, rt_sizes(*p, ix->dev, n_channels), &bytes)) return rc;
+    if (int rc = alloc_rt_arrays(rt, &bytes)) return rc;
     rt->device_bytes = bytes;
     rt->chans.resize(n_channels);
-    HIPCHK(hipStreamCreate(&rt->stream));
-    for (auto &e : rt->ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(rt->stream.create());
+    HIPCHK(rt->ev.create(3));
     guard.p = nullptr;
     *out = rt;
     return UNC_OK;
@@ -1914,14 +2012,14 @@ static int rt_launch(unc_rt *rt, const RtPlan &plan, const int16_t *raw, const f
     HIPCHK(hipMemcpyAsync(rt->d_slotmap.p, plan.slotmap.data(), n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(rt->d_newread.p, plan.newread.data(), n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(rt->d_moff.p, plan.moff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(rt->ev[0], st));
+    HIPCHK(rt->ev.record(0, st));
     launch_rt_events(d_raw, d_pa, rt->d_desc.p, n, rt->d_chans.p, rt->d_ring.p, rt->P, rt->ix->model_mean, rt->ix->model_stdv, rt->d_info.p,
                      rt->d_ring0.p, st);
-    HIPCHK(hipEventRecord(rt->ev[1], st));
+    HIPCHK(rt->ev.record(1, st));
     MapArgs a = map_args(rt->ix, rt->P, rt->sc.v, rt->pool.v, rt_reads(rt, n), rt->d_results.p, rt->d_next.p);
     a.resume = 1; a.slot_map = rt->d_slotmap.p;      // block b goes on with the read of channel slot_map[b], from the channel's ring
     launch_map(a, n, st, rt->profile, rt->team);
-    HIPCHK(hipEventRecord(rt->ev[2], st));
+    HIPCHK(rt->ev.record(2, st));
     HIPCHK(hipGetLastError());
     rt->h_info.resize(n);
     HIPCHK(hipMemcpyAsync(rt->h_info.data(), rt->d_info.p, n * sizeof(unc_evt_info_t), hipMemcpyDeviceToHost, st));
@@ -1936,8 +2034,8 @@ static int rt_collect(unc_rt *rt, bool launched, hipStream_t st) {
     HIPCHK(hipStreamSynchronize(st));
     rt->ms_events = rt->ms_map = 0;
     if (launched) {
-        HIPCHK(hipEventElapsedTime(&rt->ms_events, rt->ev[0], rt->ev[1]));
-        HIPCHK(hipEventElapsedTime(&rt->ms_map, rt->ev[1], rt->ev[2]));
+        HIPCHK(rt->ev.elapsed(0, 1, &rt->ms_events));
+        HIPCHK(rt->ev.elapsed(1, 2, &rt->ms_map));
     }
     return UNC_OK;
 }
@@ -1984,7 +2082,7 @@ static int rt_process(unc_rt_t *rt, uint32_t n_chunks, const unc_rt_chunk_t *chu
     int rc = rt_check(rt, n_chunks, chunks, raw ? (const void *)raw : (const void *)raw_pa, results);
     if (rc) return rc;
     HIPCHK(hipSetDevice(rt->ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : rt->stream;
+    hipStream_t st = stream ? (hipStream_t)stream : rt->stream.s;
     const RtPlan plan = rt_admit(rt, n_chunks, chunks, results);
     if (!plan.launched.empty() && (rc = rt_launch(rt, plan, raw, raw_pa, on_device, st)) != UNC_OK) return rc;
     if ((rc = rt_collect(rt, !plan.launched.empty(), st)) != UNC_OK) return rc;

@@ -1,5 +1,5 @@
 // Host-side helpers shared by the translation units behind the C ABI (unc_host.cpp, unc_dtw.cpp, unc_align.cpp with unc_refseq.cpp, unc_mask.cpp):
-// the error message of the calling thread, the one owner of device memory, the one owner of timing events and the hand-over of a
+// the error message of the calling thread, the one owner of device memory, the owners of timing events and of a stream, and the hand-over of a
 // per-query output to the host.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -59,7 +59,7 @@ template <class T> struct DevBuf {
     hipError_t reserve(size_t n, size_t slack = 0) { return n <= cap ? hipSuccess : alloc(n, slack); }
 };
 
-// The one owner of timing events outside unc_host.cpp.  create(n) makes events until there are n: a fixed set is made once, a growing
+// The one owner of timing events (the process-wide reference event of unc_host.cpp apart).  create(n) makes events until there are n: a fixed set is made once, a growing
 // one as it grows.  The hipError_t of every member goes through HIPCHK at the call, as DevBuf's do.
 struct DevEvents {
     std::vector<hipEvent_t> e;
@@ -75,6 +75,16 @@ struct DevEvents {
     hipError_t record(size_t i, hipStream_t st) { return hipEventRecord(e[i], st); }
     // milliseconds from event i to event j, once the stream has been waited for
     hipError_t elapsed(size_t i, size_t j, float *ms) { return hipEventElapsedTime(ms, e[i], e[j]); }
+};
+
+// The one owner of a stream, in the same style: made once, destroyed with its holder.
+struct DevStream {
+    hipStream_t s = nullptr;
+    DevStream() = default;
+    DevStream(const DevStream &) = delete;
+    DevStream &operator=(const DevStream &) = delete;
+    ~DevStream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() { return hipStreamCreate(&s); }
 };
 
 // n elements of a device array into h, queued on the stream and not waited for
