@@ -570,6 +570,121 @@ int unc_align_ref_segments_batch(const unc_refseq_t *rs, const unc_params_t *par
  * kernel's variant that writes whole Events (create_event, event_detector.cpp:296-319) */
 int unc_align_segments_last_timing(float *ms);
 
+/* ---- the pore model as an object: replaces PoreModel (src/pore_model.hpp) where the reference honours model_path
+ * (Mapper::load_static, src/mapper.cpp:113-115).  1024 (level_mean, level_stdv) pairs in k-mer order AAAAA..TTTTT (first base most
+ * significant, bp.hpp:69-75).  Immutable once made; calls on one model from several threads are allowed.  A model that an index,
+ * an alignment call or an accumulator's finish was given may be freed as soon as that call has returned. */
+typedef struct unc_model unc_model_t;
+/* the compiled-in r9.4 template pairs: the reference's preset of src/model_r94.inl (mapper.cpp:27,57) through pore_model.hpp:77-103 */
+int unc_model_default(unc_model_t **out);
+/* PoreModel(vector, cmpl), pore_model.hpp:77-103: means_stdvs2048[2 k] and [2 k + 1] are k-mer k's mean and stdv.  UNC_ERR_ARG for
+ * a value that is not finite or a stdv <= 0 (the reference takes anything) */
+int unc_model_from_pairs(const float *means_stdvs2048, unc_model_t **out);
+/* PoreModel(fname, cmpl), pore_model.hpp:108-160: one header line is skipped, then 1024 whitespace-separated `kmer mean stdv`
+ * triples in any k-mer order, the k-mer read as str_to_kmer does (bp.hpp:69-75).  Departures from the reference, which prints an
+ * error and returns a half-loaded model on a short file or a bad k-mer: this call fails with UNC_ERR_ARG and a message (UNC_ERR_IO
+ * for a file that cannot be read) and makes no model, and it also fails on a k-mer string that is not five of ACGT, a duplicate
+ * k-mer, a missing k-mer, anything behind the 1024th triple, a value that is not a finite number and stdv <= 0.  The reference
+ * sums model_mean_ in the file's order (:153); here the pairs are stored by k-mer and every sum runs in k-mer order, which is the
+ * file's order for a file written as the reference's uncalled/conf/r94_5mers.txt is, ascending. */
+int unc_model_load(const char *path, unc_model_t **out);
+/* the header line of the reference's uncalled/conf/r94_5mers.txt ("kmer\tlevel_mean\tlevel_stdv"), then the k-mers ascending as
+ * "%s\t%.9g\t%.9g": nine significant digits name a float exactly, so unc_model_load of the file gives the model back in every bit */
+int unc_model_save(const unc_model_t *m, const char *path);
+int unc_model_pairs(const unc_model_t *m, float *out2048);
+/* lv_means_, lv_vars_x2_, lognorm_denoms_ (init_kmer, pore_model.hpp:58-62), get_means_mean and get_means_stdv (init_stdv, :48-56);
+ * cmpl != 0: row k ^ 0x3FF holds k-mer k (kmer_comp, bp.hpp:77-80), as the mapper's model (mapper.cpp:57) and
+ * unc_index_model_tables; cmpl == 0: as dtw_test's (dtw_test.cpp:79) and unc_dtw_model_tables.  Any output may be NULL */
+int unc_model_tables(const unc_model_t *m, int cmpl, float *means1024, float *vars_x2_1024, float *lognorm1024, float *model_mean,
+                     float *model_stdv);
+void unc_model_free(unc_model_t *m);
+/* Mapper::load_static's `model = PoreModel(PRMS.model_path, true)` (mapper.cpp:113-115): the index's model tables on the host and
+ * on the device become the model's, complemented.  Every later reader sees them: the normaliser's target, unc_match_probs, the
+ * mapping kernels.  Allowed only while no mapper and no realtime object has EVER been made from the index (the index counts what it hands out and
+ * does not count back when one is freed: load the index again for another model):
+ * UNC_ERR_ARG otherwise, and nothing changes.  Waits for the device. */
+int unc_index_set_model(unc_index_t *ix, const unc_model_t *m);
+/* unc_dtw_batch (band == 0) / unc_dtw_band_batch (band > 0) with the costs taken from `model` (NULL: the r9.4 template, as those
+ * calls).  The model's tables are uploaded to `device` once and kept with the model. */
+int unc_dtw_model_batch(int device, const unc_model_t *model, uint32_t n, const float *events, const uint64_t *ev_off,
+                        const uint16_t *kmers, const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band,
+                        uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream);
+
+/* ---- training a model: per-k-mer statistics of the alignments' records, accumulated on the device.  The reference ships its model
+ * as a file (uncalled/conf/r94_5mers.txt read by pore_model.hpp:108-160) and has no trainer; this is the counterpart that makes such
+ * a file from alignments.  Per k-mer the accumulator holds n, S = sum of q and SS = sum of q * q (128 bits), with
+ * q = llrint((double)level * 2^20), round to nearest even.  All integers: the sums do not depend on the order of the records, on how
+ * a batch is cut into rounds, on workspace_bytes or on the caller's room in seg or path.
+ * A record is DROPPED and counted (n_dropped) when its level is not finite or |level| >= 2048 (q * q then stays below 2^62).
+ * A record with shared == 1 (a vertical move: several k-mers on one event) is skipped and not counted, unless the accumulator was
+ * made with UNC_MODEL_KEEP_SHARED.  Queries with UNC_SEG_NONE contribute nothing.
+ * One accumulator may be used by one call at a time.  A call that FAILS after device work has begun (a HIP error, an allocation
+ * that fails in a later round, UNC_ERR_OVERFLOW) may have added the records of the rounds it completed: the accumulator's contents
+ * are then undefined, and the caller resets it (unc_model_acc_reset) and adds again.  A call refused with UNC_ERR_ARG has added nothing. */
+typedef struct unc_model_acc unc_model_acc_t;
+#define UNC_MODEL_KEEP_SHARED 1u
+int unc_model_acc_create(int device, uint32_t flags, unc_model_acc_t **out);
+void unc_model_acc_free(unc_model_acc_t *acc);
+int unc_model_acc_reset(unc_model_acc_t *acc);
+/* the alignment's kernel over n records in host memory: k-mer, level and shared of record i (shared may be NULL: all 0).
+ * UNC_ERR_ARG, before the device is touched, for a k-mer >= 1024.  Returns when the records are added. */
+int unc_model_acc_add(unc_model_acc_t *acc, uint64_t n, const uint16_t *kmers, const float *levels, const uint32_t *shared,
+                      void *stream);
+/* any output may be NULL; S is the signed sum; SS = SS_hi * 2^64 + SS_lo */
+int unc_model_acc_read(const unc_model_acc_t *acc, uint64_t *n1024, int64_t *S1024, uint64_t *SS_lo1024, uint64_t *SS_hi1024,
+                       uint64_t *n_dropped);
+/* kernel milliseconds of k_model_accum in the calling thread's last unc_model_acc_add or alignment call (HIP events on the stream,
+ * summed over the DTW's rounds; 0 for a call without an accumulator) */
+int unc_model_acc_last_timing(float *ms);
+/* host side, exact.  For each k-mer, in unsigned 128-bit integers, V = n * SS - S * S (never negative).  If n < max(min_obs, 2) or
+ * V == 0 the row is the prior's pair and is counted in n_kept_prior (may be NULL).  Otherwise
+ *   mean = (float)((double)S / (double)n / 1048576.0),  stdv = (float)(sqrt((double)V) / (double)n / 1048576.0),
+ * one rounding per written operation, the 128-bit to double conversion round-to-nearest.  prior NULL: the r9.4 template.
+ * UNC_ERR_ARG if n * SS leaves 128 bits (more than 2^64 / 2^62 records of the largest level in one bin: not reachable). */
+int unc_model_acc_finish(const unc_model_acc_t *acc, const unc_model_t *prior, uint32_t min_obs, unc_model_t **out,
+                         uint32_t *n_kept_prior);
+
+/* ---- the general alignment call: one record for everything the four entry points above take, a model and an accumulator.
+ * `size` is sizeof(unc_align_call_t) as the caller was compiled: fields behind it are read as zero.  Rows come either as k-mer
+ * arrays (kmers, km_off: unc_align_batch) or as coordinates (refseq, stretches, optionally kmers_out / kmers_off:
+ * unc_align_ref_batch; `device` is then the reference's) -- exactly one of the two.  segs (may be NULL): the outputs of the
+ * _segments_ calls.  model (may be NULL: the r9.4 template): the DTW's costs, the target over the query's k-mers and the target of
+ * UNC_ALIGN_TARGET_MODEL all come from its tables, not complemented.  accumulate (may be NULL): k_model_accum runs behind
+ * k_align_segments on every round, over the round's records where they lie on the device; the records need not be asked for
+ * (segs NULL, or segs->seg NULL: nothing is copied to the host for it).  The accumulator must be on the call's device.
+ * The four entry points above are fills of this record with model and accumulate NULL. */
+typedef struct {
+    uint32_t size;
+    int device;
+    const unc_params_t *params;
+    const unc_align_opts_t *opts;
+    uint32_t n_reads;
+    int on_device;
+    const int16_t *raw;
+    const uint64_t *offsets;
+    const unc_calib_t *calib;
+    uint32_t n_queries;
+    uint32_t pad;
+    const unc_align_query_t *queries;
+    const uint16_t *kmers;
+    const uint64_t *km_off;
+    const unc_refseq_t *refseq;
+    const unc_ref_stretch_t *stretches;
+    uint16_t *kmers_out;
+    const uint64_t *kmers_off;
+    uint64_t workspace_bytes;
+    unc_align_result_t *results;
+    float *levels;
+    const uint64_t *lev_off;
+    uint32_t *path;
+    const uint64_t *path_off;
+    const unc_align_segments_t *segs;
+    const unc_model_t *model;
+    unc_model_acc_t *accumulate;
+    void *stream;
+} unc_align_call_t;
+int unc_align_call(const unc_align_call_t *call);
+
 /* ---- repeat masking: replaces masking/mask_internal.sh + masking/mask_kmers.py (jellyfish) and masking/mask_external.sh (bowtie,
  * bedtools, samtools), which the reference's masking/README.md recommends for references with intergenic eukaryotic DNA.
  * A reference is one byte per base: 0..3 = A C G T (either case), everything else 4 = "not a base"; a masked base becomes 4.

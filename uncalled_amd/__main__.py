@@ -104,7 +104,8 @@ def worker_cmd(args, list_name, dev):
     """command line of one `--gpus N` worker: everything but `-n`, which is a cap on the whole job (see map_multi_gpu)"""
     cmd = [sys.executable, "-m", "uncalled_amd", "map", args.bwa_prefix, list_name, "--device", str(dev), "--gpus", "1"]
     for opt, val in (("-p", args.idx_preset), ("-l", args.read_list), ("-e", args.max_events),
-                     ("-c", args.max_chunks), ("--chunk-time", args.chunk_time), ("--batch-reads", args.batch_reads)):
+                     ("-c", args.max_chunks), ("--chunk-time", args.chunk_time), ("--batch-reads", args.batch_reads),
+                     ("--model", getattr(args, "model_path", None))):
         if val is not None:
             cmd += [opt, str(val)]
     return cmd
@@ -176,6 +177,8 @@ def map_cmd(args):
             setattr(conf, k, v)
     _assert_exists(conf.bwa_prefix + ".bwt")
     _assert_exists(conf.bwa_prefix + ".uncl")
+    if conf.model_path:
+        _assert_exists(conf.model_path)
     if conf.read_list:
         _assert_exists(conf.read_list)
     pin_world = int(os.environ.get("UNC_PIN_WORLD", "0") or 0)
@@ -306,6 +309,8 @@ def sim_cmd(args):
     conf.active_chs = int(unc.RealtimePool.EVEN if args.even else unc.RealtimePool.ODD if args.odd else unc.RealtimePool.FULL)
     _assert_exists(conf.bwa_prefix + ".bwt")
     _assert_exists(conf.bwa_prefix + ".uncl")
+    if conf.model_path:
+        _assert_exists(conf.model_path)
     pool = None
     try:
         client = unc.ClientSim(conf)
@@ -401,11 +406,13 @@ def write_segments(out, q, row_first, segs, km, model_means):
             float(model_means[km[row]])))
 
 
-def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False, band=0, segments=False):
+def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False, band=0, segments=False, model=None,
+              accumulate=None):
     """The batches behind `dtw`: reads = [(id, int16 samples, (range, offset, digitisation))], queries as load_dtw_queries gives
     them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels, path, SEGMENT records, SEG_INFO record), in the order of
     `reads`: k-mers, levels and path are None without want_paths, the last two None without segments.  The rows of every alignment
-    are made on the device from the queries' coordinates (capi.align_ref_batch); `device` is the index's."""
+    are made on the device from the queries' coordinates (capi.align_ref_batch); `device` is the index's.  model: a capi.Model in
+    place of the r9.4 template; accumulate: a capi.ModelAcc that takes every alignment's records."""
     import numpy as np
     from . import capi
     names = index.seq_names()
@@ -426,7 +433,8 @@ def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, devic
             stretches.append((names.index(q["ref"]), q["ref_st"], q["ref_en"], q["fwd"]))
         t0 = time.time()
         out = capi.align_ref_batch(refseq, raw, offsets, calib, qs, stretches, opts=capi.align_opts(max_events=max_events, band=band),
-                                   levels=want_paths, paths=want_paths, kmers=want_paths, segments=segments)
+                                   levels=want_paths, paths=want_paths, kmers=want_paths, segments=segments, model=model,
+                                   accumulate=accumulate)
         sec = (time.time() - t0) / max(1, len(part))
         none = [None] * len(part)
         out = list(out) if isinstance(out, tuple) else [out]         # results, then what was asked for, in this order
@@ -435,6 +443,62 @@ def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, devic
         segs, infos = (out.pop(0), out.pop(0)) if segments else (none, none)
         for i, (rid, _, _) in enumerate(part):
             yield rid, res[i], sec, kms[i], levs[i], paths[i], segs[i], infos[i]
+
+
+def load_query_reads(unc, fast5, queries):
+    """the reads a query file names, from one fast5 file -> [(id, int16 samples, (range, offset, digitisation))]"""
+    reader = unc.Fast5Reader("", "", 0, max(100, len(queries)))
+    reader.add_fast5(os.path.abspath(fast5))
+    for rid in queries:
+        reader.add_read(rid)            # only the named reads are taken from the file (Fast5Reader::add_read)
+    reads = []
+    while not reader.empty():
+        r = reader.pop_read()
+        if r.id in queries:
+            reads.append((r.id, r.raw_i16, r.calibration))
+    return reads
+
+
+def train_model(index, prefix, reads, queries, start=None, iters=1, min_obs=2, keep_shared=False, band=0, max_events=50000, batch=2048,
+                device=0, report=None):
+    """The iterations behind `train`: every query aligned with the current model (dtw_align, the accumulator on the device, no
+    segment outputs), then the accumulator finished into the next model with the current one as the prior.  -> the last model.
+    report(iteration, records used, records dropped, k-mers kept from the prior, largest change of a mean)"""
+    import numpy as np
+    from . import capi
+    model = start if start is not None else capi.Model.default()
+    acc = capi.ModelAcc(device=device, keep_shared=keep_shared)
+    for it in range(iters):
+        acc.reset()
+        for _ in dtw_align(index, prefix, reads, queries, max_events=max_events, batch=batch, device=device, band=band, model=model,
+                           accumulate=acc):
+            pass
+        n, _, _, _, dropped = acc.read()
+        nxt, kept = acc.finish(model, min_obs)
+        if report:
+            report(it + 1, int(n.sum()), int(dropped), kept, float(np.abs(nxt.pairs()[:, 0] - model.pairs()[:, 0]).max()))
+        model = nxt
+    return model
+
+
+def train_cmd(args):
+    """`train`: a pore model from the alignments of mapped reads, the statistics summed on the GPU"""
+    from . import capi
+    from . import _uncalled_amd as unc
+    for f in (args.index_prefix + ".bwt", args.index_prefix + ".pac", args.fast5, args.paf) + ((args.model,) if args.model else ()):
+        _assert_exists(f)
+    queries = load_paf_queries(args.paf)
+    reads = load_query_reads(unc, args.fast5, queries)
+    clip_paf_queries(queries, reads)
+    index = capi.Index(args.index_prefix, device=args.device)
+
+    def report(it, used, dropped, kept, change):
+        sys.stderr.write("iteration %d: %d records used, %d dropped, %d k-mers kept from the prior, largest mean change %.6g\n" % (
+            it, used, dropped, kept, change))
+
+    model = train_model(index, args.index_prefix, reads, queries, capi.Model.load(args.model) if args.model else None, args.iters,
+                        args.min_obs, args.keep_shared, args.band, args.max_events, args.batch_queries, args.device, report)
+    model.save(args.out)
 
 
 def dtw_cmd(args):
@@ -448,22 +512,17 @@ def dtw_cmd(args):
     if args.segments and args.out_prefix is None:
         sys.stderr.write("Error: --segments needs -o\n")
         sys.exit(1)
+    if args.model:
+        _assert_exists(args.model)
     queries = load_paf_queries(args.queries) if args.paf else load_dtw_queries(args.queries)
-    reader = unc.Fast5Reader("", "", 0, max(100, len(queries)))
-    reader.add_fast5(os.path.abspath(args.fast5))
-    for rid in queries:
-        reader.add_read(rid)            # only the named reads are taken from the file (Fast5Reader::add_read)
-    reads = []
-    while not reader.empty():
-        r = reader.pop_read()
-        if r.id in queries:
-            reads.append((r.id, r.raw_i16, r.calibration))
+    reads = load_query_reads(unc, args.fast5, queries)
     if args.paf:
         clip_paf_queries(queries, reads)
     index = capi.Index(args.index_prefix, device=args.device)
+    model = capi.Model.load(args.model) if args.model else None
     for rid, r, sec, km, lev, path, segs, seg_info in dtw_align(index, args.index_prefix, reads, queries, max_events=args.max_events,
                                                       batch=args.batch_queries, device=args.device, want_paths=args.out_prefix is not None,
-                                                      band=args.band, segments=args.segments):
+                                                      band=args.band, segments=args.segments, model=model):
         st = int(r["status"])
         if st == capi.ALIGN_TOO_MANY:
             sys.stderr.write("Skipping %s\n" % rid)            # dtw_test.cpp:156-159
@@ -476,7 +535,7 @@ def dtw_cmd(args):
             sys.stderr.write("Skipping %s: %s\n" % (rid, "no events left to align" if st == capi.ALIGN_NO_COLUMNS else "status %d" % st))
             continue
         if args.out_prefix is not None:
-            means = capi.dtw_model_tables()[0]
+            means = model.tables(False)[0] if model is not None else capi.dtw_model_tables()[0]
             with open(args.out_prefix + rid + ".txt", "w") as out:
                 for j, i in path[::-1]:                          # from the start of the alignment to its end
                     out.write("%d\t%d\t%s\t%.6g\t%.6g\n" % (j, i, kmer_str(km[i]), lev[j], abs(float(lev[j]) - float(means[km[i]]))))
@@ -523,6 +582,8 @@ def get_parser():
     p.add_argument("-c", "--max-chunks", type=int, default=1000000, help="Will give up on a read after this many chunks have been processed")
     p.add_argument("--chunk-time", type=float, default=1, help="Length of chunks in seconds")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    p.add_argument("--model", dest="model_path", type=str, default=None, help="Pore model file (a header line, then `kmer level_mean level_stdv` "
+                   "for all 1024 5-mers) to map with in place of the built-in r9.4 template")
     p.add_argument("--batch-reads", type=int, default=None, help="Reads per GPU batch (default: four times what the mapper keeps in flight; the first batch is one load)")
     p.add_argument("--gpus", type=int, default=1, help="GPUs of this node to use: one worker process each, fast5 files dealt round-robin")
 
@@ -543,6 +604,8 @@ def get_parser():
     p.add_argument("-e", "--max-events", type=int, default=30000)
     p.add_argument("-c", "--max-chunks", type=int, default=10, help="Will give up on a read after this many chunks have been processed")
     p.add_argument("--chunk-time", type=float, default=1, help="Length of chunks in seconds")
+    p.add_argument("--model", dest="model_path", type=str, default=None, help="Pore model file (a header line, then `kmer level_mean level_stdv` "
+                   "for all 1024 5-mers) to map with in place of the built-in r9.4 template")
     p.add_argument("--duration", type=float, default=None, help="Duration to map real-time run in hours")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
 
@@ -576,6 +639,26 @@ def get_parser():
     p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
 
+    p.add_argument("--model", type=str, default=None, help="Pore model file to align with in place of the built-in r9.4 template")
+
+    p = sp.add_parser("train", help="Train a pore model from the alignments of mapped reads",
+                      description="Every mapped line of PAF is aligned as `dtw --paf` aligns it, with the current model; the normalised level "
+                      "of every reference k-mer on every path is summed per k-mer on the GPU (fixed point: the result does not depend on the "
+                      "order or the batching), and the means and deviations become the next model. A k-mer with fewer than MIN_OBS records "
+                      "keeps its row of the model before. One line per iteration goes to stderr.")
+    p.add_argument("index_prefix", type=str, help="BWA prefix of the reference (needs the .pac)")
+    p.add_argument("fast5", type=str, help="fast5 file that holds the reads")
+    p.add_argument("paf", type=str, help="PAF file, such as `map` writes")
+    p.add_argument("-o", "--out", type=str, required=True, help="The model file to write")
+    p.add_argument("--model", type=str, default=None, help="Model file to start from (default: the built-in r9.4 template)")
+    p.add_argument("--iters", type=int, default=1, help="Iterations of align and re-estimate")
+    p.add_argument("--min-obs", type=int, default=10, help="Records a k-mer needs for a row of its own (at least 2)")
+    p.add_argument("--keep-shared", action="store_true", help="Also count a k-mer whose first event is the previous k-mer's last")
+    p.add_argument("--band", type=int, default=0, help="As in dtw")
+    p.add_argument("--max-events", type=int, default=50000, help="As in dtw")
+    p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
+    p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+
     p = sp.add_parser("mask", help="Mask repeats of a FASTA reference before indexing it (the reference's masking/ scripts, on the GPU)",
                       description="`mask internal` masks the most frequent k-mer of the reference, ITERS times over (mask_internal.sh and "
                       "mask_kmers.py); ties go to the k-mer that sorts first, and the run ends early once no k-mer occurs twice. `mask external` "
@@ -599,6 +682,8 @@ def main(argv=None):
         sim_cmd(args)
     elif args.subcmd == "dtw":
         dtw_cmd(args)
+    elif args.subcmd == "train":
+        train_cmd(args)
     elif args.subcmd == "mask":
         from . import mask
         mask.run(args)

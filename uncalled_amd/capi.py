@@ -161,6 +161,19 @@ class AlignSegments(C.Structure):
 
 
 REF_STRETCH = np.dtype([("rid", "<i4"), ("fwd", "<u4"), ("st", "<u8"), ("en", "<u8")])      # unc_ref_stretch_t
+MODEL_KEEP_SHARED = 1
+
+
+class AlignCall(C.Structure):
+    """unc_align_call_t: the general alignment call's record"""
+    _fields_ = [("size", C.c_uint32), ("device", C.c_int), ("params", C.c_void_p), ("opts", C.c_void_p), ("n_reads", C.c_uint32),
+                ("on_device", C.c_int), ("raw", C.c_void_p), ("offsets", C.c_void_p), ("calib", C.c_void_p), ("n_queries", C.c_uint32),
+                ("pad", C.c_uint32), ("queries", C.c_void_p), ("kmers", C.c_void_p), ("km_off", C.c_void_p), ("refseq", C.c_void_p),
+                ("stretches", C.c_void_p), ("kmers_out", C.c_void_p), ("kmers_off", C.c_void_p), ("workspace_bytes", C.c_uint64),
+                ("results", C.c_void_p), ("levels", C.c_void_p), ("lev_off", C.c_void_p), ("path", C.c_void_p), ("path_off", C.c_void_p),
+                ("segs", C.c_void_p), ("model", C.c_void_p), ("accumulate", C.c_void_p), ("stream", C.c_void_p)]
+
+
 _libs = {}
 
 
@@ -277,6 +290,26 @@ def load(path=None):
         L.unc_align_ref_last_timing.argtypes = [C.POINTER(C.c_float)]
         if hasattr(L, "unc_align_ref_segments_batch"):
             L.unc_align_ref_segments_batch.argtypes = L.unc_align_ref_batch.argtypes[:-1] + [C.POINTER(AlignSegments), vp]
+    if hasattr(L, "unc_model_default"):
+        L.unc_model_default.argtypes = [C.POINTER(vp)]
+        L.unc_model_from_pairs.argtypes = [vp, C.POINTER(vp)]
+        L.unc_model_load.argtypes = [C.c_char_p, C.POINTER(vp)]
+        L.unc_model_save.argtypes = [vp, C.c_char_p]
+        L.unc_model_pairs.argtypes = [vp, vp]
+        L.unc_model_tables.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.unc_model_free.argtypes = [vp]; L.unc_model_free.restype = None
+        L.unc_index_set_model.argtypes = [vp, vp]
+    if hasattr(L, "unc_dtw_model_batch"):
+        L.unc_dtw_model_batch.argtypes = [C.c_int, vp, u32, vp, vp, vp, vp, C.POINTER(DTWParams), u32, u64, vp, vp, vp, vp]
+    if hasattr(L, "unc_model_acc_create"):            # (with the alignment sources)
+        L.unc_model_acc_create.argtypes = [C.c_int, u32, C.POINTER(vp)]
+        L.unc_model_acc_free.argtypes = [vp]; L.unc_model_acc_free.restype = None
+        L.unc_model_acc_reset.argtypes = [vp]
+        L.unc_model_acc_add.argtypes = [vp, u64, vp, vp, vp, vp]
+        L.unc_model_acc_read.argtypes = [vp, vp, vp, vp, vp, C.POINTER(u64)]
+        L.unc_model_acc_last_timing.argtypes = [C.POINTER(C.c_float)]
+        L.unc_model_acc_finish.argtypes = [vp, vp, u32, C.POINTER(vp), C.POINTER(u32)]
+        L.unc_align_call.argtypes = [C.POINTER(AlignCall)]
     if hasattr(L, "unc_mask_create"):                 # (the emulator builds of the other features do not hold the masking entry points)
         L.unc_mask_create.argtypes = [C.c_int, vp, u64, vp, u32, C.POINTER(vp)]
         L.unc_mask_free.argtypes = [vp]; L.unc_mask_free.restype = None
@@ -299,6 +332,112 @@ def default_params(lib=None):
     p = Params()
     (lib or load()).unc_params_default(C.byref(p))
     return p
+
+
+class Model:
+    """A pore model (unc_model_t): 1024 (level_mean, level_stdv) pairs in k-mer order.  PoreModel of the reference (pore_model.hpp)."""
+
+    def __init__(self, handle, lib):
+        self.L, self.h = lib, handle
+
+    @classmethod
+    def _made(cls, L, call, *args):
+        h = C.c_void_p()
+        _check(L, call(*args, C.byref(h)))
+        return cls(h, L)
+
+    @classmethod
+    def default(cls, lib=None):
+        """the compiled-in r9.4 template model"""
+        L = lib or load()
+        return cls._made(L, L.unc_model_default)
+
+    @classmethod
+    def load(cls, path, lib=None):
+        """a file as the reference's r94_5mers.txt: a header line, then `kmer mean stdv` for all 1024 k-mers in any order"""
+        L = lib or load()
+        return cls._made(L, L.unc_model_load, str(path).encode())
+
+    @classmethod
+    def from_pairs(cls, pairs, lib=None):
+        """pairs: float32 (1024, 2), or 2048 flat: mean and stdv of every k-mer"""
+        L = lib or load()
+        p = np.ascontiguousarray(pairs, dtype=np.float32).ravel()
+        if p.size != 2048:
+            raise ValueError("1024 (mean, stdv) pairs are needed")
+        return cls._made(L, L.unc_model_from_pairs, p.ctypes.data)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.unc_model_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def save(self, path):
+        _check(self.L, self.L.unc_model_save(self.h, str(path).encode()))
+
+    def pairs(self):
+        out = np.empty((1024, 2), dtype=np.float32)
+        _check(self.L, self.L.unc_model_pairs(self.h, out.ctypes.data))
+        return out
+
+    def tables(self, cmpl):
+        """(means, vars_x2, lognorm, model_mean, model_stdv); cmpl=True: complemented, as Index.model_tables(); False: as dtw_model_tables()"""
+        a, b, c = (np.empty(1024, dtype=np.float32) for _ in range(3))
+        mm, ms = C.c_float(), C.c_float()
+        _check(self.L, self.L.unc_model_tables(self.h, 1 if cmpl else 0, a.ctypes.data, b.ctypes.data, c.ctypes.data, C.byref(mm), C.byref(ms)))
+        return a, b, c, mm.value, ms.value
+
+
+class ModelAcc:
+    """A training accumulator on one device (unc_model_acc_t): per k-mer n, S = sum q, SS = sum q * q, q = rint(level * 2^20), all
+    integers.  Filled by add() or by align_batch / align_ref_batch with accumulate=; finish() makes the Model."""
+
+    def __init__(self, device=0, keep_shared=False, lib=None):
+        self.L = lib or load()
+        h = C.c_void_p()
+        _check(self.L, self.L.unc_model_acc_create(int(device), MODEL_KEEP_SHARED if keep_shared else 0, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.unc_model_acc_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def add(self, kmers, levels, shared=None, stream=None):
+        km = np.ascontiguousarray(kmers, dtype=np.uint16).ravel()
+        lv = np.ascontiguousarray(levels, dtype=np.float32).ravel()
+        sh = None if shared is None else np.ascontiguousarray(shared, dtype=np.uint32).ravel()
+        if km.size != lv.size or (sh is not None and sh.size != km.size):
+            raise ValueError("as many levels (and shared flags) as k-mers are needed")
+        _check(self.L, self.L.unc_model_acc_add(self.h, km.size, km.ctypes.data, lv.ctypes.data, None if sh is None else sh.ctypes.data, stream))
+
+    def read(self):
+        """-> (n uint64[1024], S int64[1024], SS_lo uint64[1024], SS_hi uint64[1024], n_dropped)"""
+        n, lo, hi = (np.empty(1024, dtype=np.uint64) for _ in range(3))
+        S = np.empty(1024, dtype=np.int64)
+        dropped = C.c_uint64()
+        _check(self.L, self.L.unc_model_acc_read(self.h, n.ctypes.data, S.ctypes.data, lo.ctypes.data, hi.ctypes.data, C.byref(dropped)))
+        return n, S, lo, hi, dropped.value
+
+    def reset(self):
+        _check(self.L, self.L.unc_model_acc_reset(self.h))
+
+    def finish(self, prior=None, min_obs=2):
+        """-> (Model, k-mers kept from the prior): a k-mer with fewer than max(min_obs, 2) records, or without spread, keeps the
+        prior's pair (None: the r9.4 template's)"""
+        h, kept = C.c_void_p(), C.c_uint32()
+        _check(self.L, self.L.unc_model_acc_finish(self.h, prior.h if prior is not None else None, int(min_obs), C.byref(h), C.byref(kept)))
+        return Model(h, self.L), kept.value
+
+    def last_timing(self):
+        """kernel milliseconds of k_model_accum in the calling thread's last add() or alignment call"""
+        ms = C.c_float()
+        self.L.unc_model_acc_last_timing(C.byref(ms))
+        return ms.value
 
 
 class Index:
@@ -347,6 +486,10 @@ class Index:
         self.L.unc_index_model_tables(self.h, a.ctypes.data, b.ctypes.data, c.ctypes.data, C.byref(mm), C.byref(ms))
         return a, b, c, mm.value, ms.value
 
+    def set_model(self, model):
+        """unc_index_set_model: the index maps with `model` from now on; refused once a Mapper or Realtime was made from the index"""
+        _check(self.L, self.L.unc_index_set_model(self.h, model.h))
+
     def get_neighbor(self, starts, ends, bases):
         s = np.ascontiguousarray(starts, dtype=np.uint64)
         e = np.ascontiguousarray(ends, dtype=np.uint64)
@@ -387,13 +530,14 @@ def dtw_model_tables(lib=None):
     return a, b, c
 
 
-def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, device=0, stream=None, lib=None, full=False, band=0):
+def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, device=0, stream=None, lib=None, full=False, band=0, model=None):
     """unc_dtw_batch: DTWr94p / DTWr94d (dtw.hpp) of events_list[a] (columns) against kmers_list[a] (rows) for every a, on the GPU.
     -> (scores float32[n], mean scores float32[n], paths): paths[a] is DTW::get_path() as an (len, 2) uint32 array of (event, k-mer)
     pairs, end cell first (None with paths=False, and for an alignment that was not computed: status DTW_TOO_LARGE or
     DTW_BAND_TOO_NARROW).  full=True returns the DTW_RESULT records (score, mean_score, path_len, status) in place of the first two.
     band=W > 0: unc_dtw_band_batch, the same within a band of half-width W around the diagonal (global alignment only); with
-    status DTW_LEFT_BAND paths[a] holds the pairs up to the last cell in the band."""
+    status DTW_LEFT_BAND paths[a] holds the pairs up to the last cell in the band.  model: a Model whose tables the costs read
+    (unc_dtw_model_batch; None: the r9.4 template)."""
     L = lib or load()
     n = len(events_list)
     if n != len(kmers_list):
@@ -414,7 +558,10 @@ def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, de
         path_off = np.cumsum([0] + [max(0, e.size + k.size - 1) for e, k in zip(evs, kms)]).astype(np.uint64)
         path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
     args = (int(workspace_bytes), res.ctypes.data, path.ctypes.data if paths else None, path_off.ctypes.data if paths else None, stream)
-    if band:
+    if model is not None:
+        _check(L, L.unc_dtw_model_batch(int(device), model.h, n, ev.ctypes.data, ev_off.ctypes.data, km.ctypes.data, km_off.ctypes.data,
+                                        C.byref(params), int(band), *args))
+    elif band:
         _check(L, L.unc_dtw_band_batch(int(device), n, ev.ctypes.data, ev_off.ctypes.data, km.ctypes.data, km_off.ctypes.data,
                                        C.byref(params), int(band), *args))
     else:
@@ -483,11 +630,12 @@ class _SegOut:
 
 
 def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths,
-           on_device, stream, segments, events):
+           on_device, stream, segments, events, model=None, accumulate=None, rec_rows=None):
     """what align_batch and align_ref_batch share: the ALIGN_QUERY records, raw on the host or the device, the room per query, the buffers
     of levels and paths, _SegOut, the call and the tuple it returns.  entries: the entry point's name without and with segments;
     first: its first argument; rows_args: what names the rows, after the queries; n_rows: the rows of every query; tap_args: what
-    follows lev_off; tap: None, or what makes the list that goes between the paths and the segments' outputs"""
+    follows lev_off; tap: None, or what makes the list that goes between the paths and the segments' outputs.  With a model or an
+    accumulator the call goes through unc_align_call: rec_rows are then the fields of its record that name the rows"""
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     calib = np.ascontiguousarray(calib, dtype=CALIB)
     n_reads, n = offsets.size - 1, len(queries)
@@ -518,9 +666,24 @@ def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, ca
             *rows_args, int(workspace_bytes), res.ctypes.data,
             lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None, *tap_args,
             path.ctypes.data if paths else None, path_off.ctypes.data if paths else None)
-    so = None
-    if segments or events:
-        so = _SegOut(n_rows, room, segments, events)
+    so = _SegOut(n_rows, room, segments, events) if segments or events else None
+    if model is not None or accumulate is not None:
+        rec = AlignCall()
+        rec.size = C.sizeof(AlignCall)
+        rec.params = C.cast(C.pointer(params), C.c_void_p) if params is not None else None
+        rec.opts = C.cast(C.pointer(opts), C.c_void_p) if opts is not None else None
+        rec.n_reads, rec.on_device, rec.raw, rec.offsets, rec.calib = n_reads, 1 if on_device else 0, raw_ptr, offsets.ctypes.data, calib.ctypes.data
+        rec.n_queries, rec.queries, rec.workspace_bytes, rec.results = n, qs.ctypes.data, int(workspace_bytes), res.ctypes.data
+        rec.levels, rec.lev_off = (lev.ctypes.data, lev_off.ctypes.data) if levels else (None, None)
+        rec.path, rec.path_off = (path.ctypes.data, path_off.ctypes.data) if paths else (None, None)
+        rec.segs = C.cast(C.pointer(so.arg), C.c_void_p) if so is not None else None
+        rec.model = model.h if model is not None else None
+        rec.accumulate = accumulate.h if accumulate is not None else None
+        rec.stream = stream
+        for k, v in rec_rows.items():
+            setattr(rec, k, v)
+        _check(L, L.unc_align_call(C.byref(rec)))
+    elif so is not None:
         _check(L, getattr(L, entries[1])(*args, C.byref(so.arg), stream))
     else:
         _check(L, getattr(L, entries[0])(*args, stream))
@@ -539,7 +702,7 @@ def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, ca
 
 
 def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
-                on_device=False, device=0, stream=None, lib=None, segments=False, events=False):
+                on_device=False, device=0, stream=None, lib=None, segments=False, events=False, model=None, accumulate=None):
     """unc_align_batch: the pipeline of the reference's dtw_test (slice -> events -> stall mask -> normalisation to the k-mers'
     levels -> DTW) for a batch of queries on the GPU.  raw / offsets / calib: the reads as Mapper.map_batch takes them (raw: an int16
     array, or with on_device=True a device address).  queries: (read index, smp_st, smp_en) triples, smp_en == 0 = to the read's end;
@@ -547,7 +710,9 @@ def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None
     tgt_mean, tgt_stdv, scale, shift, status); with levels=True and / or paths=True also a list of the normalised columns per query and
     a list of paths as dtw_batch returns them (None for a query that was not aligned).  segments=True (unc_align_segments_batch): then
     also a list of SEGMENT arrays -- per query one record per k-mer on its path, in the read's sample coordinates -- and the SEG_INFO
-    records (row_first, n_rows, status); events=True: then also a list of EVENT arrays, the query's columns as events."""
+    records (row_first, n_rows, status); events=True: then also a list of EVENT arrays, the query's columns as events.
+    model: a Model in place of the r9.4 template (costs and targets); accumulate: a ModelAcc that receives every record of the
+    alignments' paths, asked for or not (unc_align_call)."""
     if len(queries) != len(kmers_list):
         raise ValueError("as many k-mer arrays as queries are needed")
     kms = [np.ascontiguousarray(k, dtype=np.uint16).ravel() for k in kmers_list]
@@ -555,7 +720,7 @@ def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None
     km = np.concatenate(kms + [np.zeros(1, np.uint16)])         # (one element more: a valid address for the library's own argument checks)
     return _align(lib or load(), ("unc_align_batch", "unc_align_segments_batch"), int(device), (km.ctypes.data, km_off.ctypes.data),
                   [k.size for k in kms], (), None, raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths, on_device, stream,
-                  segments, events)
+                  segments, events, model, accumulate, dict(device=int(device), kmers=km.ctypes.data, km_off=km_off.ctypes.data))
 
 
 def align_segments_last_timing(lib=None):
@@ -706,12 +871,12 @@ def ref_kmers_batch(refseq, stretches, stream=None):
 
 
 def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
-                    kmers=False, on_device=False, stream=None, segments=False, events=False):
+                    kmers=False, on_device=False, stream=None, segments=False, events=False, model=None, accumulate=None):
     """unc_align_ref_batch: align_batch with coordinates in place of k-mer arrays.  stretches[q] = (rid, st, en, fwd) names the bases
     whose k-mers are query q's rows; they are made on the GPU (the index's) and reach the host only with kmers=True.  Everything else
     as align_batch, and so are the results, bit for bit, for the k-mers ref_kmers gives for the same stretches.  -> ALIGN_RESULT
     records, then, as asked for, the lists of levels, of paths and of k-mers per query, and what segments=True / events=True add
-    (unc_align_ref_segments_batch; as in align_batch, after everything else)."""
+    (unc_align_ref_segments_batch; as in align_batch, after everything else).  model, accumulate: as in align_batch."""
     if len(queries) != len(stretches):
         raise ValueError("as many stretches as queries are needed")
     ss = _stretches(stretches)
@@ -721,7 +886,9 @@ def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, 
     return _align(refseq.L, ("unc_align_ref_batch", "unc_align_ref_segments_batch"), refseq.h, (ss.ctypes.data,), counts,
                   (km.ctypes.data, km_off.ctypes.data) if kmers else (None, None),
                   (lambda: [km[int(km_off[q]):int(km_off[q + 1])].copy() for q in range(len(counts))]) if kmers else None,
-                  raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths, on_device, stream, segments, events)
+                  raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths, on_device, stream, segments, events, model,
+                  accumulate, dict(refseq=refseq.h, stretches=ss.ctypes.data, kmers_out=km.ctypes.data if kmers else None,
+                                   kmers_off=km_off.ctypes.data if kmers else None))
 
 
 def align_ref_last_timing(lib=None):

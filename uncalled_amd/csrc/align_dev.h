@@ -79,12 +79,14 @@ struct AlignRows {
 };
 // What the four entry points (unc_align_batch, unc_align_segments_batch, unc_align_ref_batch, unc_align_ref_segments_batch) share of
 // their parameters, under the names include/uncalled_hip.h gives them.  Each fills one, once.  who: the entry point's name, for the
-// messages.  segs (null: none): the outputs of the two _segments_ entry points
+// messages.  segs (null: none): the outputs of the two _segments_ entry points.  model and acc: unc_align_call's (uncalled_hip.h)
 struct AlignCall {
     const char *who; int device; const unc_params_t *params; const unc_align_opts_t *opts;
     uint32_t n_reads; const int16_t *raw; const uint64_t *offsets; const unc_calib_t *calib; int on_device;
     uint32_t n_queries; const unc_align_query_t *queries; uint64_t workspace_bytes; unc_align_result_t *results;
     float *levels; const uint64_t *lev_off; uint32_t *path; const uint64_t *path_off; void *stream; const unc_align_segments_t *segs;
+    const unc_model_t *model;       // null: the template model
+    unc_model_acc_t *acc;           // null: no accumulator
 };
 int align_run(const AlignCall &c, AlignRows &rows);
 }  // namespace unc

@@ -5,6 +5,8 @@
 
 #include "../../include/uncalled_hip.h"
 
+struct unc_model;
+
 namespace unc {
 
 constexpr uint32_t DTW_LANES = 64;          // rows of a strip: one per lane
@@ -91,15 +93,20 @@ void launch_dtw(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st)
 // hook (may be null): every alignment's path is then kept whole on the device (rows + cols - 1 pairs of room, whatever the caller's),
 // and after each round's kernel, before anything is copied out and the next round reuses the buffers, the hook is handed the round.
 // What the caller gets is as without it: path_cap pairs at most, and UNC_DTW_PATH_TRUNCATED by path_cap.
+// model (may be null: the template's, kept per device for the life of the process): whose tables the costs are read from.
 struct DtwRoundHook {
     virtual ~DtwRoundHook() = default;
-    // d_jobs: the round's jobs as the kernel saw them (path_cap = rows + cols - 1); d_res is indexed by DtwJob::out
-    virtual int round(const DtwJob *d_jobs, uint32_t n_jobs, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) = 0;
+    // d_jobs: the round's jobs as the kernel saw them (path_cap = rows + cols - 1); n_rows: the sum of their rows; d_res is indexed
+    // by DtwJob::out
+    virtual int round(const DtwJob *d_jobs, uint32_t n_jobs, uint64_t n_rows, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) = 0;
 };
 int dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
                    const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                   const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook = nullptr);
-// the template model's 3 x 1024 floats on `device` (uploaded once per device) and on the host
+                   const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook = nullptr, const unc_model *model = nullptr);
+// the template model's 3 x 1024 floats on `device` (uploaded once per device) and on the host; dtw_model_default: with its mean and
+// deviation over all k-mers (unc_model.h)
 int dtw_model_device(int device, const float **out);
 const float *dtw_model_host();
+struct ModelTables;
+const ModelTables &dtw_model_default();
 }  // namespace unc

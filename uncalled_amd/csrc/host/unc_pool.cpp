@@ -283,6 +283,17 @@ bool write_fast5(const std::string &path, const std::vector<RawRead> &reads, boo
     return true;
 }
 
+// Mapper::load_static, mapper.cpp:113-115: a model_path replaces the index's model before anything is made from the index.
+// Empty: the compiled-in r9.4 template stays
+int index_set_model_path(unc_index_t *ix, const std::string &model_path) {
+    if (model_path.empty()) return UNC_OK;
+    unc_model_t *m = nullptr;
+    if (int rc = unc_model_load(model_path.c_str(), &m)) return rc;
+    const int rc = unc_index_set_model(ix, m);
+    unc_model_free(m);
+    return rc;
+}
+
 // ------------------------------------------------------------------ MapPool (map_pool.cpp:28-158), batched on one GPU
 MapPool::MapPool(const Conf &conf) : conf_(conf), reader_(conf) {
     unc_params_t p;
@@ -293,7 +304,7 @@ MapPool::MapPool(const Conf &conf) : conf_(conf), reader_(conf) {
     p.sample_rate = conf.sample_rate;
     bp_per_samp_ = p.bp_per_sec / p.sample_rate;
     if (unc_index_load(conf.bwa_prefix.c_str(), conf.idx_preset.c_str(), conf.device, &ix_) != UNC_OK ||
-        unc_mapper_create(ix_, &p, nullptr, &mapper_) != UNC_OK) {
+        index_set_model_path(ix_, conf.model_path) != UNC_OK || unc_mapper_create(ix_, &p, nullptr, &mapper_) != UNC_OK) {
         std::cerr << "Error: " << unc_last_error() << "\n";   // Mapper::load_static aborts on a bad index, mapper.cpp:118-127
         abort();
     }

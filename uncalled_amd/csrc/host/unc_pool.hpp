@@ -35,6 +35,9 @@ struct Conf {
     float duration = 0;              // hours (0 = until the source runs dry)
     uint32_t max_active_reads = 512;
 };
+// model_path (Mapper::load_static, mapper.cpp:113-115): loads the model file and sets it on an index nothing was made from yet;
+// an empty path leaves the r9.4 template.  Returns the C ABI's status
+int index_set_model_path(unc_index_t *ix, const std::string &model_path);
 
 class Paf {
 public:

@@ -62,7 +62,7 @@ RealtimePool::RealtimePool(const Conf &conf) : conf_(conf), chans_(conf.num_chan
     prms_.chunk_time = conf.chunk_time;
     prms_.sample_rate = conf.sample_rate;
     if (unc_index_load(conf.bwa_prefix.c_str(), conf.idx_preset.c_str(), conf.device, &ix_) != UNC_OK ||
-        unc_rt_create(ix_, &prms_, conf.num_channels, &rt_) != UNC_OK) {
+        index_set_model_path(ix_, conf.model_path) != UNC_OK || unc_rt_create(ix_, &prms_, conf.num_channels, &rt_) != UNC_OK) {
         std::cerr << "Error: " << unc_last_error() << "\n";   // Mapper::load_static aborts on a bad index, mapper.cpp:118-127
         abort();
     }

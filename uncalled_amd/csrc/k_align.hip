@@ -181,3 +181,5 @@ void launch_align_prep(const AlignPrep &p, hipStream_t st) {
 #include "k_refseq.hip"
 // and so is k_align_segments, which collapses a round's paths to one record per k-mer
 #include "k_segments.hip"
+// and k_model_accum, which sums a round's records per k-mer into a training accumulator
+#include "k_model.hip"

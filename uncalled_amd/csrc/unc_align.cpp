@@ -13,8 +13,10 @@
 
 #include "align_dev.h"
 #include "dtw_dev.h"
+#include "model_dev.h"
 #include "unc_host_util.h"
 #include "unc_kernels.h"
+#include "unc_model.h"
 
 using namespace unc;
 
@@ -33,35 +35,42 @@ extern "C" int unc_align_last_timing(float *ms4) {
     return UNC_OK;
 }
 
-// PoreModel(vector, cmpl=false): model_mean_ is the float sum of the means in table order over the count (pore_model.hpp:82-99),
-// init_stdv (:48-56) a float accumulator of double squares of float differences
+// PoreModel::get_means_mean / get_means_stdv of the template model, not complemented (the one builder, unc_model.h)
 extern "C" void unc_align_model_target(float *mean, float *stdv) {
-    const float *mu = dtw_model_host();
-    float s = 0;
-    for (uint32_t k = 0; k < (uint32_t)UNC_NKMER; ++k) s = s + mu[k];
-    s = s / (float)UNC_NKMER;
-    float acc = 0;
-    for (uint32_t k = 0; k < (uint32_t)UNC_NKMER; ++k) {
-        const float d = mu[k] - s;
-        acc = (float)((double)acc + (double)d * (double)d);
-    }
-    if (mean) *mean = s;
-    if (stdv) *stdv = sqrtf(acc / (float)UNC_NKMER);
+    const ModelTables &t = dtw_model_default();
+    if (mean) *mean = t.mean;
+    if (stdv) *stdv = t.stdv;
 }
 
+namespace unc {
+// unc_model_acc.cpp (included below): what the alignment needs of an accumulator
+void model_acc_set_timing(float ms);
+int model_acc_device(const unc_model_acc *acc);
+void model_acc_args(unc_model_acc *acc, ModelAccum *a);
+}  // namespace unc
+
 namespace {
-// k_align_segments on every round of the DTW, while the round's paths are on the device (the next round reuses their buffer)
+// k_align_segments on every round of the DTW, while the round's paths are on the device (the next round reuses their buffer), and
+// with an accumulator k_model_accum behind it, over the records the round has just written
 struct SegmentsHook : DtwRoundHook {
     SegArgs args{};
-    DevEvents ev;       // (timing only) two per round
-    int round(const DtwJob *d_jobs, uint32_t n_jobs, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) override {
+    bool accumulate = false;
+    ModelAccum acc{};   // (with accumulate) everything but the round's jobs
+    DevEvents ev;       // (timing only) two per round, three with an accumulator
+    int round(const DtwJob *d_jobs, uint32_t n_jobs, uint64_t n_rows, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) override {
         const size_t i = ev.e.size();
-        HIPCHK(ev.create(i + 2));
+        HIPCHK(ev.create(i + (accumulate ? 3 : 2)));
         args.jobs = d_jobs; args.n_jobs = n_jobs; args.path = d_path; args.res = d_res;
         HIPCHK(ev.record(i, st));
         launch_align_segments(args, st);
         HIPCHK(hipGetLastError());
         HIPCHK(ev.record(i + 1, st));
+        if (accumulate) {
+            acc.jobs = d_jobs; acc.n_jobs = n_jobs;
+            launch_model_accum(acc, n_rows, st);
+            HIPCHK(hipGetLastError());
+            HIPCHK(ev.record(i + 2, st));
+        }
         return UNC_OK;
     }
 };
@@ -105,6 +114,8 @@ struct AlignRun : AlignCall {
     DevBuf<unc_seg_info_t> d_seginfo;
 
     AlignRun(const AlignCall &c, AlignRows &r) : AlignCall(c), rows(r) {}
+    // the call's model on the host: the given one, or the template (both not complemented)
+    const ModelTables &tables() const { return model ? model->fwd : dtw_model_default(); }
 
     // ---- arguments: everything is checked before the device is touched: this step makes no HIP call, and every later one may.
     // Then every query's checks in their order, and where its slice, its columns and its k-mers lie
@@ -114,9 +125,11 @@ struct AlignRun : AlignCall {
         if (levels && !lev_off) return fail(UNC_ERR_ARG, "%s: levels without lev_off", who);
         if (segs && segs->seg && !segs->seg_off) return fail(UNC_ERR_ARG, "%s: seg without seg_off", who);
         if (segs && segs->events && !segs->evt_off) return fail(UNC_ERR_ARG, "%s: events without evt_off", who);
-        want_seg = segs && (segs->seg || segs->info);
+        want_seg = (segs && (segs->seg || segs->info)) || acc;
         want_tap = segs && segs->events;
         if (device < 0 || device >= DTW_MAX_DEVICES) return fail(UNC_ERR_ARG, "%s: device %d", who, device);
+        if (acc && model_acc_device(acc) != device)
+            return fail(UNC_ERR_ARG, "%s: the accumulator is on device %d, the call on device %d", who, model_acc_device(acc), device);
         memset(&O, 0, sizeof O);
         if (opts) O = *opts;
         if (O.flags & ~(UNC_ALIGN_DTW_PARAMS | UNC_ALIGN_NO_MASK | UNC_ALIGN_RAW | UNC_ALIGN_TARGET_MODEL))
@@ -136,6 +149,7 @@ struct AlignRun : AlignCall {
         // (the timings are zeroed here: after the options' and parameters' checks, before a batch of no queries returns)
         memset(g_align_ms, 0, sizeof g_align_ms);
         g_seg_ms = 0;
+        model_acc_set_timing(0);
         if (n_queries == 0) return UNC_OK;
         for (uint32_t i = 0; i < n_reads; ++i)
             if (offsets[i + 1] < offsets[i]) return fail(UNC_ERR_ARG, "%s: offsets must ascend", who);
@@ -175,7 +189,7 @@ struct AlignRun : AlignCall {
     // the spans between the events hold kernels only
     int upload() {
         HIPCHK(hipSetDevice(device));
-        if (int rc = dtw_model_device(device, &d_model)) return rc;
+        if (int rc = model ? model_device(model, device, &d_model) : dtw_model_device(device, &d_model)) return rc;
         d_raw = raw + offsets[0];
         if (!on_device) {
             const uint64_t n_smp = offsets[n_reads] - offsets[0];
@@ -199,7 +213,7 @@ struct AlignRun : AlignCall {
             HIPCHK(hipMemcpyAsync(d_calib.p, qcal.data(), qcal.size() * sizeof(unc_calib_t), hipMemcpyHostToDevice, st));
             rd.raw = d_gather.p; rd.offsets = d_goff.p; rd.calib = d_calib.p; rd.means = d_means.p; rd.moff = d_moff.p; rd.info = d_info.p;
             rd.n_reads = n_queries;
-            unc_align_model_target(&rd.tgt_mean, &rd.tgt_stdv);       // (k_events' own scale and shift are not used here)
+            rd.tgt_mean = tables().mean; rd.tgt_stdv = tables().stdv;       // (k_events' own scale and shift are not used here)
         }
         HIPCHK(ev.create(4));
         return UNC_OK;
@@ -227,7 +241,7 @@ struct AlignRun : AlignCall {
         ap.means = d_means.p;
         ap.levels = d_levels.p;
         ap.kmers = d_kmers; ap.model = d_model;
-        unc_align_model_target(&ap.model_mean, &ap.model_stdv);
+        ap.model_mean = tables().mean; ap.model_stdv = tables().stdv;
         ap.rec = d_rec.p;
         ap.col_evt = whole_events ? d_col_evt.p : nullptr;
         launch_align_prep(ap, st);
@@ -271,13 +285,16 @@ struct AlignRun : AlignCall {
     }
 
     // f. (with segments) what k_align_segments needs on every round's paths.  The records' layout on the device, from 0: a query's room
-    // there is the caller's, or its k-mers if those are fewer (a path has no more rows); without seg no room at all, and info alone is filled
+    // there is the caller's, or its k-mers if those are fewer (a path has no more rows); without seg no room at all, and info alone is
+    // filled.  With an accumulator the room is the query's k-mers whatever the caller's: every record is made, for k_model_accum
     int set_up_segments() {
+        const bool caller_seg = segs && segs->seg;
         seg_off.assign((size_t)n_queries + 1, 0);
         smp_st.resize(n_queries);
         for (uint32_t q = 0; q < n_queries; ++q) {
             smp_st[q] = queries[q].smp_st;
-            seg_off[q + 1] = seg_off[q] + (segs->seg ? std::min<uint64_t>(segs->seg_off[q + 1] - segs->seg_off[q], hq[q].n_km) : 0);
+            const uint64_t room = caller_seg ? std::min<uint64_t>(segs->seg_off[q + 1] - segs->seg_off[q], hq[q].n_km) : 0;
+            seg_off[q + 1] = seg_off[q] + (acc ? hq[q].n_km : room);
         }
         HIPCHK(d_seg.alloc(seg_off[n_queries])); HIPCHK(d_seginfo.alloc(n_queries));
         HIPCHK(d_seg_off.alloc(seg_off.size())); HIPCHK(d_smp_st.alloc(n_queries));
@@ -288,20 +305,32 @@ struct AlignRun : AlignCall {
         sa.queries = d_q.p; sa.rec = d_rec.p;
         sa.events = d_events.p; sa.means = d_means.p; sa.col_evt = d_col_evt.p;
         sa.smp_st = d_smp_st.p; sa.seg_off = d_seg_off.p; sa.seg = d_seg.p; sa.info = d_seginfo.p;
+        if (acc) {
+            hook.accumulate = true;
+            model_acc_args(acc, &hook.acc);
+            hook.acc.kmers = d_kmers; hook.acc.info = d_seginfo.p; hook.acc.queries = d_q.p; hook.acc.seg_off = d_seg_off.p; hook.acc.seg = d_seg.p;
+        }
         return UNC_OK;
     }
 
     // the DTW's rounds (with segments: k_align_segments on each), their times, and the results of the queries that were in one
     int run_dtw() {
         if (int rc = dtw_run_device(device, n_queries, d_levels.p, d_kmers, jobs.data(), skip.data(), &prm, O.band, workspace_bytes, dres.data(),
-                                    path, path_off, st, want_seg ? &hook : nullptr))
+                                    path, path_off, st, want_seg ? &hook : nullptr, model))
             return rc;
         (void)unc_dtw_last_timing(&g_align_ms[3], nullptr, nullptr);
-        for (size_t i = 0; i + 1 < hook.ev.e.size(); i += 2) {       // (g_seg_ms is 0 since check_and_lay_out)
+        const size_t per_round = hook.accumulate ? 3 : 2;
+        float acc_ms = 0;
+        for (size_t i = 0; i + per_round <= hook.ev.e.size(); i += per_round) {       // (g_seg_ms is 0 since check_and_lay_out)
             float t = 0;
             HIPCHK(hook.ev.elapsed(i, i + 1, &t));
             g_seg_ms += t;
+            if (hook.accumulate) {
+                HIPCHK(hook.ev.elapsed(i + 1, i + 2, &t));
+                acc_ms += t;
+            }
         }
+        model_acc_set_timing(acc_ms);
         for (uint32_t q = 0; q < n_queries; ++q) {
             if (skip[q]) continue;
             results[q].dtw = dres[q];
@@ -313,7 +342,8 @@ struct AlignRun : AlignCall {
     // ---- the outputs on request: one copy of a whole device array each, dealt out per query on the host (deal_out, unc_host_util.h),
     // so that nothing outside a query's count is written
     int hand_over() {
-        if (want_seg) {     // the rows' counts first, then the records by them
+        const bool caller_seg = segs && segs->seg;
+        if (segs && (segs->seg || segs->info)) {     // the rows' counts first, then the records by them
             std::vector<unc_seg_info_t> info;
             HIPCHK(download(info, d_seginfo.p, n_queries, st));
             HIPCHK(hipStreamSynchronize(st));
@@ -322,12 +352,15 @@ struct AlignRun : AlignCall {
                 unc_seg_info_t &inf = info[q];
                 // (a query that was in no round, or whose path has no start, has no rows: its record on the device may never have been written)
                 if (skip[q] || (s != UNC_DTW_OK && s != UNC_DTW_PATH_TRUNCATED)) { inf.row_first = 0; inf.n_rows = 0; inf.status = UNC_SEG_NONE; inf.pad = 0; }
-                if (!segs->seg && inf.status == UNC_SEG_TRUNCATED) inf.status = UNC_SEG_OK;       // (no records were asked for: none is missing)
+                if (!caller_seg && inf.status == UNC_SEG_TRUNCATED) inf.status = UNC_SEG_OK;       // (no records were asked for: none is missing)
+                // (with an accumulator the room on the device is not the caller's: the status goes by the caller's)
+                if (caller_seg && inf.status == UNC_SEG_OK && inf.n_rows > segs->seg_off[q + 1] - segs->seg_off[q]) inf.status = UNC_SEG_TRUNCATED;
                 if (segs->info) segs->info[q] = inf;
             }
-            if (segs->seg)
+            if (caller_seg)
                 HIPCHK(deal_out(d_seg.p, (size_t)seg_off[n_queries], st, n_queries,
-                                [&](uint32_t q) { return std::min<uint64_t>(info[q].n_rows, seg_off[q + 1] - seg_off[q]); },
+                                [&](uint32_t q) { return std::min<uint64_t>(info[q].n_rows, std::min<uint64_t>(seg_off[q + 1] - seg_off[q],
+                                                                                                            segs->seg_off[q + 1] - segs->seg_off[q])); },
                                 [&](uint32_t q) { return seg_off[q]; }, [&](uint32_t q) { return segs->seg + segs->seg_off[q]; }));
         }
         if (want_tap) {     // the tap: the columns as events.  It transforms what it copies, so the loop is its own
@@ -405,16 +438,43 @@ struct UploadedRows : AlignRows {
 };
 }  // namespace
 
+// The one way in: a call's record (unc_align_call_t, include/uncalled_hip.h) under the name of the entry point that filled it
+static int align_dispatch(const unc_align_call_t &u, const char *who);
+
+extern "C" int unc_align_call(const unc_align_call_t *call) {
+    static const char *who = "unc_align_call";
+    if (!call) return fail(UNC_ERR_ARG, "%s: null argument", who);
+    if (call->size < sizeof(uint32_t) || call->size > sizeof(unc_align_call_t))
+        return fail(UNC_ERR_ARG, "%s: size %u is not that of a record of this library (%zu)", who, call->size, sizeof(unc_align_call_t));
+    unc_align_call_t u;
+    memset(&u, 0, sizeof u);
+    memcpy(&u, call, call->size);
+    if ((u.kmers != nullptr) == (u.refseq != nullptr)) return fail(UNC_ERR_ARG, "%s: rows come as kmers or as refseq, one of the two", who);
+    return align_dispatch(u, who);
+}
+
+// the parameters that all four entry points below share, as a record
+static unc_align_call_t align_record(int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
+                                     const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
+                                     const unc_align_query_t *queries, uint64_t workspace_bytes, unc_align_result_t *results, float *levels,
+                                     const uint64_t *lev_off, uint32_t *path, const uint64_t *path_off, const unc_align_segments_t *segs, void *stream) {
+    unc_align_call_t u;
+    memset(&u, 0, sizeof u);
+    u.size = sizeof u; u.device = device; u.params = params; u.opts = opts; u.n_reads = n_reads; u.on_device = on_device; u.raw = raw;
+    u.offsets = offsets; u.calib = calib; u.n_queries = n_queries; u.queries = queries; u.workspace_bytes = workspace_bytes;
+    u.results = results; u.levels = levels; u.lev_off = lev_off; u.path = path; u.path_off = path_off; u.segs = segs; u.stream = stream;
+    return u;
+}
+
 extern "C" int unc_align_batch(int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
                                const uint64_t *offsets, const unc_calib_t *calib, int on_device, uint32_t n_queries,
                                const unc_align_query_t *queries, const uint16_t *kmers, const uint64_t *km_off, uint64_t workspace_bytes,
                                unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path, const uint64_t *path_off,
                                void *stream) {
-    const AlignCall c{"unc_align_batch", device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, workspace_bytes,
-                      results, levels, lev_off, path, path_off, stream, nullptr};
-    if (!raw || !offsets || !calib || !queries || !kmers || !km_off || !results) return fail(UNC_ERR_ARG, "%s: null argument", c.who);
-    UploadedRows rows(kmers, km_off, n_queries);
-    return align_run(c, rows);
+    unc_align_call_t u = align_record(device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, workspace_bytes, results,
+                                      levels, lev_off, path, path_off, nullptr, stream);
+    u.kmers = kmers; u.km_off = km_off;
+    return align_dispatch(u, "unc_align_batch");
 }
 
 extern "C" int unc_align_segments_batch(int device, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads, const int16_t *raw,
@@ -422,13 +482,26 @@ extern "C" int unc_align_segments_batch(int device, const unc_params_t *params, 
                                         const unc_align_query_t *queries, const uint16_t *kmers, const uint64_t *km_off, uint64_t workspace_bytes,
                                         unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint32_t *path,
                                         const uint64_t *path_off, const unc_align_segments_t *out, void *stream) {
-    const AlignCall c{"unc_align_segments_batch", device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries,
-                      workspace_bytes, results, levels, lev_off, path, path_off, stream, out};
-    if (!raw || !offsets || !calib || !queries || !kmers || !km_off || !results || !out) return fail(UNC_ERR_ARG, "%s: null argument", c.who);
-    UploadedRows rows(kmers, km_off, n_queries);
-    return align_run(c, rows);
+    if (!out) return fail(UNC_ERR_ARG, "%s: null argument", "unc_align_segments_batch");
+    unc_align_call_t u = align_record(device, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, workspace_bytes, results,
+                                      levels, lev_off, path, path_off, out, stream);
+    u.kmers = kmers; u.km_off = km_off;
+    return align_dispatch(u, "unc_align_segments_batch");
 }
 
 // unc_align_ref_batch and the packed reference: unc_refseq.cpp and k_refseq.hip are compiled as part of this translation unit, so that
 // every build of the alignment sources holds them
 #include "unc_refseq.cpp"
+
+// rows as coordinates (u.refseq; the route of unc_refseq.cpp), or the caller's k-mers, uploaded
+static int align_dispatch(const unc_align_call_t &u, const char *who) {
+    const AlignCall c{who, u.device, u.params, u.opts, u.n_reads, u.raw, u.offsets, u.calib, u.on_device, u.n_queries, u.queries,
+                      u.workspace_bytes, u.results, u.levels, u.lev_off, u.path, u.path_off, u.stream, u.segs, u.model, u.accumulate};
+    if (u.refseq || u.stretches) return align_ref(c, u.refseq, u.stretches, u.kmers_out, u.kmers_off);
+    if (!u.raw || !u.offsets || !u.calib || !u.queries || !u.kmers || !u.km_off || !u.results) return fail(UNC_ERR_ARG, "%s: null argument", who);
+    UploadedRows rows(u.kmers, u.km_off, u.n_queries);
+    return align_run(c, rows);
+}
+
+// the training accumulator's host side is compiled as part of this translation unit in the same way
+#include "unc_model_acc.cpp"

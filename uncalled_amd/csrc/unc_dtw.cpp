@@ -14,33 +14,25 @@
 #include <vector>
 
 #include "dtw_dev.h"
-#include "r94_model_table.h"
 #include "unc_host_util.h"
+#include "unc_model.h"
 
 using namespace unc;
 
 // ------------------------------------------------------------------ the template model
-// PoreModel(vector, cmpl=false), pore_model.hpp:58-62,77-103: the arithmetic of build_model (unc_host.cpp), rows not complemented --
-// row k here is row k ^ 0x3FF there.
-const float *unc::dtw_model_host() {
-    static std::vector<float> tab;
+// PoreModel(vector, cmpl=false) of the compiled-in pairs, through the one builder (unc_model.h): rows not complemented -- row k here
+// is row k ^ 0x3FF of the index's tables (unc_host.cpp).
+const ModelTables &unc::dtw_model_default() {
+    static ModelTables tab;
     static std::once_flag once;
     std::call_once(once, [] {
-        tab.assign(3 * UNC_NKMER, 0.0f);
-        float *mu = tab.data(), *v2 = mu + UNC_NKMER, *ld = mu + 2 * UNC_NKMER;
-        for (uint32_t k = 0; k < (uint32_t)UNC_NKMER; ++k) {
-            float mean, stdv;
-            memcpy(&mean, &UNC_R94_MEAN_STDV_BITS[2 * k], 4);
-            memcpy(&stdv, &UNC_R94_MEAN_STDV_BITS[2 * k + 1], 4);
-            mu[k] = mean;
-            float tv = 2 * stdv;
-            tv = tv * stdv;
-            v2[k] = tv;
-            ld[k] = (float)log(sqrt(M_PI * (double)v2[k]));
-        }
+        float pairs[2 * UNC_NKMER];
+        model_default_pairs(pairs);
+        model_build_tables(pairs, false, &tab);
     });
-    return tab.data();
+    return tab;
 }
+const float *unc::dtw_model_host() { return dtw_model_default().tab; }
 
 extern "C" void unc_dtw_model_tables(float *means1024, float *vars_x2_1024, float *lognorm1024) {
     const float *t = dtw_model_host();
@@ -79,7 +71,7 @@ extern "C" int unc_dtw_last_timing(float *ms_kernel, uint32_t *rounds, uint64_t 
 // The queue, the rounds and the launches over columns and k-mers that lie in device memory already (dtw_dev.h).
 int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
                         const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                        const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook) {
+                        const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook, const unc_model *model) {
     g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
     std::vector<uint64_t> cells(n), words(n);
     for (uint32_t a = 0; a < n; ++a) {
@@ -114,7 +106,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
     if (todo.empty()) return UNC_OK;
 
     const float *d_model = nullptr;
-    if (int rc = dtw_model_device(device, &d_model)) return rc;
+    if (int rc = model ? model_device(model, device, &d_model) : dtw_model_device(device, &d_model)) return rc;
     DevBuf<float> d_lines;
     DevBuf<uint32_t> d_crumbs, d_path, d_next;
     DevBuf<DtwJob> d_jobs;
@@ -134,7 +126,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
     while (at < todo.size()) {
         // a round: the next alignments of the queue whose back-pointers fit the workspace together
         round.clear(); caller_cap.clear();
-        uint64_t w = 0, lines = 0, pairs = 0;
+        uint64_t w = 0, lines = 0, pairs = 0, rows = 0;
         while (at < todo.size() && (round.empty() || (w + words[todo[at]]) * 4 <= workspace_bytes)) {
             DtwJob j = jobs[todo[at]];
             j.crumb_off = w; j.line_off = lines; j.path_off = pairs;
@@ -143,6 +135,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
             w += words[todo[at]];
             lines += 2 * dtw_line_floats(j.cols);
             pairs += j.path_cap;
+            rows += j.rows;
             round.push_back(j);
             ++at;
         }
@@ -162,7 +155,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
         HIPCHK(hipGetLastError());
         HIPCHK(ev.record(1, st));
         if (hook)
-            if (int rc = hook->round(d_jobs.p, nr, d_path.p, d_res.p, st)) return rc;
+            if (int rc = hook->round(d_jobs.p, nr, rows, d_path.p, d_res.p, st)) return rc;
         h_res.resize(n);
         h_path.resize(path ? 2 * pairs : 0);
         // (the results of this round's alignments lie scattered over d_res: the whole array is small)
@@ -192,7 +185,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
 }
 
 // unc_dtw_batch (band == 0) and unc_dtw_band_batch (band > 0: its own two rules are checked by the entry point)
-static int dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
+static int dtw_batch(int device, const unc_model *model, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
                      const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
                      const uint64_t *path_off, void *stream) {
     // ---- arguments: everything is checked before the device is touched
@@ -232,13 +225,13 @@ static int dtw_batch(int device, uint32_t n, const float *events, const uint64_t
     HIPCHK(d_events.alloc(n_ev)); HIPCHK(d_kmers.alloc(n_km));
     HIPCHK(hipMemcpyAsync(d_events.p, events + ev_off[0], n_ev * sizeof(float), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_kmers.p, kmers + km_off[0], n_km * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    return dtw_run_device(device, n, d_events.p, d_kmers.p, jobs.data(), nullptr, prm, band, workspace_bytes, res, path, path_off, st);
+    return dtw_run_device(device, n, d_events.p, d_kmers.p, jobs.data(), nullptr, prm, band, workspace_bytes, res, path, path_off, st, nullptr, model);
 }
 
 extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
                              const uint64_t *km_off, const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res,
                              uint32_t *path, const uint64_t *path_off, void *stream) {
-    return dtw_batch(device, n, events, ev_off, kmers, km_off, prm, 0, workspace_bytes, res, path, path_off, stream);
+    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, 0, workspace_bytes, res, path, path_off, stream);
 }
 
 extern "C" int unc_dtw_band_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
@@ -247,7 +240,16 @@ extern "C" int unc_dtw_band_batch(int device, uint32_t n, const float *events, c
     if (band == 0) return fail(UNC_ERR_ARG, "unc_dtw_band_batch: a band of 0 (unc_dtw_batch is the full matrix)");
     if (prm && prm->subseq != UNC_DTW_NONE && prm->subseq <= UNC_DTW_COL)
         return fail(UNC_ERR_ARG, "unc_dtw_band_batch: the band is global only (subseq %u)", prm->subseq);
-    return dtw_batch(device, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream);
+    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream);
+}
+
+// either of the two above, by `band`, with the costs of a model (null: the template's)
+extern "C" int unc_dtw_model_batch(int device, const unc_model_t *model, uint32_t n, const float *events, const uint64_t *ev_off,
+                                   const uint16_t *kmers, const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band,
+                                   uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) {
+    if (band && prm && prm->subseq != UNC_DTW_NONE && prm->subseq <= UNC_DTW_COL)
+        return fail(UNC_ERR_ARG, "unc_dtw_model_batch: the band is global only (subseq %u)", prm->subseq);
+    return dtw_batch(device, model, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream);
 }
 
 // ------------------------------------------------------------------ BwaIndex::get_kmers

@@ -14,15 +14,16 @@
 #include <chrono>
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <utility>
 #include <vector>
 
-#include "r94_model_table.h"
 #include "unc_dev_types.h"
 #include "unc_kernels.h"
 #include "unc_host_util.h"
+#include "unc_model.h"
 
 using namespace unc;
 
@@ -77,6 +78,7 @@ struct unc_index {
     float thresholds[64];
     std::vector<float> model;                // [3][1024] host copy
     float model_mean = 0, model_stdv = 0;
+    mutable std::atomic<uint32_t> handed_out{0};     // mappers and realtime objects ever made from the index, freed ones included (unc_index_set_model)
     // device
     DevBuf<uint32_t> d_bwt;
     DevBuf<uint64_t> d_sa;
@@ -102,32 +104,14 @@ static bool read_file(const std::string &fn, std::vector<char> &out) {
     return ok;
 }
 
-// PoreModel(vector, cmpl=true): pore_model.hpp:77-103, init_kmer 58-62, init_stdv 48-56.  Host libm
-// builds the three float tables once; the device only ever consumes the resulting float32 values.
-static void build_model(unc_index *ix) {
-    ix->model.assign(3 * NKMER, 0.0f);
-    float *mu = ix->model.data(), *v2 = mu + NKMER, *ld = mu + 2 * NKMER;
-    float model_mean = 0;
-    for (uint32_t kmer = 0; kmer < (uint32_t)NKMER; ++kmer) {
-        float mean, stdv;
-        memcpy(&mean, &UNC_R94_MEAN_STDV_BITS[2 * kmer], 4);
-        memcpy(&stdv, &UNC_R94_MEAN_STDV_BITS[2 * kmer + 1], 4);
-        const uint32_t k = kmer ^ KMASK;   // complement model, mapper.cpp:57 / bp.hpp:77-80
-        mu[k] = mean;
-        float tv = 2 * stdv;
-        tv = tv * stdv;
-        v2[k] = tv;
-        ld[k] = (float)log(sqrt(M_PI * (double)v2[k]));
-        model_mean = model_mean + mean;
-    }
-    model_mean = model_mean / (float)NKMER;
-    float acc = 0;
-    for (uint32_t k = 0; k < (uint32_t)NKMER; ++k) {
-        float d = mu[k] - model_mean;
-        acc = (float)((double)acc + (double)d * (double)d);
-    }
-    ix->model_mean = model_mean;
-    ix->model_stdv = sqrtf(acc / (float)NKMER);
+// PoreModel(vector, cmpl=true) through the one builder (unc_model.h): host libm builds the three float tables once; the device
+// only ever consumes the resulting float32 values.  Complemented: mapper.cpp:57 / bp.hpp:77-80
+static void build_model(unc_index *ix, const float *pairs2048) {
+    ModelTables t;
+    model_build_tables(pairs2048, true, &t);
+    ix->model.assign(t.tab, t.tab + 3 * NKMER);
+    ix->model_mean = t.mean;
+    ix->model_stdv = t.stdv;
 }
 
 // mapper.cpp:123-157
@@ -271,7 +255,11 @@ static int plan_index(const char *bwa_prefix, const char *idx_preset, unc_index 
 
     if (int rc = parse_ann(prefix + ".ann", ix)) return rc;
     if (int rc = parse_uncl(prefix + ".uncl", idx_preset ? idx_preset : "default", ix->thresholds)) return rc;
-    build_model(ix);
+    {
+        float pairs[2 * NKMER];
+        model_default_pairs(pairs);
+        build_model(ix, pairs);
+    }
 
     pl.bwt_bytes = ((pl.n_words * 4 + 63) / 64 + 1) * 64;
     pl.sa_bytes = pl.n_sa * 8;
@@ -282,6 +270,15 @@ static int plan_index(const char *bwa_prefix, const char *idx_preset, unc_index 
     // it differs from the allocations ON PURPOSE -- it decides the spacer's size, and with it where the tables lie)
     const size_t dense_sa_estimate = (pl.n_words * 16 + 2) / 2 * 12;
     pl.spacer_need = pl.bwt_bytes + pl.sa_bytes + dense_sa_estimate + pl.n_words * 2 + (64u << 20);
+    return UNC_OK;
+}
+
+// the host tables of the pore model into their two layouts on the device, which are allocated
+static int upload_model(unc_index *ix) {
+    HIPCHK(hipMemcpy(ix->d_model.p, ix->model.data(), N_MODEL * 4, hipMemcpyHostToDevice));
+    std::vector<float> m4(N_MODEL4, 0.0f);
+    for (int k = 0; k < NKMER; ++k) { m4[4 * k] = ix->model[k]; m4[4 * k + 1] = ix->model[NKMER + k]; m4[4 * k + 2] = ix->model[2 * NKMER + k]; }
+    HIPCHK(hipMemcpy(ix->d_model4.p, m4.data(), N_MODEL4 * 4, hipMemcpyHostToDevice));
     return UNC_OK;
 }
 
@@ -299,13 +296,8 @@ static int upload_tables(unc_index *ix, const IndexPlan &pl) {
     }
     HIPCHK(ix->d_kmer_ranges.alloc(N_RANGES));
     HIPCHK(ix->d_model.alloc(N_MODEL));
-    HIPCHK(hipMemcpy(ix->d_model.p, ix->model.data(), N_MODEL * 4, hipMemcpyHostToDevice));
-    {
-        std::vector<float> m4(N_MODEL4, 0.0f);
-        for (int k = 0; k < NKMER; ++k) { m4[4 * k] = ix->model[k]; m4[4 * k + 1] = ix->model[NKMER + k]; m4[4 * k + 2] = ix->model[2 * NKMER + k]; }
-        HIPCHK(ix->d_model4.alloc(N_MODEL4));
-        HIPCHK(hipMemcpy(ix->d_model4.p, m4.data(), N_MODEL4 * 4, hipMemcpyHostToDevice));
-    }
+    HIPCHK(ix->d_model4.alloc(N_MODEL4));
+    if (int rc = upload_model(ix)) return rc;
     // (what unc_index_device_bytes reports leaves out d_model4 and, below, d_kmer_valid -- 16.1 KB together --: kept ON PURPOSE, the
     // number is compared between versions)
     ix->device_bytes = pl.bwt_bytes + pl.sa_bytes + N_RANGES * 8 + N_MODEL * 4;
@@ -506,6 +498,17 @@ extern "C" void unc_index_model_tables(const unc_index_t *ix, float *mu, float *
     memcpy(ld, ix->model.data() + 2 * NKMER, NKMER * 4);
     *mm = ix->model_mean;
     *ms = ix->model_stdv;
+}
+
+// Mapper::load_static, mapper.cpp:113-115.  The tables keep their place on the device: every DevIndex handed out stays valid
+extern "C" int unc_index_set_model(unc_index_t *ix, const unc_model_t *m) {
+    if (!ix || !m) return fail(UNC_ERR_ARG, "unc_index_set_model: null argument");
+    if (const uint32_t n = ix->handed_out.load())
+        return fail(UNC_ERR_ARG, "unc_index_set_model: %u mapper or realtime objects were made from this index already", n);
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipDeviceSynchronize());
+    build_model(ix, m->pairs);
+    return upload_model(ix);
 }
 
 extern "C" int unc_fm_get_neighbor(const unc_index_t *ix, uint32_t n, const uint64_t *starts, const uint64_t *ends,
@@ -867,6 +870,7 @@ extern "C" int unc_mapper_create(const unc_index_t *ix, const unc_params_t *p, c
     HIPCHK(m->ev.create(3));
     { hipEvent_t ref = nullptr; if (int rc = ref_event(&ref)) return rc; }      // (before the first batch of any mapper)
     guard.p = nullptr;
+    ix->handed_out.fetch_add(1);
     *out = m;
     return UNC_OK;
 }
@@ -1901,6 +1905,7 @@ extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint3
     HIPCHK(rt->stream.create());
     HIPCHK(rt->ev.create(3));
     guard.p = nullptr;
+    ix->handed_out.fetch_add(1);
     *out = rt;
     return UNC_OK;
 }
@@ -2134,3 +2139,7 @@ extern "C" int unc_self_align(const unc_index_t *ix, const char *bwa_prefix, uin
     HIPCHK(hipMemcpy(full_len, d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return UNC_OK;
 }
+
+// the pore model object (unc_model_default / _load / _save / ...): compiled as part of this translation unit, so that every build of
+// the host library holds it
+#include "unc_model.cpp"

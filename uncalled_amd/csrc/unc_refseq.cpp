@@ -215,9 +215,11 @@ extern "C" int unc_align_ref_batch(const unc_refseq_t *rs, const unc_params_t *p
                                    unc_align_result_t *results, float *levels, const uint64_t *lev_off, uint16_t *kmers_out,
                                    const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off, void *stream) {
     // (the device is the reference's: align_ref sets it once rs is known not to be null)
-    const AlignCall c{"unc_align_ref_batch", 0, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, workspace_bytes,
-                      results, levels, lev_off, path, path_off, stream, nullptr};
-    return align_ref(c, rs, stretches, kmers_out, kmers_off);
+    unc_align_call_t u = align_record(0, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, workspace_bytes, results,
+                                      levels, lev_off, path, path_off, nullptr, stream);
+    u.refseq = rs; u.stretches = stretches; u.kmers_out = kmers_out; u.kmers_off = kmers_off;
+    if (!rs || !stretches) return fail(UNC_ERR_ARG, "%s: null argument", "unc_align_ref_batch");
+    return align_dispatch(u, "unc_align_ref_batch");
 }
 
 extern "C" int unc_align_ref_segments_batch(const unc_refseq_t *rs, const unc_params_t *params, const unc_align_opts_t *opts, uint32_t n_reads,
@@ -226,8 +228,9 @@ extern "C" int unc_align_ref_segments_batch(const unc_refseq_t *rs, const unc_pa
                                             uint64_t workspace_bytes, unc_align_result_t *results, float *levels, const uint64_t *lev_off,
                                             uint16_t *kmers_out, const uint64_t *kmers_off, uint32_t *path, const uint64_t *path_off,
                                             const unc_align_segments_t *out, void *stream) {
-    const AlignCall c{"unc_align_ref_segments_batch", 0, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries,
-                      workspace_bytes, results, levels, lev_off, path, path_off, stream, out};
-    if (!out) return fail(UNC_ERR_ARG, "%s: null argument", c.who);
-    return align_ref(c, rs, stretches, kmers_out, kmers_off);
+    unc_align_call_t u = align_record(0, params, opts, n_reads, raw, offsets, calib, on_device, n_queries, queries, workspace_bytes, results,
+                                      levels, lev_off, path, path_off, out, stream);
+    u.refseq = rs; u.stretches = stretches; u.kmers_out = kmers_out; u.kmers_off = kmers_off;
+    if (!out || !rs || !stretches) return fail(UNC_ERR_ARG, "%s: null argument", "unc_align_ref_segments_batch");
+    return align_dispatch(u, "unc_align_ref_segments_batch");
 }
