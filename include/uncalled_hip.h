@@ -685,6 +685,88 @@ typedef struct {
 } unc_align_call_t;
 int unc_align_call(const unc_align_call_t *call);
 
+/* ---- the signal pile-up at reference coordinates: the records of the alignments (unc_segment_t), summed per reference position and
+ * strand over many reads, on the device.  The reference has no counterpart; it is the step its alignments are made for (Tombo,
+ * nanocompore): the signal at a position against what the model expects there, or against a second sample's.
+ * A pile-up lives on the device of an unc_refseq_t and is freed before it.  It covers a list of regions (rid, st, en) -- an
+ * unc_ref_stretch_t each, fwd ignored; NULL with n_regions 0: every sequence, whole -- which the create call sorts.  A BIN is a pair
+ * (position p, strand): p the forward coordinate of the leftmost base of a 5-mer, st <= p < en - 4; the minus-strand bin at p holds
+ * the records of minus-strand alignments whose k-mer is the reverse complement of the forward 5-mer at p.  Bins are numbered by
+ * region in sorted order, then position, then strand: bin = 2 * (positions of the regions before + p - st) + (0 plus, 1 minus), 64
+ * bits wide; there are 2 * sum of max(en - st - 4, 0) of them (a region of fewer than five bases is legal and holds none).
+ * Each bin holds five 64-bit words, all integers: n (records), S (the signed sum of q), SS_lo and SS_hi (the 128-bit sum of q * q),
+ * D (the sum of the records' smp_n: dwell in samples), q = llrint((double)level * 2^20) as in the training accumulator.  Three
+ * counters beside them; a record is looked at in this order:
+ *   shared == 1      skipped and not counted, unless the pile-up was made with UNC_PILEUP_KEEP_SHARED;
+ *   n_dropped        its level is not finite or |level| >= 2048;
+ *   n_outside        its position lies in no region;
+ *   n_added          otherwise: it is in its bin.
+ * The table after a set of records does not depend on their order, on how the set is split into calls or rounds, on
+ * workspace_bytes or on the caller's room in seg or path.  One pile-up may be used by one call at a time.  A call that FAILS after
+ * device work has begun may have added the records of the rounds it completed: the pile-up's contents are then undefined, and the
+ * caller resets it and adds again.  A call refused with UNC_ERR_ARG has added nothing. */
+typedef struct unc_pileup unc_pileup_t;
+#define UNC_PILEUP_KEEP_SHARED 1u
+/* UNC_ERR_ARG before the device is touched: a rid out of range, st > en, en past the sequence, regions that overlap, unknown flags.
+ * UNC_ERR_NOMEM when the table (40 bytes a bin) cannot be allocated. */
+int unc_pileup_create(const unc_refseq_t *rs, uint32_t n_regions, const unc_ref_stretch_t *regions, uint32_t flags, unc_pileup_t **out);
+void unc_pileup_free(unc_pileup_t *pu);
+int unc_pileup_reset(unc_pileup_t *pu);
+uint64_t unc_pileup_device_bytes(const unc_pileup_t *pu);
+uint64_t unc_pileup_n_bins(const unc_pileup_t *pu);
+/* any output may be NULL */
+int unc_pileup_counters(const unc_pileup_t *pu, uint64_t *n_dropped, uint64_t *n_outside, uint64_t *n_added);
+/* k_pileup_accum over n records in host memory: record i lies at position pos[i] of sequence rid[i], strand fwd[i] != 0 plus, with
+ * level[i], smp_n[i] and shared[i] (shared may be NULL: all 0).  UNC_ERR_ARG, before the device is touched, for a rid out of range;
+ * a position in no region is no error (n_outside).  Returns when the records are added. */
+int unc_pileup_add(unc_pileup_t *pu, uint64_t n, const int32_t *rid, const uint64_t *pos, const uint32_t *fwd, const float *level,
+                   const uint32_t *smp_n, const uint32_t *shared, void *stream);
+/* unc_align_call with a pile-up (NULL: exactly unc_align_call): k_pileup_accum runs behind k_align_segments (and behind
+ * k_model_accum, when there is an accumulator) on every round of the DTW, over the round's records where they lie on the device;
+ * they need not be asked for.  Record s of a query with stretch (rid, fwd, st, en) is row r = row_first + s: position st + r on the
+ * plus strand, en - 5 - r on the minus strand (BwaIndex::get_kmers + kmers_revcomp reverse the list: row r is the reverse complement
+ * of the forward k-mer that starts at en - 5 - r).  Queries with UNC_SEG_NONE contribute nothing.  Everything the call returns is bit
+ * for bit what unc_align_call returns for the same record.  UNC_ERR_ARG before the device is touched, besides what unc_align_call
+ * refuses: rows given as k-mer arrays (they have no coordinates), a pile-up of another unc_refseq_t or device. */
+int unc_align_pileup_call(const unc_align_call_t *call, unc_pileup_t *pileup);
+/* kernel milliseconds of k_pileup_accum in the calling thread's last unc_pileup_add or alignment call (HIP events on the stream,
+ * summed over the DTW's rounds; 0 for a call without a pile-up) */
+int unc_pileup_last_timing(float *ms);
+/* the indices of the bins with n >= min_cov in a (and in b as well, unless b is NULL), ASCENDING: an ordered compaction on the device
+ * in three launches (counts per workgroup, an exclusive scan, the write).  At most cap indices are written to bins_out (may be NULL
+ * with cap 0); *n_out is the full count either way.  UNC_ERR_ARG for min_cov == 0 and for a b that has other regions or lies on
+ * another device. */
+int unc_pileup_covered(const unc_pileup_t *a, const unc_pileup_t *b, uint64_t min_cov, uint64_t *bins_out, uint64_t cap, uint64_t *n_out);
+/* kernel milliseconds of the three launches of the calling thread's last unc_pileup_covered: counts, scan, write */
+int unc_pileup_covered_last_timing(float *ms3);
+/* the five words (n, S, SS_lo, SS_hi, D) of n listed bins, gathered on the device: out_words[5 i ..].  UNC_ERR_ARG for a bin that
+ * does not exist */
+int unc_pileup_gather(const unc_pileup_t *pu, uint64_t n, const uint64_t *bins, uint64_t *out_words);
+/* host only, from the region table: where bin bins[i] lies.  Any output may be NULL */
+int unc_pileup_bin_locate(const unc_pileup_t *pu, uint64_t n, const uint64_t *bins, int32_t *rid, uint64_t *pos, uint32_t *fwd);
+/* dst += src, word by word with the 128-bit carry, and the three counters.  Both must have the same regions (UNC_ERR_ARG); src may
+ * lie on another device, and is then staged through the host */
+int unc_pileup_merge(unc_pileup_t *dst, const unc_pileup_t *src);
+/* Statistics of listed bins, on the host, exact.  kmer: the bin's 5-mer from the packed reference, reverse-complemented for the
+ * minus strand; model_mean / model_stdv: the model's pair for it (model NULL: the r9.4 template).  In unsigned 128-bit integers
+ * V = n * SS - S * S; then in double, one rounding per written operation, 128-bit values converted round-to-nearest:
+ *   mean = (double)S / (double)n / 1048576.0        sd = sqrt((double)V) / (double)n / 1048576.0        dwell = (double)D / (double)n
+ *   z = ((mean - (double)model_mean) / (double)model_stdv) * sqrt((double)n)
+ * A bin with n == 0 gives zeros.  UNC_ERR_ARG if n * SS leaves 128 bits (not reachable, as for unc_model_acc_finish). */
+typedef struct {
+    uint64_t n;
+    double mean, sd, dwell, z;
+    float model_mean, model_stdv;
+    uint32_t kmer;
+    uint32_t pad;
+} unc_pileup_stat_t;
+int unc_pileup_stats(const unc_pileup_t *pu, const unc_model_t *model, uint64_t n, const uint64_t *bins, unc_pileup_stat_t *out);
+/* Welch's statistic of two pile-ups with the same regions over listed bins, mean and sd as above:
+ *   se2 = sd_a * sd_a / (double)(n_a - 1) + sd_b * sd_b / (double)(n_b - 1)        t = se2 > 0 ? (mean_a - mean_b) / sqrt(se2) : 0
+ * UNC_ERR_ARG for a bin with n_a < 2 or n_b < 2.  No p-values: they would need a distribution function whose bits nothing pins. */
+typedef struct { uint64_t n_a, n_b; double mean_a, mean_b, sd_a, sd_b, se2, t; } unc_pileup_cmp_t;
+int unc_pileup_compare(const unc_pileup_t *a, const unc_pileup_t *b, uint64_t n, const uint64_t *bins, unc_pileup_cmp_t *out);
+
 /* ---- repeat masking: replaces masking/mask_internal.sh + masking/mask_kmers.py (jellyfish) and masking/mask_external.sh (bowtie,
  * bedtools, samtools), which the reference's masking/README.md recommends for references with intergenic eukaryotic DNA.
  * A reference is one byte per base: 0..3 = A C G T (either case), everything else 4 = "not a base"; a masked base becomes 4.

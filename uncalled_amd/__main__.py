@@ -407,16 +407,18 @@ def write_segments(out, q, row_first, segs, km, model_means):
 
 
 def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False, band=0, segments=False, model=None,
-              accumulate=None):
+              accumulate=None, pileup=None, refseq=None):
     """The batches behind `dtw`: reads = [(id, int16 samples, (range, offset, digitisation))], queries as load_dtw_queries gives
     them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels, path, SEGMENT records, SEG_INFO record), in the order of
     `reads`: k-mers, levels and path are None without want_paths, the last two None without segments.  The rows of every alignment
     are made on the device from the queries' coordinates (capi.align_ref_batch); `device` is the index's.  model: a capi.Model in
-    place of the r9.4 template; accumulate: a capi.ModelAcc that takes every alignment's records."""
+    place of the r9.4 template; accumulate: a capi.ModelAcc that takes every alignment's records; pileup: a capi.Pileup that takes
+    them at their reference positions, made for `refseq`, the packed reference to align with (None: read here)."""
     import numpy as np
     from . import capi
     names = index.seq_names()
-    refseq = capi.RefSeq(index, prefix)         # the packed reference: read and uploaded once per run
+    if refseq is None:
+        refseq = capi.RefSeq(index, prefix)     # the packed reference: read and uploaded once per run
     for b0 in range(0, len(reads), batch):
         part = reads[b0:b0 + batch]
         raw = np.concatenate([np.asarray(r[1], np.int16) for r in part]) if part else np.zeros(0, np.int16)
@@ -434,7 +436,7 @@ def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, devic
         t0 = time.time()
         out = capi.align_ref_batch(refseq, raw, offsets, calib, qs, stretches, opts=capi.align_opts(max_events=max_events, band=band),
                                    levels=want_paths, paths=want_paths, kmers=want_paths, segments=segments, model=model,
-                                   accumulate=accumulate)
+                                   accumulate=accumulate, pileup=pileup)
         sec = (time.time() - t0) / max(1, len(part))
         none = [None] * len(part)
         out = list(out) if isinstance(out, tuple) else [out]         # results, then what was asked for, in this order
@@ -499,6 +501,84 @@ def train_cmd(args):
     model = train_model(index, args.index_prefix, reads, queries, capi.Model.load(args.model) if args.model else None, args.iters,
                         args.min_obs, args.keep_shared, args.band, args.max_events, args.batch_queries, args.device, report)
     model.save(args.out)
+
+
+PILEUP_COLUMNS = ("contig", "pos", "strand", "kmer", "cov", "mean", "stdv", "dwell", "model_mean", "model_stdv", "z")
+PILEUP_CONTROL_COLUMNS = ("ctl_cov", "ctl_mean", "ctl_stdv", "t")
+
+
+def parse_region(text, names, index):
+    """NAME:ST-EN -> (rid, st, en); the name may hold colons itself, so the last one counts"""
+    name, _, span = text.rpartition(":")
+    st, _, en = span.partition("-")
+    if name not in names or not st.isdigit() or not en.isdigit() or int(st) > int(en) or int(en) > index.seq_len(names.index(name)):
+        sys.stderr.write("Error: --region %s: expected NAME:ST-EN inside a sequence of the index\n" % text)
+        sys.exit(1)
+    return names.index(name), int(st), int(en)
+
+
+def pileup_fill(unc, index, prefix, refseq, pileup, fast5, paf, model, args):
+    """every mapped line of `paf` aligned as `dtw --paf` aligns it, the records piled up on the device -> alignments made"""
+    from . import capi
+    queries = load_paf_queries(paf)
+    reads = load_query_reads(unc, fast5, queries)
+    clip_paf_queries(queries, reads)
+    done = 0
+    for _, r, _, _, _, _, _, _ in dtw_align(index, prefix, reads, queries, max_events=args.max_events, batch=args.batch_queries,
+                                            device=args.device, band=args.band, model=model, pileup=pileup, refseq=refseq):
+        done += int(r["status"]) == capi.DTW_OK
+    return done
+
+
+def write_pileup(out, names, pileup, control, min_cov, model):
+    """one line per covered bin, by bin index; floats as %.17g, which names a double exactly"""
+    out.write("\t".join(PILEUP_COLUMNS + (PILEUP_CONTROL_COLUMNS if control is not None else ())) + "\n")
+    bins = pileup.covered(min_cov, other=control)
+    rid, pos, fwd = pileup.locate(bins)
+    st = pileup.stats(bins, model)
+    cs = control.stats(bins, model) if control is not None else None
+    t = {}
+    if control is not None:       # Welch's t needs two records on either side
+        both = [i for i in range(len(bins)) if st["n"][i] >= 2 and cs["n"][i] >= 2]
+        t = dict(zip(both, pileup.compare(control, bins[both])["t"])) if both else {}
+    for i in range(len(bins)):
+        line = "%s\t%d\t%s\t%s\t%d\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g" % (
+            names[int(rid[i])], int(pos[i]), "+" if fwd[i] else "-", kmer_str(st["kmer"][i]), int(st["n"][i]), st["mean"][i], st["sd"][i],
+            st["dwell"][i], st["model_mean"][i], st["model_stdv"][i], st["z"][i])
+        if control is not None:
+            line += "\t%d\t%.17g\t%.17g\t%.17g" % (int(cs["n"][i]), cs["mean"][i], cs["sd"][i], t.get(i, float("nan")))
+        out.write(line + "\n")
+    return len(bins)
+
+
+def pileup_cmd(args):
+    """`pileup`: the signal of many alignments per reference position and strand, summed on the GPU, against the model's expectation
+    and optionally against a control sample's"""
+    from . import capi
+    from . import _uncalled_amd as unc
+    inputs = [args.fast5, args.paf] + (list(args.control) if args.control else [])
+    for f in [args.index_prefix + ".bwt", args.index_prefix + ".pac"] + inputs + ([args.model] if args.model else []):
+        _assert_exists(f)
+    min_cov = args.min_cov if args.min_cov is not None else (2 if args.control else 1)
+    if min_cov < 1:
+        sys.stderr.write("Error: --min-cov must be at least 1\n")
+        sys.exit(1)
+    index = capi.Index(args.index_prefix, device=args.device)
+    names = index.seq_names()
+    regions = [parse_region(r, names, index) for r in args.region] if args.region else None
+    refseq = capi.RefSeq(index, args.index_prefix)
+    model = capi.Model.load(args.model) if args.model else None
+    pileup = capi.Pileup(refseq, regions, args.keep_shared)
+    control = capi.Pileup(refseq, regions, args.keep_shared) if args.control else None
+    for pu, (fast5, paf), what in ((pileup, (args.fast5, args.paf), "sample"), (control, args.control or (None, None), "control")):
+        if pu is None:
+            continue
+        done = pileup_fill(unc, index, args.index_prefix, refseq, pu, fast5, paf, model, args)
+        sys.stderr.write("%s: %d alignments, %d records added, %d dropped, %d outside the regions\n" % (
+            (what, done) + tuple(pu.counters()[i] for i in (2, 0, 1))))
+    with open(args.out, "w") as out:
+        n = write_pileup(out, names, pileup, control, min_cov, model)
+    sys.stderr.write("%d bins with at least %d records written to %s\n" % (n, min_cov, args.out))
 
 
 def dtw_cmd(args):
@@ -659,6 +739,28 @@ def get_parser():
     p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
 
+    p = sp.add_parser("pileup", help="Pile the aligned signal of mapped reads up per reference position and strand",
+                      description="Every mapped line of PAF is aligned as `dtw --paf` aligns it; the normalised level and the dwell of every "
+                      "reference k-mer on every path are summed on the GPU per position of the k-mer's leftmost base and strand (fixed point: "
+                      "the result does not depend on the order or the batching). One line per position and strand with at least MIN_COV "
+                      "records: contig, pos, strand, kmer, cov, mean, stdv, dwell (samples), the model's mean and stdv for the k-mer, and "
+                      "z = (mean - model_mean) / model_stdv * sqrt(cov). With --control: positions covered in both samples, the control's "
+                      "cov, mean, stdv, and Welch's t of the two means (nan where either sample has fewer than two records there). Floats are printed as %.17g.")
+    p.add_argument("index_prefix", type=str, help="BWA prefix of the reference (needs the .pac)")
+    p.add_argument("fast5", type=str, help="fast5 file that holds the reads")
+    p.add_argument("paf", type=str, help="PAF file, such as `map` writes")
+    p.add_argument("-o", "--out", type=str, required=True, help="The TSV file to write")
+    p.add_argument("--control", nargs=2, metavar=("FAST5", "PAF"), default=None, help="A second sample to compare with")
+    p.add_argument("--region", action="append", default=None, metavar="NAME:ST-EN", help="Pile up only inside these bases of the reference "
+                   "(repeatable; regions may not overlap; default: every sequence, whole -- 80 bytes of GPU memory per base)")
+    p.add_argument("--min-cov", type=int, default=None, help="Records a position needs to be written (default 1, with --control 2)")
+    p.add_argument("--model", type=str, default=None, help="Pore model file to align with and compare against (default: the built-in r9.4 template)")
+    p.add_argument("--keep-shared", action="store_true", help="Also count a k-mer whose first event is the previous k-mer's last")
+    p.add_argument("--band", type=int, default=0, help="As in dtw")
+    p.add_argument("--max-events", type=int, default=50000, help="As in dtw")
+    p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
+    p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+
     p = sp.add_parser("mask", help="Mask repeats of a FASTA reference before indexing it (the reference's masking/ scripts, on the GPU)",
                       description="`mask internal` masks the most frequent k-mer of the reference, ITERS times over (mask_internal.sh and "
                       "mask_kmers.py); ties go to the k-mer that sorts first, and the run ends early once no k-mer occurs twice. `mask external` "
@@ -684,6 +786,8 @@ def main(argv=None):
         dtw_cmd(args)
     elif args.subcmd == "train":
         train_cmd(args)
+    elif args.subcmd == "pileup":
+        pileup_cmd(args)
     elif args.subcmd == "mask":
         from . import mask
         mask.run(args)

@@ -162,6 +162,13 @@ class AlignSegments(C.Structure):
 
 REF_STRETCH = np.dtype([("rid", "<i4"), ("fwd", "<u4"), ("st", "<u8"), ("en", "<u8")])      # unc_ref_stretch_t
 MODEL_KEEP_SHARED = 1
+PILEUP_KEEP_SHARED = 1
+# unc_pileup_stat_t, unc_pileup_cmp_t; a bin's five words as unc_pileup_gather returns them
+PILEUP_STAT = np.dtype([("n", "<u8"), ("mean", "<f8"), ("sd", "<f8"), ("dwell", "<f8"), ("z", "<f8"), ("model_mean", "<f4"), ("model_stdv", "<f4"),
+                        ("kmer", "<u4"), ("pad", "<u4")])
+PILEUP_CMP = np.dtype([("n_a", "<u8"), ("n_b", "<u8"), ("mean_a", "<f8"), ("mean_b", "<f8"), ("sd_a", "<f8"), ("sd_b", "<f8"), ("se2", "<f8"),
+                       ("t", "<f8")])
+PILEUP_WORDS = np.dtype([("n", "<u8"), ("S", "<i8"), ("SS_lo", "<u8"), ("SS_hi", "<u8"), ("D", "<u8")])
 
 
 class AlignCall(C.Structure):
@@ -310,6 +317,23 @@ def load(path=None):
         L.unc_model_acc_last_timing.argtypes = [C.POINTER(C.c_float)]
         L.unc_model_acc_finish.argtypes = [vp, vp, u32, C.POINTER(vp), C.POINTER(u32)]
         L.unc_align_call.argtypes = [C.POINTER(AlignCall)]
+    if hasattr(L, "unc_pileup_create"):               # (with the alignment sources)
+        L.unc_pileup_create.argtypes = [vp, u32, vp, u32, C.POINTER(vp)]
+        L.unc_pileup_free.argtypes = [vp]; L.unc_pileup_free.restype = None
+        L.unc_pileup_reset.argtypes = [vp]
+        L.unc_pileup_device_bytes.argtypes = [vp]; L.unc_pileup_device_bytes.restype = u64
+        L.unc_pileup_n_bins.argtypes = [vp]; L.unc_pileup_n_bins.restype = u64
+        L.unc_pileup_counters.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.unc_pileup_add.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        L.unc_align_pileup_call.argtypes = [C.POINTER(AlignCall), vp]
+        L.unc_pileup_last_timing.argtypes = [C.POINTER(C.c_float)]
+        L.unc_pileup_covered.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+        L.unc_pileup_covered_last_timing.argtypes = [vp]
+        L.unc_pileup_gather.argtypes = [vp, u64, vp, vp]
+        L.unc_pileup_bin_locate.argtypes = [vp, u64, vp, vp, vp, vp]
+        L.unc_pileup_merge.argtypes = [vp, vp]
+        L.unc_pileup_stats.argtypes = [vp, vp, u64, vp, vp]
+        L.unc_pileup_compare.argtypes = [vp, vp, u64, vp, vp]
     if hasattr(L, "unc_mask_create"):                 # (the emulator builds of the other features do not hold the masking entry points)
         L.unc_mask_create.argtypes = [C.c_int, vp, u64, vp, u32, C.POINTER(vp)]
         L.unc_mask_free.argtypes = [vp]; L.unc_mask_free.restype = None
@@ -630,12 +654,13 @@ class _SegOut:
 
 
 def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths,
-           on_device, stream, segments, events, model=None, accumulate=None, rec_rows=None):
+           on_device, stream, segments, events, model=None, accumulate=None, rec_rows=None, pileup=None):
     """what align_batch and align_ref_batch share: the ALIGN_QUERY records, raw on the host or the device, the room per query, the buffers
     of levels and paths, _SegOut, the call and the tuple it returns.  entries: the entry point's name without and with segments;
     first: its first argument; rows_args: what names the rows, after the queries; n_rows: the rows of every query; tap_args: what
     follows lev_off; tap: None, or what makes the list that goes between the paths and the segments' outputs.  With a model or an
-    accumulator the call goes through unc_align_call: rec_rows are then the fields of its record that name the rows"""
+    accumulator the call goes through unc_align_call: rec_rows are then the fields of its record that name the rows; with a pile-up
+    through unc_align_pileup_call, with the same record"""
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     calib = np.ascontiguousarray(calib, dtype=CALIB)
     n_reads, n = offsets.size - 1, len(queries)
@@ -667,7 +692,7 @@ def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, ca
             lev.ctypes.data if levels else None, lev_off.ctypes.data if levels else None, *tap_args,
             path.ctypes.data if paths else None, path_off.ctypes.data if paths else None)
     so = _SegOut(n_rows, room, segments, events) if segments or events else None
-    if model is not None or accumulate is not None:
+    if model is not None or accumulate is not None or pileup is not None:
         rec = AlignCall()
         rec.size = C.sizeof(AlignCall)
         rec.params = C.cast(C.pointer(params), C.c_void_p) if params is not None else None
@@ -682,7 +707,7 @@ def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, ca
         rec.stream = stream
         for k, v in rec_rows.items():
             setattr(rec, k, v)
-        _check(L, L.unc_align_call(C.byref(rec)))
+        _check(L, L.unc_align_call(C.byref(rec)) if pileup is None else L.unc_align_pileup_call(C.byref(rec), pileup.h))
     elif so is not None:
         _check(L, getattr(L, entries[1])(*args, C.byref(so.arg), stream))
     else:
@@ -702,7 +727,7 @@ def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, ca
 
 
 def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
-                on_device=False, device=0, stream=None, lib=None, segments=False, events=False, model=None, accumulate=None):
+                on_device=False, device=0, stream=None, lib=None, segments=False, events=False, model=None, accumulate=None, pileup=None):
     """unc_align_batch: the pipeline of the reference's dtw_test (slice -> events -> stall mask -> normalisation to the k-mers'
     levels -> DTW) for a batch of queries on the GPU.  raw / offsets / calib: the reads as Mapper.map_batch takes them (raw: an int16
     array, or with on_device=True a device address).  queries: (read index, smp_st, smp_en) triples, smp_en == 0 = to the read's end;
@@ -712,7 +737,9 @@ def align_batch(raw, offsets, calib, queries, kmers_list, opts=None, params=None
     also a list of SEGMENT arrays -- per query one record per k-mer on its path, in the read's sample coordinates -- and the SEG_INFO
     records (row_first, n_rows, status); events=True: then also a list of EVENT arrays, the query's columns as events.
     model: a Model in place of the r9.4 template (costs and targets); accumulate: a ModelAcc that receives every record of the
-    alignments' paths, asked for or not (unc_align_call)."""
+    alignments' paths, asked for or not (unc_align_call).  pileup: refused -- k-mer arrays have no coordinates (align_ref_batch)."""
+    if pileup is not None:
+        raise ValueError("a pile-up needs coordinates: use align_ref_batch")
     if len(queries) != len(kmers_list):
         raise ValueError("as many k-mer arrays as queries are needed")
     kms = [np.ascontiguousarray(k, dtype=np.uint16).ravel() for k in kmers_list]
@@ -871,12 +898,13 @@ def ref_kmers_batch(refseq, stretches, stream=None):
 
 
 def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, params=None, workspace_bytes=0, levels=False, paths=False,
-                    kmers=False, on_device=False, stream=None, segments=False, events=False, model=None, accumulate=None):
+                    kmers=False, on_device=False, stream=None, segments=False, events=False, model=None, accumulate=None, pileup=None):
     """unc_align_ref_batch: align_batch with coordinates in place of k-mer arrays.  stretches[q] = (rid, st, en, fwd) names the bases
     whose k-mers are query q's rows; they are made on the GPU (the index's) and reach the host only with kmers=True.  Everything else
     as align_batch, and so are the results, bit for bit, for the k-mers ref_kmers gives for the same stretches.  -> ALIGN_RESULT
     records, then, as asked for, the lists of levels, of paths and of k-mers per query, and what segments=True / events=True add
-    (unc_align_ref_segments_batch; as in align_batch, after everything else).  model, accumulate: as in align_batch."""
+    (unc_align_ref_segments_batch; as in align_batch, after everything else).  model, accumulate: as in align_batch.  pileup: a Pileup of
+    this refseq that receives every record of the alignments' paths at its reference position, asked for or not (unc_align_pileup_call)."""
     if len(queries) != len(stretches):
         raise ValueError("as many stretches as queries are needed")
     ss = _stretches(stretches)
@@ -888,7 +916,113 @@ def align_ref_batch(refseq, raw, offsets, calib, queries, stretches, opts=None, 
                   (lambda: [km[int(km_off[q]):int(km_off[q + 1])].copy() for q in range(len(counts))]) if kmers else None,
                   raw, offsets, calib, queries, opts, params, workspace_bytes, levels, paths, on_device, stream, segments, events, model,
                   accumulate, dict(refseq=refseq.h, stretches=ss.ctypes.data, kmers_out=km.ctypes.data if kmers else None,
-                                   kmers_off=km_off.ctypes.data if kmers else None))
+                                   kmers_off=km_off.ctypes.data if kmers else None), pileup)
+
+
+class Pileup:
+    """A signal pile-up on the device of a RefSeq (unc_pileup_t): per bin = (reference position of a 5-mer's leftmost base, strand) the
+    integer sums n, S = sum q, SS = sum q * q (128 bits), D = sum of dwell samples over the records of many alignments,
+    q = rint(level * 2^20).  regions: (rid, st, en) triples (None: every sequence, whole); the bins are numbered in the regions' sorted
+    order, by position, then strand (plus first).  Filled by add() or by align_ref_batch with pileup=.  Close it before its RefSeq (it
+    keeps a reference to it, so garbage collection takes them in that order)."""
+
+    def __init__(self, refseq, regions=None, keep_shared=False, lib=None):
+        self.refseq = refseq
+        self.L = lib or refseq.L
+        rg = None if regions is None else _stretches([(rid, st, en, True) for rid, st, en in regions])
+        h = C.c_void_p()
+        _check(self.L, self.L.unc_pileup_create(refseq.h, 0 if rg is None else len(rg), None if rg is None else rg.ctypes.data,
+                                                PILEUP_KEEP_SHARED if keep_shared else 0, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.unc_pileup_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def n_bins(self):
+        return int(self.L.unc_pileup_n_bins(self.h))
+
+    def device_bytes(self):
+        return int(self.L.unc_pileup_device_bytes(self.h))
+
+    def add(self, rid, pos, fwd, level, smp_n, shared=None, stream=None):
+        """records from host arrays: sequence, position, strand (non-zero: plus), normalised level, dwell samples, shared flag"""
+        r = np.ascontiguousarray(rid, dtype=np.int32).ravel()
+        p = np.ascontiguousarray(pos, dtype=np.uint64).ravel()
+        f = np.ascontiguousarray(fwd, dtype=np.uint32).ravel()
+        lv = np.ascontiguousarray(level, dtype=np.float32).ravel()
+        d = np.ascontiguousarray(smp_n, dtype=np.uint32).ravel()
+        sh = None if shared is None else np.ascontiguousarray(shared, dtype=np.uint32).ravel()
+        if not (r.size == p.size == f.size == lv.size == d.size) or (sh is not None and sh.size != r.size):
+            raise ValueError("the records' arrays must be equally long")
+        _check(self.L, self.L.unc_pileup_add(self.h, r.size, r.ctypes.data, p.ctypes.data, f.ctypes.data, lv.ctypes.data, d.ctypes.data,
+                                             None if sh is None else sh.ctypes.data, stream))
+
+    def reset(self):
+        _check(self.L, self.L.unc_pileup_reset(self.h))
+
+    def counters(self):
+        """-> (n_dropped, n_outside, n_added)"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(self.L, self.L.unc_pileup_counters(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def covered(self, min_cov, other=None, cap=None):
+        """the bins with at least min_cov records (in `other` as well, if given), ascending -> uint64 array; with cap (the first cap
+        of them) -> (array, full count)"""
+        n = C.c_uint64()
+        room = self.n_bins() if cap is None else int(cap)
+        out = np.empty(max(1, room), dtype=np.uint64)
+        _check(self.L, self.L.unc_pileup_covered(self.h, other.h if other is not None else None, int(min_cov), out.ctypes.data, room, C.byref(n)))
+        got = out[:min(room, n.value)].copy()
+        return got if cap is None else (got, n.value)
+
+    def covered_last_timing(self):
+        """kernel milliseconds of the calling thread's last covered(): (counts, scan, write)"""
+        ms = np.zeros(3, np.float32)
+        self.L.unc_pileup_covered_last_timing(ms.ctypes.data)
+        return tuple(float(x) for x in ms)
+
+    def gather(self, bins):
+        """the five words of the listed bins -> PILEUP_WORDS records (n, S, SS_lo, SS_hi, D)"""
+        b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+        out = np.zeros(b.size, dtype=PILEUP_WORDS)
+        _check(self.L, self.L.unc_pileup_gather(self.h, b.size, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def locate(self, bins):
+        """-> (rid int32, pos uint64, fwd uint32) of the listed bins"""
+        b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+        rid, pos, fwd = np.zeros(b.size, np.int32), np.zeros(b.size, np.uint64), np.zeros(b.size, np.uint32)
+        _check(self.L, self.L.unc_pileup_bin_locate(self.h, b.size, b.ctypes.data, rid.ctypes.data, pos.ctypes.data, fwd.ctypes.data))
+        return rid, pos, fwd
+
+    def stats(self, bins, model=None):
+        """-> PILEUP_STAT records: kmer, n, mean, sd, dwell, the model's pair and z, exact (model None: the r9.4 template)"""
+        b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+        out = np.zeros(b.size, dtype=PILEUP_STAT)
+        _check(self.L, self.L.unc_pileup_stats(self.h, model.h if model is not None else None, b.size, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def compare(self, other, bins):
+        """-> PILEUP_CMP records: the two means and deviations, se2 and Welch's t; every listed bin needs two records in both"""
+        b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+        out = np.zeros(b.size, dtype=PILEUP_CMP)
+        _check(self.L, self.L.unc_pileup_compare(self.h, other.h, b.size, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def merge(self, other):
+        """adds `other` (same regions; any device) into this one"""
+        _check(self.L, self.L.unc_pileup_merge(self.h, other.h))
+
+    def last_timing(self):
+        """kernel milliseconds of k_pileup_accum in the calling thread's last add() or alignment call"""
+        ms = C.c_float()
+        self.L.unc_pileup_last_timing(C.byref(ms))
+        return ms.value
 
 
 def align_ref_last_timing(lib=None):

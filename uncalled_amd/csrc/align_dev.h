@@ -79,7 +79,8 @@ struct AlignRows {
 };
 // What the four entry points (unc_align_batch, unc_align_segments_batch, unc_align_ref_batch, unc_align_ref_segments_batch) share of
 // their parameters, under the names include/uncalled_hip.h gives them.  Each fills one, once.  who: the entry point's name, for the
-// messages.  segs (null: none): the outputs of the two _segments_ entry points.  model and acc: unc_align_call's (uncalled_hip.h)
+// messages.  segs (null: none): the outputs of the two _segments_ entry points.  model and acc: unc_align_call's (uncalled_hip.h);
+// pileup and stretches: unc_align_pileup_call's
 struct AlignCall {
     const char *who; int device; const unc_params_t *params; const unc_align_opts_t *opts;
     uint32_t n_reads; const int16_t *raw; const uint64_t *offsets; const unc_calib_t *calib; int on_device;
@@ -87,6 +88,8 @@ struct AlignCall {
     float *levels; const uint64_t *lev_off; uint32_t *path; const uint64_t *path_off; void *stream; const unc_align_segments_t *segs;
     const unc_model_t *model;       // null: the template model
     unc_model_acc_t *acc;           // null: no accumulator
+    unc_pileup_t *pileup;           // null: no pile-up
+    const unc_ref_stretch_t *stretches;     // (with a pile-up) the queries' coordinates, n_queries of them
 };
 int align_run(const AlignCall &c, AlignRows &rows);
 }  // namespace unc

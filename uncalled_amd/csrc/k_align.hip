@@ -183,3 +183,5 @@ void launch_align_prep(const AlignPrep &p, hipStream_t st) {
 #include "k_segments.hip"
 // and k_model_accum, which sums a round's records per k-mer into a training accumulator
 #include "k_model.hip"
+// and k_pileup_accum with the covered-bin kernels, which sum a round's records per reference position into a pile-up
+#include "k_pileup.hip"

@@ -14,6 +14,7 @@
 #include "align_dev.h"
 #include "dtw_dev.h"
 #include "model_dev.h"
+#include "pileup_dev.h"
 #include "unc_host_util.h"
 #include "unc_kernels.h"
 #include "unc_model.h"
@@ -47,19 +48,27 @@ namespace unc {
 void model_acc_set_timing(float ms);
 int model_acc_device(const unc_model_acc *acc);
 void model_acc_args(unc_model_acc *acc, ModelAccum *a);
+// unc_pileup.cpp (included below): what the alignment needs of a pile-up
+void pileup_set_timing(float ms);
+int pileup_device(const unc_pileup *pu);
+const unc_refseq *pileup_refseq(const unc_pileup *pu);
+void pileup_args(unc_pileup *pu, PileupAccum *a);
 }  // namespace unc
 
 namespace {
 // k_align_segments on every round of the DTW, while the round's paths are on the device (the next round reuses their buffer), and
-// with an accumulator k_model_accum behind it, over the records the round has just written
+// with an accumulator k_model_accum behind it, over the records the round has just written, and with a pile-up k_pileup_accum behind
+// that, over the same records
 struct SegmentsHook : DtwRoundHook {
     SegArgs args{};
-    bool accumulate = false;
+    bool accumulate = false, pile = false;
     ModelAccum acc{};   // (with accumulate) everything but the round's jobs
-    DevEvents ev;       // (timing only) two per round, three with an accumulator
+    PileupAccum pu{};   // (with pile) the same
+    DevEvents ev;       // (timing only) two per round, one more with an accumulator, one more with a pile-up
+    size_t per_round() const { return 2 + (accumulate ? 1 : 0) + (pile ? 1 : 0); }
     int round(const DtwJob *d_jobs, uint32_t n_jobs, uint64_t n_rows, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) override {
         const size_t i = ev.e.size();
-        HIPCHK(ev.create(i + (accumulate ? 3 : 2)));
+        HIPCHK(ev.create(i + per_round()));
         args.jobs = d_jobs; args.n_jobs = n_jobs; args.path = d_path; args.res = d_res;
         HIPCHK(ev.record(i, st));
         launch_align_segments(args, st);
@@ -70,6 +79,12 @@ struct SegmentsHook : DtwRoundHook {
             launch_model_accum(acc, n_rows, st);
             HIPCHK(hipGetLastError());
             HIPCHK(ev.record(i + 2, st));
+        }
+        if (pile) {
+            pu.jobs = d_jobs; pu.n_jobs = n_jobs;
+            launch_pileup_accum(pu, n_rows, st);
+            HIPCHK(hipGetLastError());
+            HIPCHK(ev.record(i + per_round() - 1, st));
         }
         return UNC_OK;
     }
@@ -112,6 +127,7 @@ struct AlignRun : AlignCall {
     SegmentsHook hook;                      // set_up_segments
     DevBuf<unc_segment_t> d_seg;
     DevBuf<unc_seg_info_t> d_seginfo;
+    DevBuf<unc_ref_stretch_t> d_stretches;  // (with a pile-up) the queries' coordinates
 
     AlignRun(const AlignCall &c, AlignRows &r) : AlignCall(c), rows(r) {}
     // the call's model on the host: the given one, or the template (both not complemented)
@@ -125,7 +141,7 @@ struct AlignRun : AlignCall {
         if (levels && !lev_off) return fail(UNC_ERR_ARG, "%s: levels without lev_off", who);
         if (segs && segs->seg && !segs->seg_off) return fail(UNC_ERR_ARG, "%s: seg without seg_off", who);
         if (segs && segs->events && !segs->evt_off) return fail(UNC_ERR_ARG, "%s: events without evt_off", who);
-        want_seg = (segs && (segs->seg || segs->info)) || acc;
+        want_seg = (segs && (segs->seg || segs->info)) || acc || pileup;
         want_tap = segs && segs->events;
         if (device < 0 || device >= DTW_MAX_DEVICES) return fail(UNC_ERR_ARG, "%s: device %d", who, device);
         if (acc && model_acc_device(acc) != device)
@@ -150,6 +166,7 @@ struct AlignRun : AlignCall {
         memset(g_align_ms, 0, sizeof g_align_ms);
         g_seg_ms = 0;
         model_acc_set_timing(0);
+        pileup_set_timing(0);
         if (n_queries == 0) return UNC_OK;
         for (uint32_t i = 0; i < n_reads; ++i)
             if (offsets[i + 1] < offsets[i]) return fail(UNC_ERR_ARG, "%s: offsets must ascend", who);
@@ -286,7 +303,8 @@ struct AlignRun : AlignCall {
 
     // f. (with segments) what k_align_segments needs on every round's paths.  The records' layout on the device, from 0: a query's room
     // there is the caller's, or its k-mers if those are fewer (a path has no more rows); without seg no room at all, and info alone is
-    // filled.  With an accumulator the room is the query's k-mers whatever the caller's: every record is made, for k_model_accum
+    // filled.  With an accumulator or a pile-up the room is the query's k-mers whatever the caller's: every record is made, for
+    // k_model_accum and k_pileup_accum
     int set_up_segments() {
         const bool caller_seg = segs && segs->seg;
         seg_off.assign((size_t)n_queries + 1, 0);
@@ -294,7 +312,7 @@ struct AlignRun : AlignCall {
         for (uint32_t q = 0; q < n_queries; ++q) {
             smp_st[q] = queries[q].smp_st;
             const uint64_t room = caller_seg ? std::min<uint64_t>(segs->seg_off[q + 1] - segs->seg_off[q], hq[q].n_km) : 0;
-            seg_off[q + 1] = seg_off[q] + (acc ? hq[q].n_km : room);
+            seg_off[q + 1] = seg_off[q] + (acc || pileup ? hq[q].n_km : room);
         }
         HIPCHK(d_seg.alloc(seg_off[n_queries])); HIPCHK(d_seginfo.alloc(n_queries));
         HIPCHK(d_seg_off.alloc(seg_off.size())); HIPCHK(d_smp_st.alloc(n_queries));
@@ -310,6 +328,14 @@ struct AlignRun : AlignCall {
             model_acc_args(acc, &hook.acc);
             hook.acc.kmers = d_kmers; hook.acc.info = d_seginfo.p; hook.acc.queries = d_q.p; hook.acc.seg_off = d_seg_off.p; hook.acc.seg = d_seg.p;
         }
+        if (pileup) {
+            HIPCHK(d_stretches.alloc(n_queries));
+            HIPCHK(hipMemcpyAsync(d_stretches.p, stretches, (size_t)n_queries * sizeof(unc_ref_stretch_t), hipMemcpyHostToDevice, st));
+            hook.pile = true;
+            pileup_args(pileup, &hook.pu);
+            hook.pu.info = d_seginfo.p; hook.pu.queries = d_q.p; hook.pu.seg_off = d_seg_off.p; hook.pu.seg = d_seg.p;
+            hook.pu.stretches = d_stretches.p;
+        }
         return UNC_OK;
     }
 
@@ -319,8 +345,8 @@ struct AlignRun : AlignCall {
                                     path, path_off, st, want_seg ? &hook : nullptr, model))
             return rc;
         (void)unc_dtw_last_timing(&g_align_ms[3], nullptr, nullptr);
-        const size_t per_round = hook.accumulate ? 3 : 2;
-        float acc_ms = 0;
+        const size_t per_round = hook.per_round();
+        float acc_ms = 0, pile_ms = 0;
         for (size_t i = 0; i + per_round <= hook.ev.e.size(); i += per_round) {       // (g_seg_ms is 0 since check_and_lay_out)
             float t = 0;
             HIPCHK(hook.ev.elapsed(i, i + 1, &t));
@@ -329,8 +355,13 @@ struct AlignRun : AlignCall {
                 HIPCHK(hook.ev.elapsed(i + 1, i + 2, &t));
                 acc_ms += t;
             }
+            if (hook.pile) {
+                HIPCHK(hook.ev.elapsed(i + per_round - 2, i + per_round - 1, &t));
+                pile_ms += t;
+            }
         }
         model_acc_set_timing(acc_ms);
+        pileup_set_timing(pile_ms);
         for (uint32_t q = 0; q < n_queries; ++q) {
             if (skip[q]) continue;
             results[q].dtw = dres[q];
@@ -353,7 +384,7 @@ struct AlignRun : AlignCall {
                 // (a query that was in no round, or whose path has no start, has no rows: its record on the device may never have been written)
                 if (skip[q] || (s != UNC_DTW_OK && s != UNC_DTW_PATH_TRUNCATED)) { inf.row_first = 0; inf.n_rows = 0; inf.status = UNC_SEG_NONE; inf.pad = 0; }
                 if (!caller_seg && inf.status == UNC_SEG_TRUNCATED) inf.status = UNC_SEG_OK;       // (no records were asked for: none is missing)
-                // (with an accumulator the room on the device is not the caller's: the status goes by the caller's)
+                // (with an accumulator or a pile-up the room on the device is not the caller's: the status goes by the caller's)
                 if (caller_seg && inf.status == UNC_SEG_OK && inf.n_rows > segs->seg_off[q + 1] - segs->seg_off[q]) inf.status = UNC_SEG_TRUNCATED;
                 if (segs->info) segs->info[q] = inf;
             }
@@ -439,7 +470,7 @@ struct UploadedRows : AlignRows {
 }  // namespace
 
 // The one way in: a call's record (unc_align_call_t, include/uncalled_hip.h) under the name of the entry point that filled it
-static int align_dispatch(const unc_align_call_t &u, const char *who);
+static int align_dispatch(const unc_align_call_t &u, const char *who, unc_pileup_t *pileup = nullptr);
 
 extern "C" int unc_align_call(const unc_align_call_t *call) {
     static const char *who = "unc_align_call";
@@ -494,9 +525,10 @@ extern "C" int unc_align_segments_batch(int device, const unc_params_t *params, 
 #include "unc_refseq.cpp"
 
 // rows as coordinates (u.refseq; the route of unc_refseq.cpp), or the caller's k-mers, uploaded
-static int align_dispatch(const unc_align_call_t &u, const char *who) {
+static int align_dispatch(const unc_align_call_t &u, const char *who, unc_pileup_t *pileup) {
     const AlignCall c{who, u.device, u.params, u.opts, u.n_reads, u.raw, u.offsets, u.calib, u.on_device, u.n_queries, u.queries,
-                      u.workspace_bytes, u.results, u.levels, u.lev_off, u.path, u.path_off, u.stream, u.segs, u.model, u.accumulate};
+                      u.workspace_bytes, u.results, u.levels, u.lev_off, u.path, u.path_off, u.stream, u.segs, u.model, u.accumulate,
+                      pileup, pileup ? u.stretches : nullptr};
     if (u.refseq || u.stretches) return align_ref(c, u.refseq, u.stretches, u.kmers_out, u.kmers_off);
     if (!u.raw || !u.offsets || !u.calib || !u.queries || !u.kmers || !u.km_off || !u.results) return fail(UNC_ERR_ARG, "%s: null argument", who);
     UploadedRows rows(u.kmers, u.km_off, u.n_queries);
@@ -505,3 +537,22 @@ static int align_dispatch(const unc_align_call_t &u, const char *who) {
 
 // the training accumulator's host side is compiled as part of this translation unit in the same way
 #include "unc_model_acc.cpp"
+// and so is the pile-up's
+#include "unc_pileup.cpp"
+
+// unc_align_call with a pile-up behind the segments (and behind the accumulator, when there is one): the same record, the same body
+extern "C" int unc_align_pileup_call(const unc_align_call_t *call, unc_pileup_t *pileup) {
+    static const char *who = "unc_align_pileup_call";
+    if (!pileup) return unc_align_call(call);
+    if (!call) return fail(UNC_ERR_ARG, "%s: null argument", who);
+    if (call->size < sizeof(uint32_t) || call->size > sizeof(unc_align_call_t))
+        return fail(UNC_ERR_ARG, "%s: size %u is not that of a record of this library (%zu)", who, call->size, sizeof(unc_align_call_t));
+    unc_align_call_t u;
+    memset(&u, 0, sizeof u);
+    memcpy(&u, call, call->size);
+    if (u.kmers || !u.refseq || !u.stretches)
+        return fail(UNC_ERR_ARG, "%s: a pile-up needs the rows as refseq and stretches: k-mer arrays have no coordinates", who);
+    if (pileup_refseq(pileup) != u.refseq || pileup_device(pileup) != u.refseq->device)
+        return fail(UNC_ERR_ARG, "%s: the pile-up was made for another packed reference or device", who);
+    return align_dispatch(u, who, pileup);
+}

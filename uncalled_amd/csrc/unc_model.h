@@ -49,6 +49,31 @@ inline void model_build_tables(const float *pairs2048, bool cmpl, ModelTables *o
 
 // the compiled-in r9.4 template pairs
 inline void model_default_pairs(float *pairs2048) { memcpy(pairs2048, UNC_R94_MEAN_STDV_BITS, 2 * UNC_NKMER * sizeof(float)); }
+
+// The exact finish of a bin of fixed-point sums (n records, S the sum of q, SS = hi * 2^64 + lo the sum of q * q, q = level * 2^20),
+// shared by the training accumulator (unc_model_acc.cpp) and the pile-up (unc_pileup.cpp).  V = n * SS - S * S in unsigned 128-bit
+// integers (Cauchy-Schwarz: never negative); false if n * SS leaves 128 bits
+typedef unsigned __int128 u128;
+inline bool sums_variance(uint64_t n, int64_t S, uint64_t lo, uint64_t hi, u128 *V) {
+    const u128 SS = ((u128)hi << 64) | lo;
+    if (n && SS > ~(u128)0 / n) return false;
+    const u128 mag = S < 0 ? (u128)(0 - (uint64_t)S) : (u128)(uint64_t)S;
+    *V = (u128)n * SS - mag * mag;
+    return true;
+}
+// mean and deviation in levels, in double: one rounding per written operation, the 128-bit to double conversion round-to-nearest
+constexpr double SUMS_Q_ONE = 1048576.0;      // 2^20, MODEL_Q_ONE of model_dev.h
+inline double sums_mean(uint64_t n, int64_t S) {
+    double mean = (double)S / (double)n;
+    mean = mean / SUMS_Q_ONE;
+    return mean;
+}
+inline double sums_sd(uint64_t n, u128 V) {
+    double sd = sqrt((double)V);
+    sd = sd / (double)n;
+    sd = sd / SUMS_Q_ONE;
+    return sd;
+}
 }  // namespace unc
 
 // The object: immutable once made.  Its tables for the alignment (not complemented) are built with it; their copy on a device is

@@ -124,24 +124,15 @@ extern "C" int unc_model_acc_finish(const unc_model_acc_t *acc, const unc_model_
     float pairs[2 * UNC_NKMER];
     if (prior) memcpy(pairs, prior->pairs, sizeof pairs);
     else model_default_pairs(pairs);
-    typedef unsigned __int128 u128;
+    static_assert(SUMS_Q_ONE == MODEL_Q_ONE, "the finish divides by the scale the kernel multiplies with");
     const uint64_t need = min_obs > 2 ? min_obs : 2;
     uint32_t kept = 0;
     for (uint32_t k = 0; k < (uint32_t)UNC_NKMER; ++k) {
-        const u128 SS = ((u128)hi[k] << 64) | lo[k];
-        if (n[k] && SS > ~(u128)0 / n[k]) return fail(UNC_ERR_ARG, "unc_model_acc_finish: k-mer %u: n * SS leaves 128 bits", k);
-        const u128 mag = S[k] < 0 ? (u128)(0 - (uint64_t)S[k]) : (u128)(uint64_t)S[k];
-        const u128 nSS = (u128)n[k] * SS, S2 = mag * mag;
-        const u128 V = nSS - S2;        // Cauchy-Schwarz: n * SS >= S * S
+        u128 V = 0;
+        if (!sums_variance(n[k], S[k], lo[k], hi[k], &V)) return fail(UNC_ERR_ARG, "unc_model_acc_finish: k-mer %u: n * SS leaves 128 bits", k);
         if (n[k] < need || V == 0) { ++kept; continue; }
-        const double dn = (double)n[k];
-        double mean = (double)S[k] / dn;
-        mean = mean / MODEL_Q_ONE;
-        double sd = sqrt((double)V);
-        sd = sd / dn;
-        sd = sd / MODEL_Q_ONE;
-        pairs[2 * k] = (float)mean;
-        pairs[2 * k + 1] = (float)sd;
+        pairs[2 * k] = (float)sums_mean(n[k], S[k]);
+        pairs[2 * k + 1] = (float)sums_sd(n[k], V);
     }
     if (n_kept_prior) *n_kept_prior = kept;
     return unc_model_from_pairs(pairs, out);
