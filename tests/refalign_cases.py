@@ -40,6 +40,26 @@ def tiny_reference(tmp_path, m, seed=5):
     return prefix, seqs
 
 
+MULTI_LENS = (141, 4, 131075, 150, 132703)
+MULTI_BINS = 528106            # 2 * (137 + 0 + 131071 + 146 + 132699): the default pile-up's table, 516 workgroups of the covered-bin kernels
+
+
+def multi_reference(tmp_path, seed=7):
+    """five sequences without N: the second is shorter than a k-mer, the third and the fifth start at offsets 145 and 131370, no
+    multiples of 4, and the default pile-up's table takes k_pileup_scan three passes -> (prefix, [sequence strings])"""
+    from uncalled_amd import build_index
+    rng = np.random.default_rng(seed)
+    lens = MULTI_LENS
+    assert sum(lens[:2]) % 4 and sum(lens[:4]) % 4 and lens[1] < 5
+    assert 2 * sum(max(0, n - 4) for n in lens) == MULTI_BINS and -(-MULTI_BINS // 1024) == 516 > 2 * 256
+    seqs = ["".join(np.array(list("ACGT"))[rng.integers(0, 4, n)]) for n in lens]
+    fa = tmp_path / "multi.fa"
+    fa.write_text("".join(">m%d\n%s\n" % (i, s) for i, s in enumerate(seqs)))
+    prefix = str(tmp_path / "multi")
+    build_index.build_from_fasta(str(fa), prefix)
+    return prefix, seqs
+
+
 def random_reference(tmp_path, n_bases, seed=6, name="long"):
     from uncalled_amd import build_index
     rng = np.random.default_rng(seed)
@@ -252,26 +272,75 @@ def check_contract(G, refseq, index, prefix, seq_len, small):
     return seen
 
 
+def refused_stretch(G, refseq, good_s, s):
+    """unc_align_ref_batch on a good stretch and on s: UNC_ERR_ARG and no result written; a stretch below five bases is named"""
+    from uncalled_amd import capi
+    L = refseq.L
+    res = np.full(2, 0xAB, np.uint8).repeat(capi.ALIGN_RESULT.itemsize).view(capi.ALIGN_RESULT)
+    qs = np.zeros(2, capi.ALIGN_QUERY)
+    qs["read"], qs["smp_st"], qs["smp_en"] = 0, 1000, 1400
+    ss = capi._stretches([good_s, s])
+    rc = L.unc_align_ref_batch(refseq.h, None, None, len(G.offsets) - 1, G.raw.ctypes.data, G.offsets.ctypes.data, G.calib.ctypes.data, 0, 2,
+                               qs.ctypes.data, ss.ctypes.data, 0, res.ctypes.data, None, None, None, None, None, None, None)
+    assert rc == ERR_ARG and (res.view(np.uint8) == 0xAB).all(), s
+    if s[2] - s[1] < 5 and s[1] <= s[2]:
+        assert b"query 1 has no k-mers" in L.unc_last_error()
+
+
+def multi_stretches(G, members, lens):
+    """a stretch per golden query on multi_reference's sequences 0, 2, 3 and 4 in turn, as many k-mers as the golden has (the whole
+    sequence where it holds fewer); per sequence the stretches start at its first base, end at its last and lie between, on both strands"""
+    out = []
+    for i, c in enumerate(members):
+        rid = (0, 2, 3, 4)[i % 4]
+        n = min(int(G.kmers(c).size) + 4, lens[rid])
+        st = (0, lens[rid] - n, (997 * c) % (lens[rid] - n + 1))[(i // 4) % 3]
+        out.append((rid, st, st + n, bool((i // 4) & 1)))
+    return out
+
+
+def check_multi(G, refseq, index, prefix, lens, small):
+    """19. the alignment contract on sequences behind the first: unc_align_ref_batch against unc_align_batch fed unc_ref_kmers' output
+    (run_both: every byte of results, levels, paths and what lies around them) for stretches on sequences 0, 2, 3 and 4, both strands;
+    among them every such sequence's first five bases, its last five, and the two short sequences whole.  A stretch in the sequence of
+    4 bases has no k-mers and rid == 5 names no sequence: refused, nothing written -> queries compared"""
+    from uncalled_amd import capi
+    assert list(lens) == list(MULTI_LENS)
+    every = [c for c in range(G.n) if not small or G.signals[G.query(c)[0]].size < 20000]
+    stretches = multi_stretches(G, every, lens)
+    assert {(s[0], s[3]) for s in stretches} == {(r, f) for r in (0, 2, 3, 4) for f in (True, False)}
+    assert {s[0] for s in stretches if s[1] == 0} == {0, 2, 3, 4} == {s[0] for s in stretches if s[2] == lens[s[0]]}
+    queries = [G.query(c) for c in every]
+    short = G.query(G.idx("events_50"))
+    for rid in (0, 2, 3, 4):
+        for fwd in (True, False):
+            stretches += [(rid, 0, 5, fwd), (rid, lens[rid] - 5, lens[rid], fwd)] + ([(rid, 0, lens[rid], fwd)] if lens[rid] < 200 else [])
+    queries += [short] * (len(stretches) - len(queries))
+    seen = 0
+    for opts, kw in ((capi.align_opts(), {}), (capi.align_opts(dtw=capi.DTWParams(capi.DTW_ROW, capi.DTW_R94D, 2, 1, 100)), {}),
+                     (capi.align_opts(band=1 << 20), dict(workspace=200000))):
+        res, rc = run_both(G, refseq, index, prefix, queries, stretches, opts, **kw)
+        assert rc == 0, refseq.L.unc_last_error()
+        assert capi.DTW_OK in set(map(int, res["status"])) and int((res["status"] == capi.DTW_OK).sum()) > len(queries) // 2
+        seen += len(queries)
+    assert capi.dtw_last_timing(refseq.L)[1] >= 2
+    good_s = (2, 100, 144, True)
+    for s in ((1, 0, 4, True), (1, 0, 4, False), (5, 0, 30, True), (3, 0, 151, True), (2, lens[2] - 10, lens[2] + 1, False)):
+        refused_stretch(G, refseq, good_s, s)
+    return seen
+
+
 def check_align_argument_errors(G, refseq, index, prefix, seq_len):
     """what unc_align_batch refuses, and the stretches unc_refseq_kmers_batch refuses, and a stretch of four bases: UNC_ERR_ARG
     before any result is written"""
     from uncalled_amd import capi
-    L = refseq.L
     good_q, good_s = (0, 1000, 1400), (0, 100, 144, True)
     n0 = G.signals[0].size
     for q in ((0, 0, n0 + 1), (0, 200, 100), (len(G.signals), 0, 0)):       # both entry points refuse these, with the same code
         res, rc = run_both(G, refseq, index, prefix, [good_q, q], [good_s, good_s])
         assert rc == ERR_ARG, q
     for s in ((1, 100, 144, True), (-1, 100, 144, True), (0, 144, 100, True), (0, 100, seq_len + 1, False), (0, 100, 104, True), (0, 7, 7, False)):
-        res = np.full(2, 0xAB, np.uint8).repeat(capi.ALIGN_RESULT.itemsize).view(capi.ALIGN_RESULT)
-        qs = np.zeros(2, capi.ALIGN_QUERY)
-        qs["read"], qs["smp_st"], qs["smp_en"] = 0, 1000, 1400
-        ss = capi._stretches([good_s, s])
-        rc = L.unc_align_ref_batch(refseq.h, None, None, len(G.offsets) - 1, G.raw.ctypes.data, G.offsets.ctypes.data, G.calib.ctypes.data, 0, 2,
-                                   qs.ctypes.data, ss.ctypes.data, 0, res.ctypes.data, None, None, None, None, None, None, None)
-        assert rc == ERR_ARG and (res.view(np.uint8) == 0xAB).all(), s
-        if s[2] - s[1] < 5 and s[1] <= s[2]:
-            assert b"query 1 has no k-mers" in L.unc_last_error()
+        refused_stretch(G, refseq, good_s, s)
     # opts the pipeline refuses, through the binding
     import pytest
     for o in (capi.align_opts(dtw=capi.DTWParams(3, 0, 1, 1, 1)), capi.align_opts(dtw=capi.DTWParams(capi.DTW_ROW, 0, 1, 1, 1), band=3)):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pileup_cases as pc
+import refalign_cases as rc
 import segments_cases as sc
 from conftest import EX_PREFIX, GOLD, ROOT
 
@@ -28,6 +29,17 @@ def X(L):
 @pytest.fixture(scope="module")
 def reads():
     return sc.Reads()
+
+
+@pytest.fixture(scope="module")
+def M(L, tmp_path_factory):
+    """five sequences; the default table must keep k_pileup_scan at three passes"""
+    prefix, seqs = rc.multi_reference(tmp_path_factory.mktemp("multi"))
+    ctx = pc.Ctx(L, prefix, seqs)
+    assert ctx.lens == list(rc.MULTI_LENS) == [len(s) for s in seqs]
+    n_bins = ctx.pileup().n_bins()
+    assert n_bins == 528106 and -(-n_bins // pc.SCAN_CHUNK) == 516
+    return ctx
 
 
 def test_layout_and_symbols(L):
@@ -87,6 +99,36 @@ def test_merge(X):
 
 def test_refusals(X, reads):
     pc.case_refusals(X, reads)
+
+
+def test_sequences(M):
+    pc.case_sequences(M)
+
+
+def test_stats_sequences(M):
+    pc.case_stats_sequences(M)
+
+
+@pytest.mark.parametrize("fill", ["a", "b", "c", "d", "e"])
+def test_scan_passes(M, fill):
+    """the only check of the barriers around k_pileup_scan's reuse of its shared words: the emulator runs the lanes in order"""
+    pc.case_scan_passes(M, fill, on_gpu=True)
+
+
+def test_scan_merge_gather(M):
+    pc.case_scan_merge_gather(M)
+
+
+def test_alignment_sequences(M, reads):
+    pc.case_alignment_sequences(M, reads)
+
+
+def test_alignment_sequences_band_and_cut(M, reads):
+    pc.case_alignment_sequences_band_and_cut(M, reads)
+
+
+def test_alignment_sequences_accumulator_and_regions(M, reads):
+    pc.case_alignment_sequences_accumulator_and_regions(M, reads)
 
 
 # ---- the command line

@@ -71,6 +71,20 @@ def test_align_ref_batch_equals_align_batch_fed_ref_kmers(G, example):
     assert rc.check_contract(G, rs, ix, EX_PREFIX, ix.seq_len(0), small=False) > 250
 
 
+@pytest.fixture(scope="module")
+def multi(hip_lib, tmp_path_factory):
+    from uncalled_amd import capi
+    prefix, seqs = rc.multi_reference(tmp_path_factory.mktemp("multi"))
+    ix = capi.Index(prefix, lib=hip_lib)
+    return ix, capi.RefSeq(ix, prefix), prefix, [len(s) for s in seqs]
+
+
+def test_align_ref_batch_on_later_sequences(G, multi):
+    ix, rs, prefix, lens = multi
+    assert [ix.seq_len(r) for r in range(5)] == lens
+    assert rc.check_multi(G, rs, ix, prefix, lens, small=False) > 100
+
+
 def test_align_argument_errors_write_nothing(G, example):
     ix, rs = example
     rc.check_align_argument_errors(G, rs, ix, EX_PREFIX, ix.seq_len(0))

@@ -118,6 +118,32 @@ def test_conf_defaults_and_cli_parser():
     assert a.bwa_prefix is None and a.probs == "0.1,0.2" and a.max_sample_dist == 100
 
 
+def test_pileup_region_argument(capsys):
+    """--region's reader on the names of an index it does not load: the last colon separates the name from the range, so a name may
+    hold colons and may be the beginning of another; a range outside its sequence and a name that is not in the list end the
+    program with status 1 and a message"""
+    from uncalled_amd.__main__ import parse_region
+
+    class Stub:
+        lens = [150, 10000, 40, 7]
+
+        def seq_len(self, rid):
+            return self.lens[rid]
+    names = ["chr1", "Escherichia_coli_chromosome:2400000-2410000", "chr10", "chr1:7"]
+    ix = Stub()
+    assert parse_region("chr1:0-150", names, ix) == (0, 0, 150)
+    assert parse_region("chr10:5-40", names, ix) == (2, 5, 40)
+    assert parse_region("chr1:7:3-7", names, ix) == (3, 3, 7)
+    assert parse_region("Escherichia_coli_chromosome:2400000-2410000:6000-7500", names, ix) == (1, 6000, 7500)
+    assert parse_region("chr1:9-9", names, ix) == (0, 9, 9)
+    assert not capsys.readouterr().err
+    for bad in ("chr1:20-10", "chr10:0-41", "chr1:0-151", "chr1:7:0-8", "chr2:0-10", "chr:0-10", "chr1", "chr1:7", "chr10:5", "chr10:-5-9", ":0-5"):
+        with pytest.raises(SystemExit) as e:
+            parse_region(bad, names, ix)
+        assert e.value.code == 1
+        assert capsys.readouterr().err == "Error: --region %s: expected NAME:ST-EN inside a sequence of the index\n" % bad
+
+
 def test_multi_gpu_file_sharding():
     from uncalled_amd.__main__ import get_parser, shard_files
     files = ["f%02d.fast5" % i for i in range(11)] + [None]

@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 import pileup_cases as pc
+import refalign_cases as rc
 import segments_cases as sc
 from conftest import EX_PREFIX, ROOT, build_lock
 
@@ -49,6 +50,17 @@ def reads():
     return sc.Reads()
 
 
+@pytest.fixture(scope="module")
+def M(L, tmp_path_factory):
+    """five sequences; the default table must keep k_pileup_scan at three passes"""
+    prefix, seqs = rc.multi_reference(tmp_path_factory.mktemp("multi"))
+    ctx = pc.Ctx(L, prefix, seqs)
+    assert ctx.lens == list(rc.MULTI_LENS) == [len(s) for s in seqs]
+    n_bins = ctx.pileup().n_bins()
+    assert n_bins == 528106 and -(-n_bins // pc.SCAN_CHUNK) == 516
+    return ctx
+
+
 def test_included_sources_are_part_of_the_build():
     import __graft_entry__ as g
     assert "k_pileup.hip" in g.HIP_INCLUDED and "unc_pileup.cpp" in g.HIP_INCLUDED
@@ -69,6 +81,18 @@ def test_naive_checker_by_hand():
     assert pn.stats(nv.bins[(0, 10, 0)], 1.0, 0.5)[1:] == (2.0, 0.5, 5.0, 2.0 * math.sqrt(2.0))
     assert pn.py_kmer("ACGTAC", 0, True) == 0b0001101100 and pn.py_kmer("ACGTAC", 1, False) == pn.py_kmer("GTACG", 0, True)
     assert nv.keys_in_order()[:3] == [(0, 10, 0), (0, 10, 1), (0, 11, 0)] and len(nv.keys_in_order()) == 12
+    # two sequences, given unsorted: sequence 0 has positions 3 and 4, sequence 1 positions 0..2 and a region of 4 bases without a bin
+    two = pn.Naive([(1, 0, 7), (1, 20, 24), (0, 3, 9)])
+    assert two.keys_in_order() == [(0, 3, 0), (0, 3, 1), (0, 4, 0), (0, 4, 1), (1, 0, 0), (1, 0, 1), (1, 1, 0), (1, 1, 1), (1, 2, 0), (1, 2, 1)]
+    two.add([1, 0, 0, 1, 1, 1, 0], [0, 4, 5, 3, 20, 2, 4], [1, 0, 1, 1, 1, 0, 0], [1.0] * 7, [2] * 7)
+    assert two.bins == {(1, 0, 0): [1, 1 << 20, 1 << 40, 2], (0, 4, 1): [2, 2 << 20, 2 << 40, 4], (1, 2, 1): [1, 1 << 20, 1 << 40, 2]}
+    assert two.counters() == (0, 3, 4)      # (0, 5), (1, 3) and (1, 20) hold no whole k-mer of their regions
+    assert two.covered(1) == [3, 4, 9] == two.covered_of_bins(1) and two.covered(2) == [3] == two.covered_of_bins(2)
+    assert two.covered(1, pn.Naive(two.regions).add([1], [2], [0], [1.0], [1])) == [9] == two.covered_of_bins(1, pn.Naive(two.regions).add([1], [2], [0], [1.0], [1]))
+    assert [two.bin_of(k) for k in two.keys_in_order()] == list(range(10)) and [two.key_of(i) for i in range(10)] == two.keys_in_order()
+    for bad in ((1, 3, 0), (0, 2, 0), (1, 20, 0), (2, 0, 0)):
+        with pytest.raises(KeyError):
+            two.bin_of(bad)
 
 
 @pytest.mark.lanesim
@@ -129,3 +153,39 @@ def test_merge(X):
 @pytest.mark.lanesim
 def test_refusals(X, reads):
     pc.case_refusals(X, reads)
+
+
+@pytest.mark.lanesim
+def test_sequences(M):
+    pc.case_sequences(M)
+
+
+@pytest.mark.lanesim
+def test_stats_sequences(M):
+    pc.case_stats_sequences(M)
+
+
+@pytest.mark.lanesim
+@pytest.mark.parametrize("fill", ["a", "b", "c", "d", "e"])
+def test_scan_passes(M, fill):
+    pc.case_scan_passes(M, fill)
+
+
+@pytest.mark.lanesim
+def test_scan_merge_gather(M):
+    pc.case_scan_merge_gather(M)
+
+
+@pytest.mark.lanesim
+def test_alignment_sequences(M, reads):
+    pc.case_alignment_sequences(M, reads)
+
+
+@pytest.mark.lanesim
+def test_alignment_sequences_band_and_cut(M, reads):
+    pc.case_alignment_sequences_band_and_cut(M, reads)
+
+
+@pytest.mark.lanesim
+def test_alignment_sequences_accumulator_and_regions(M, reads):
+    pc.case_alignment_sequences_accumulator_and_regions(M, reads)

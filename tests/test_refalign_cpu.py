@@ -112,6 +112,21 @@ def test_align_ref_batch_equals_align_batch_fed_ref_kmers(G, example):
     assert rc.check_contract(G, rs, ix, EX_PREFIX, ix.seq_len(0), small=True) > 200
 
 
+@pytest.fixture(scope="module")
+def multi(sim, tmp_path_factory):
+    from uncalled_amd import capi
+    prefix, seqs = rc.multi_reference(tmp_path_factory.mktemp("multi"))
+    ix = capi.Index(prefix, lib=sim)
+    return ix, capi.RefSeq(ix, prefix), prefix, [len(s) for s in seqs]
+
+
+@pytest.mark.lanesim
+def test_align_ref_batch_on_later_sequences(G, multi):
+    ix, rs, prefix, lens = multi
+    assert [ix.seq_len(r) for r in range(5)] == lens
+    assert rc.check_multi(G, rs, ix, prefix, lens, small=True) > 100
+
+
 @pytest.mark.lanesim
 def test_align_argument_errors_write_nothing(G, example):
     ix, rs = example
