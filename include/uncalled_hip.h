@@ -370,6 +370,8 @@ typedef struct {
 #define UNC_DTW_PATH_TRUNCATED 2u   /* path_len exceeds the room the caller gave: score and path_len are right, the first pairs are written */
 #define UNC_DTW_BAND_TOO_NARROW 5u   /* band calls: the band does not hold a path to the last cell: not computed, score and path_len are 0 */
 #define UNC_DTW_LEFT_BAND 6u        /* band calls: the traceback met a cell outside the band and stopped (see unc_dtw_band_batch) */
+#define UNC_DTW_REF_END 7u          /* unc_dtw_adapt_batch: the end cell lies in the last row: the k-mers ran out before the events did.  The
+                                       result is valid as computed; a caller who can extend the reference stretch should */
 typedef struct {
     float score, mean_score;        /* DTW::score / DTW::mean_score, dtw.hpp:126-132 */
     uint64_t path_len;              /* DTW::get_path().size() */
@@ -408,7 +410,41 @@ int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *e
 int unc_dtw_band_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
                        const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
                        const uint64_t *path_off, void *stream);
-/* milliseconds the DTW kernel of the calling thread's last unc_dtw_batch / unc_dtw_band_batch ran (HIP events on the stream, summed
+/* unc_dtw_batch within a band of `band` = B rows that follows the path, with an open end: for a read of which only the start on the
+ * reference is known.  B is 64, 128 or 256; every other argument as unc_dtw_band_batch.  For R rows (k-mers) and C columns (events)
+ * the matrix is swept by anti-diagonals d = i + j, d = 0, 1, ...:
+ *   band        on anti-diagonal d the band holds the B rows [lo_d, lo_d + B), row i at column j = d - i.  lo_d is a signed 32-bit
+ *               value, lo_0 = -B / 2;
+ *   present     the present cells of d are those of the band inside the matrix: rows i_t = max(lo_d, 0, d - (C - 1)) to
+ *               i_b = min(lo_d + B - 1, R - 1, d).  They are computed; no other cell of d is;
+ *   recurrence  the reference's (dtw.hpp:51-74) as unc_dtw_batch states it: the same float additions and multiplications, the same
+ *               cost, the same D <= H <= V tie rule, a global start (D of (0, 0) is 0, everything else outside the matrix FLT_MAX / 2).
+ *               The predecessors of (i, j) on d are H (i, j - 1) on d - 1, V (i - 1, j) on d - 1 and D (i - 1, j - 1) on d - 2; one that
+ *               is not a present cell of its anti-diagonal reads as FLT_MAX / 2;
+ *   move        after d is computed, with s(i) the score of (i, d - i): lo_{d+1} = lo_d + 1 ("down") if s(i_b) < s(i_t); lo_{d+1} = lo_d
+ *               ("right") if s(i_t) < s(i_b); otherwise -- equal scores, i_t == i_b, or a NaN on either side, for which neither
+ *               comparison holds -- down if d is odd and right if d is even.  One exception: if lo_d + B - 1 >= R - 1, the band holds
+ *               the matrix's last row already and the move is right whatever the scores are (a band led by its last row, where
+ *               the path runs once the k-mers are used up, would otherwise leave the matrix before the events end);
+ *   end         the sweep stops after d = R + C - 2, or at the first d that has no present cell (that d is not computed);
+ *   open end    the end cell is the first smallest score among the computed cells of column C - 1, scanned by ascending row from
+ *               +infinity: a cell becomes the candidate if its score compares smaller, so the lowest row wins ties.  If no score
+ *               compares smaller (each is NaN or +infinity) the end cell is the computed cell of column C - 1 in the highest row.
+ *               The score is the end cell's;
+ *   traceback   the reference's (dtw.hpp:100-119) from the end cell to (0, 0).  If it is led to a cell that was not computed -- by
+ *               non-finite scores, or through a cell all of whose predecessors were absent -- it stops: UNC_DTW_LEFT_BAND, path_len
+ *               counts the pairs up to and including the last computed cell, those pairs are written.  If no cell of column C - 1 was
+ *               computed (the band ran off the last row first) the status is UNC_DTW_LEFT_BAND with score 0 and path_len 0;
+ *   statuses    UNC_DTW_REF_END: the end cell lies in row R - 1; everything is as with UNC_DTW_OK.  Where several apply:
+ *               UNC_DTW_LEFT_BAND, then UNC_DTW_PATH_TRUNCATED (the first pair written is the end cell), then UNC_DTW_REF_END.
+ * For finite events a cell's value is never below its full-matrix value, hence: if the path of the full-matrix alignment with the
+ * same open end lies among the computed cells, score and path are that alignment's bit for bit.  Back-pointers take 2 bits per band
+ * cell plus lo_d per anti-diagonal: about (R + C) * (B / 4 + 4) bytes, which is what workspace_bytes, the rounds and
+ * UNC_DTW_TOO_LARGE go by.  band not 64, 128 or 256, or prm->subseq != UNC_DTW_NONE, is UNC_ERR_ARG before anything touches the device. */
+int unc_dtw_adapt_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
+                        const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
+                        const uint64_t *path_off, void *stream);
+/* milliseconds the DTW kernel of the calling thread's last unc_dtw_batch / unc_dtw_band_batch / unc_dtw_adapt_batch ran (HIP events on the stream, summed
  * over its rounds), the rounds it took and the bytes of back-pointers it held at most */
 int unc_dtw_last_timing(float *ms_kernel, uint32_t *rounds, uint64_t *crumb_bytes);
 /* host copies of the three tables of the r9.4 template model the DTW costs read (PoreModel(vector, cmpl=false), pore_model.hpp:77-103) */
@@ -437,14 +473,17 @@ typedef struct {
 #define UNC_ALIGN_NO_MASK 2u        /* every detected event is kept */
 #define UNC_ALIGN_RAW 4u            /* create_events off (dtw_test.cpp:146-148): the calibrated samples of the slice are normalised and aligned */
 #define UNC_ALIGN_TARGET_MODEL 8u   /* normalise to the model's mean and deviation over all k-mers (the line commented out at dtw_test.cpp:118) */
+#define UNC_ALIGN_ADAPTIVE 16u      /* opts.band is the width B of unc_dtw_adapt_batch (64, 128 or 256): the DTW stage runs as that call */
 typedef struct {
     uint32_t flags;         /* UNC_ALIGN_*; a zeroed struct is dtw_test */
     uint32_t max_events;    /* a query with more columns than this is not aligned (dtw_test.cpp:156-159 uses 50000); 0 = no limit */
     unc_dtw_params_t dtw;   /* read with UNC_ALIGN_DTW_PARAMS only */
-    uint32_t band;          /* 0: the full matrix; W > 0: the DTW stage runs as unc_dtw_band_batch with this half-width (global only) */
+    uint32_t band;          /* 0: the full matrix; W > 0: the DTW stage runs as unc_dtw_band_batch with this half-width (global only);
+                               with UNC_ALIGN_ADAPTIVE: as unc_dtw_adapt_batch with this width */
 } unc_align_opts_t;
 /* per-query status: UNC_DTW_OK, UNC_DTW_TOO_LARGE, UNC_DTW_PATH_TRUNCATED (with a band also UNC_DTW_BAND_TOO_NARROW and
- * UNC_DTW_LEFT_BAND) as unc_dtw_batch / unc_dtw_band_batch give them, or one of */
+ * UNC_DTW_LEFT_BAND, with UNC_ALIGN_ADAPTIVE UNC_DTW_LEFT_BAND and UNC_DTW_REF_END) as unc_dtw_batch / unc_dtw_band_batch /
+ * unc_dtw_adapt_batch give them, or one of */
 #define UNC_ALIGN_NO_COLUMNS 3u     /* nothing left to align: the slice is too short for an event, or every event was masked.  Not aligned */
 #define UNC_ALIGN_TOO_MANY 4u       /* more columns than opts.max_events.  Not aligned (counts, target, scale and shift are filled) */
 typedef struct {
@@ -534,7 +573,7 @@ typedef struct {
 } unc_segment_t;
 #define UNC_SEG_OK 0u
 #define UNC_SEG_TRUNCATED 1u    /* the caller's room is smaller than n_rows: the first records are written, as many as the room holds */
-#define UNC_SEG_NONE 2u         /* the query's status is neither UNC_DTW_OK nor UNC_DTW_PATH_TRUNCATED: no path, no records, n_rows 0 */
+#define UNC_SEG_NONE 2u         /* the query's status is none of UNC_DTW_OK, UNC_DTW_PATH_TRUNCATED and UNC_DTW_REF_END: no path, no records, n_rows 0 */
 /* the rows on a query's path are [row_first, row_first + n_rows) (DTW::get_path(), dtw.hpp:100-119: rows and columns fall by at
  * most one per pair); record s is row row_first + s */
 typedef struct { uint32_t row_first, n_rows, status, pad; } unc_seg_info_t;

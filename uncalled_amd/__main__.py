@@ -377,6 +377,26 @@ def clip_paf_queries(queries, reads):
         q["smp_en"] = min(len(samples), q["smp_en"])
 
 
+def extend_paf_queries(queries, reads, index, slack=1.5):
+    """`--adaptive`: a query becomes the read from the hit's first sample to the read's end, against a stretch that starts where the
+    hit starts on its strand (the minus strand runs leftwards from the hit's end) and is ceil(samples * bp_per_sec / sample_rate *
+    slack) bases long, clipped to the sequence.  The adaptive band finds where on it the read ends."""
+    import math
+    from . import capi
+    prm = capi.default_params()
+    names = index.seq_names()
+    for rid, samples, _ in reads:
+        q = queries[rid]
+        if q["ref"] not in names:
+            continue                    # (dtw_align reports it)
+        q["smp_en"] = len(samples)
+        n = max(5, math.ceil((len(samples) - q["smp_st"]) * float(prm.bp_per_sec) / float(prm.sample_rate) * slack))
+        if q["fwd"]:
+            q["ref_en"] = min(q["ref_st"] + n, index.seq_len(names.index(q["ref"])))
+        else:
+            q["ref_st"] = max(q["ref_en"] - n, 0)
+
+
 KMER_BASES = "ACGT"
 
 
@@ -407,13 +427,14 @@ def write_segments(out, q, row_first, segs, km, model_means):
 
 
 def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, device=0, want_paths=False, band=0, segments=False, model=None,
-              accumulate=None, pileup=None, refseq=None):
+              accumulate=None, pileup=None, refseq=None, adaptive=0):
     """The batches behind `dtw`: reads = [(id, int16 samples, (range, offset, digitisation))], queries as load_dtw_queries gives
     them.  Yields per read (id, ALIGN_RESULT record, seconds, k-mers, levels, path, SEGMENT records, SEG_INFO record), in the order of
     `reads`: k-mers, levels and path are None without want_paths, the last two None without segments.  The rows of every alignment
     are made on the device from the queries' coordinates (capi.align_ref_batch); `device` is the index's.  model: a capi.Model in
     place of the r9.4 template; accumulate: a capi.ModelAcc that takes every alignment's records; pileup: a capi.Pileup that takes
-    them at their reference positions, made for `refseq`, the packed reference to align with (None: read here)."""
+    them at their reference positions, made for `refseq`, the packed reference to align with (None: read here).  adaptive: the
+    width of the adaptive band with an open end (capi.align_opts), in place of band."""
     import numpy as np
     from . import capi
     names = index.seq_names()
@@ -434,7 +455,7 @@ def dtw_align(index, prefix, reads, queries, max_events=50000, batch=2048, devic
             qs.append((i, q["smp_st"], q["smp_en"]))
             stretches.append((names.index(q["ref"]), q["ref_st"], q["ref_en"], q["fwd"]))
         t0 = time.time()
-        out = capi.align_ref_batch(refseq, raw, offsets, calib, qs, stretches, opts=capi.align_opts(max_events=max_events, band=band),
+        out = capi.align_ref_batch(refseq, raw, offsets, calib, qs, stretches, opts=capi.align_opts(max_events=max_events, band=band, adaptive=adaptive),
                                    levels=want_paths, paths=want_paths, kmers=want_paths, segments=segments, model=model,
                                    accumulate=accumulate, pileup=pileup)
         sec = (time.time() - t0) / max(1, len(part))
@@ -462,7 +483,7 @@ def load_query_reads(unc, fast5, queries):
 
 
 def train_model(index, prefix, reads, queries, start=None, iters=1, min_obs=2, keep_shared=False, band=0, max_events=50000, batch=2048,
-                device=0, report=None):
+                device=0, report=None, adaptive=0):
     """The iterations behind `train`: every query aligned with the current model (dtw_align, the accumulator on the device, no
     segment outputs), then the accumulator finished into the next model with the current one as the prior.  -> the last model.
     report(iteration, records used, records dropped, k-mers kept from the prior, largest change of a mean)"""
@@ -473,7 +494,7 @@ def train_model(index, prefix, reads, queries, start=None, iters=1, min_obs=2, k
     for it in range(iters):
         acc.reset()
         for _ in dtw_align(index, prefix, reads, queries, max_events=max_events, batch=batch, device=device, band=band, model=model,
-                           accumulate=acc):
+                           accumulate=acc, adaptive=adaptive):
             pass
         n, _, _, _, dropped = acc.read()
         nxt, kept = acc.finish(model, min_obs)
@@ -493,14 +514,24 @@ def train_cmd(args):
     reads = load_query_reads(unc, args.fast5, queries)
     clip_paf_queries(queries, reads)
     index = capi.Index(args.index_prefix, device=args.device)
+    if _adaptive(args):
+        extend_paf_queries(queries, reads, index, args.slack)
 
     def report(it, used, dropped, kept, change):
         sys.stderr.write("iteration %d: %d records used, %d dropped, %d k-mers kept from the prior, largest mean change %.6g\n" % (
             it, used, dropped, kept, change))
 
     model = train_model(index, args.index_prefix, reads, queries, capi.Model.load(args.model) if args.model else None, args.iters,
-                        args.min_obs, args.keep_shared, args.band, args.max_events, args.batch_queries, args.device, report)
+                        args.min_obs, args.keep_shared, args.band, args.max_events, args.batch_queries, args.device, report, args.adaptive)
     model.save(args.out)
+
+
+def _adaptive(args):
+    """--adaptive B as given: 0, or a width the library takes; it excludes --band"""
+    if args.adaptive and (args.adaptive not in (64, 128, 256) or args.band):
+        sys.stderr.write("Error: --adaptive takes 64, 128 or 256 and goes without --band\n")
+        sys.exit(1)
+    return args.adaptive
 
 
 PILEUP_COLUMNS = ("contig", "pos", "strand", "kmer", "cov", "mean", "stdv", "dwell", "model_mean", "model_stdv", "z")
@@ -523,10 +554,13 @@ def pileup_fill(unc, index, prefix, refseq, pileup, fast5, paf, model, args):
     queries = load_paf_queries(paf)
     reads = load_query_reads(unc, fast5, queries)
     clip_paf_queries(queries, reads)
+    if _adaptive(args):
+        extend_paf_queries(queries, reads, index, args.slack)
     done = 0
     for _, r, _, _, _, _, _, _ in dtw_align(index, prefix, reads, queries, max_events=args.max_events, batch=args.batch_queries,
-                                            device=args.device, band=args.band, model=model, pileup=pileup, refseq=refseq):
-        done += int(r["status"]) == capi.DTW_OK
+                                            device=args.device, band=args.band, model=model, pileup=pileup, refseq=refseq,
+                                            adaptive=args.adaptive):
+        done += int(r["status"]) in (capi.DTW_OK, capi.DTW_REF_END)
     return done
 
 
@@ -599,10 +633,15 @@ def dtw_cmd(args):
     if args.paf:
         clip_paf_queries(queries, reads)
     index = capi.Index(args.index_prefix, device=args.device)
+    if _adaptive(args):
+        if not args.paf:
+            sys.stderr.write("Error: --adaptive needs --paf\n")
+            sys.exit(1)
+        extend_paf_queries(queries, reads, index, args.slack)
     model = capi.Model.load(args.model) if args.model else None
     for rid, r, sec, km, lev, path, segs, seg_info in dtw_align(index, args.index_prefix, reads, queries, max_events=args.max_events,
                                                       batch=args.batch_queries, device=args.device, want_paths=args.out_prefix is not None,
-                                                      band=args.band, segments=args.segments, model=model):
+                                                      band=args.band, segments=args.segments, model=model, adaptive=args.adaptive):
         st = int(r["status"])
         if st == capi.ALIGN_TOO_MANY:
             sys.stderr.write("Skipping %s\n" % rid)            # dtw_test.cpp:156-159
@@ -611,7 +650,7 @@ def dtw_cmd(args):
             sys.stdout.write("%s\t%.6g\t%.6g\tstatus %d\n" % (rid, 0.0, sec, st))      # (nothing computed: the line says why)
             sys.stdout.flush()
             continue
-        if st not in (capi.DTW_OK, capi.DTW_LEFT_BAND):
+        if st not in (capi.DTW_OK, capi.DTW_LEFT_BAND, capi.DTW_REF_END):
             sys.stderr.write("Skipping %s: %s\n" % (rid, "no events left to align" if st == capi.ALIGN_NO_COLUMNS else "status %d" % st))
             continue
         if args.out_prefix is not None:
@@ -619,7 +658,7 @@ def dtw_cmd(args):
             with open(args.out_prefix + rid + ".txt", "w") as out:
                 for j, i in path[::-1]:                          # from the start of the alignment to its end
                     out.write("%d\t%d\t%s\t%.6g\t%.6g\n" % (j, i, kmer_str(km[i]), lev[j], abs(float(lev[j]) - float(means[km[i]]))))
-            if args.segments and st == capi.DTW_OK:              # (a path that left the band has no start: no records)
+            if args.segments and st in (capi.DTW_OK, capi.DTW_REF_END):      # (a path that left the band has no start: no records)
                 with open(args.out_prefix + rid + ".segments.tsv", "w") as out:
                     write_segments(out, queries[rid], int(seg_info["row_first"]), segs, km, means)
         sys.stdout.write("%s\t%.6g\t%.6g%s\n" % (rid, float(r["dtw"]["mean_score"]), sec, "\tstatus %d" % st if st else ""))
@@ -716,6 +755,8 @@ def get_parser():
     p.add_argument("--band", type=int, default=0, help="Align within a band of this half-width (in k-mers) around the diagonal: work and memory "
                    "grow with the events times the band, not with events times k-mers (0: the full matrix). A line then ends in "
                    "`status 5` (the band is too narrow to reach the end: not aligned) or `status 6` (the path left the band) where so")
+    p.add_argument("--adaptive", type=int, default=0, metavar="B", help="With --paf: align the whole read from where its hit starts. The query is the read from the hit's first sample to its end, the stretch starts at the hit's start on its strand and is ceil(samples * bp_per_sec / sample_rate * F) bases long (--slack F), and the DTW runs in a band of B k-mers (64, 128 or 256) that follows the path, with an open end. A line then ends in `status 7` where the alignment ends in the stretch's last k-mer (the stretch was too short) or `status 6` where the path left the band")
+    p.add_argument("--slack", type=float, default=1.5, metavar="F", help="With --adaptive: the stretch is F times the bases the samples are expected to cover")
     p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
 
@@ -735,6 +776,8 @@ def get_parser():
     p.add_argument("--min-obs", type=int, default=10, help="Records a k-mer needs for a row of its own (at least 2)")
     p.add_argument("--keep-shared", action="store_true", help="Also count a k-mer whose first event is the previous k-mer's last")
     p.add_argument("--band", type=int, default=0, help="As in dtw")
+    p.add_argument("--adaptive", type=int, default=0, metavar="B", help="As in dtw: whole reads, aligned from where their hits start")
+    p.add_argument("--slack", type=float, default=1.5, metavar="F", help="With --adaptive: the stretch is F times the bases the samples are expected to cover")
     p.add_argument("--max-events", type=int, default=50000, help="As in dtw")
     p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")
@@ -757,6 +800,8 @@ def get_parser():
     p.add_argument("--model", type=str, default=None, help="Pore model file to align with and compare against (default: the built-in r9.4 template)")
     p.add_argument("--keep-shared", action="store_true", help="Also count a k-mer whose first event is the previous k-mer's last")
     p.add_argument("--band", type=int, default=0, help="As in dtw")
+    p.add_argument("--adaptive", type=int, default=0, metavar="B", help="As in dtw: whole reads, aligned from where their hits start")
+    p.add_argument("--slack", type=float, default=1.5, metavar="F", help="With --adaptive: the stretch is F times the bases the samples are expected to cover")
     p.add_argument("--max-events", type=int, default=50000, help="As in dtw")
     p.add_argument("--batch-queries", type=int, default=2048, help="Queries per GPU batch")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal")

@@ -126,6 +126,7 @@ DTW_NONE, DTW_ROW, DTW_COL = 0, 1, 2                  # DTWSubSeq
 DTW_R94P, DTW_R94D = 0, 1                             # dtwcost_r94p / dtwcost_r94d
 DTW_OK, DTW_TOO_LARGE, DTW_PATH_TRUNCATED = 0, 1, 2   # unc_dtw_result_t.status
 DTW_BAND_TOO_NARROW, DTW_LEFT_BAND = 5, 6             # ... of band calls (3 and 4 are the ALIGN_* ones below)
+DTW_REF_END = 7                                       # ... of adaptive calls: the end cell lies in the last row, the result is valid
 # the presets of dtw.hpp:15-28 (cost r94p; .with_cost(DTW_R94D) for the other)
 DTW_EVENT_GLOB = DTWParams(DTW_NONE, DTW_R94P, 2, 1, 100)
 DTW_EVENT_QSUB = DTWParams(DTW_COL, DTW_R94P, 2, 1, 100)
@@ -142,6 +143,7 @@ class AlignOpts(C.Structure):
 
 
 ALIGN_DTW_PARAMS, ALIGN_NO_MASK, ALIGN_RAW, ALIGN_TARGET_MODEL = 1, 2, 4, 8       # unc_align_opts_t.flags
+ALIGN_ADAPTIVE = 16                                                               # ... band is unc_dtw_adapt_batch's width
 ALIGN_NO_COLUMNS, ALIGN_TOO_MANY = 3, 4                                           # unc_align_result_t.status beside the DTW_* ones
 ALIGN_QUERY = np.dtype([("read", "<u4"), ("pad", "<u4"), ("smp_st", "<u8"), ("smp_en", "<u8")])
 ALIGN_RESULT = np.dtype([("dtw", DTW_RESULT), ("n_events", "<u4"), ("n_kept", "<u4"), ("tgt_mean", "<f4"), ("tgt_stdv", "<f4"),
@@ -274,6 +276,8 @@ def load(path=None):
         L.unc_dtw_batch.argtypes = [C.c_int, u32, vp, vp, vp, vp, C.POINTER(DTWParams), u64, vp, vp, vp, vp]
         if hasattr(L, "unc_dtw_band_batch"):
             L.unc_dtw_band_batch.argtypes = [C.c_int, u32, vp, vp, vp, vp, C.POINTER(DTWParams), u32, u64, vp, vp, vp, vp]
+        if hasattr(L, "unc_dtw_adapt_batch"):
+            L.unc_dtw_adapt_batch.argtypes = [C.c_int, u32, vp, vp, vp, vp, C.POINTER(DTWParams), u32, u64, vp, vp, vp, vp]
         L.unc_dtw_last_timing.argtypes = [C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(u64)]
         L.unc_dtw_model_tables.argtypes = [vp, vp, vp]
         L.unc_dtw_model_tables.restype = None
@@ -554,15 +558,19 @@ def dtw_model_tables(lib=None):
     return a, b, c
 
 
-def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, device=0, stream=None, lib=None, full=False, band=0, model=None):
+def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, device=0, stream=None, lib=None, full=False, band=0, model=None,
+              adaptive=0):
     """unc_dtw_batch: DTWr94p / DTWr94d (dtw.hpp) of events_list[a] (columns) against kmers_list[a] (rows) for every a, on the GPU.
     -> (scores float32[n], mean scores float32[n], paths): paths[a] is DTW::get_path() as an (len, 2) uint32 array of (event, k-mer)
     pairs, end cell first (None with paths=False, and for an alignment that was not computed: status DTW_TOO_LARGE or
     DTW_BAND_TOO_NARROW).  full=True returns the DTW_RESULT records (score, mean_score, path_len, status) in place of the first two.
     band=W > 0: unc_dtw_band_batch, the same within a band of half-width W around the diagonal (global alignment only); with
     status DTW_LEFT_BAND paths[a] holds the pairs up to the last cell in the band.  model: a Model whose tables the costs read
-    (unc_dtw_model_batch; None: the r9.4 template)."""
+    (unc_dtw_model_batch; None: the r9.4 template).  adaptive=B (64, 128 or 256): unc_dtw_adapt_batch, a band of B rows that follows
+    the path from (0, 0) to an open end in the last column; status DTW_REF_END: the end cell lies in the last row."""
     L = lib or load()
+    if adaptive and (band or model is not None):
+        raise ValueError("adaptive= goes with neither band= nor model=")
     n = len(events_list)
     if n != len(kmers_list):
         raise ValueError("as many k-mer arrays as event arrays are needed")
@@ -582,7 +590,10 @@ def dtw_batch(events_list, kmers_list, params, workspace_bytes=0, paths=True, de
         path_off = np.cumsum([0] + [max(0, e.size + k.size - 1) for e, k in zip(evs, kms)]).astype(np.uint64)
         path = np.empty((max(1, int(path_off[-1])), 2), dtype=np.uint32)
     args = (int(workspace_bytes), res.ctypes.data, path.ctypes.data if paths else None, path_off.ctypes.data if paths else None, stream)
-    if model is not None:
+    if adaptive:
+        _check(L, L.unc_dtw_adapt_batch(int(device), n, ev.ctypes.data, ev_off.ctypes.data, km.ctypes.data, km_off.ctypes.data,
+                                        C.byref(params), int(adaptive), *args))
+    elif model is not None:
         _check(L, L.unc_dtw_model_batch(int(device), model.h, n, ev.ctypes.data, ev_off.ctypes.data, km.ctypes.data, km_off.ctypes.data,
                                         C.byref(params), int(band), *args))
     elif band:
@@ -608,16 +619,18 @@ def dtw_last_timing(lib=None):
     return ms.value, rounds.value, nbytes.value
 
 
-def align_opts(dtw=None, mask=True, create_events=True, target="kmers", max_events=0, band=0):
+def align_opts(dtw=None, mask=True, create_events=True, target="kmers", max_events=0, band=0, adaptive=0):
     """AlignOpts from words: dtw = a DTWParams (None: dtw_test's), target = "kmers" | "model", band = the DTW's half-width (0: the
-    full matrix)."""
+    full matrix), adaptive = the width B of the adaptive band with an open end (in place of band)."""
     if target not in ("kmers", "model"):
         raise ValueError("target is 'kmers' or 'model'")
+    if adaptive and band:
+        raise ValueError("adaptive= and band= exclude each other")
     o = AlignOpts()
     o.flags = (ALIGN_DTW_PARAMS if dtw is not None else 0) | (0 if mask else ALIGN_NO_MASK) | (0 if create_events else ALIGN_RAW) | \
-        (ALIGN_TARGET_MODEL if target == "model" else 0)
+        (ALIGN_TARGET_MODEL if target == "model" else 0) | (ALIGN_ADAPTIVE if adaptive else 0)
     o.max_events = int(max_events)
-    o.band = int(band)
+    o.band = int(adaptive) if adaptive else int(band)
     if dtw is not None:
         o.dtw = dtw
     return o
@@ -716,7 +729,7 @@ def _align(L, entries, first, rows_args, n_rows, tap_args, tap, raw, offsets, ca
     if levels:
         out.append([lev[int(lev_off[q]):int(lev_off[q]) + int(res["n_kept"][q])].copy() for q in range(n)])
     if paths:
-        done = (DTW_OK, DTW_PATH_TRUNCATED, DTW_LEFT_BAND)
+        done = (DTW_OK, DTW_PATH_TRUNCATED, DTW_LEFT_BAND, DTW_REF_END)
         out.append([path[int(path_off[q]):int(path_off[q]) + int(res["dtw"]["path_len"][q])].copy() if res["status"][q] in done else None
                     for q in range(n)])
     if tap is not None:

@@ -56,6 +56,19 @@ __host__ __device__ inline uint64_t dtw_band_steps(uint32_t rows, uint32_t cols,
     return dtw_strips(rows) * (dtw_band_width(rows, cols, W) + 63);
 }
 
+// ---- the adaptive band (unc_dtw_adapt_batch, include/uncalled_hip.h): B rows per anti-diagonal, B / 64 cells per lane.  Per block
+// of 16 anti-diagonals one word per band cell (cell c of lane l: word (block * B / 64 + c) * 64 + l), then lo_d as int32 per
+// anti-diagonal, padded to whole blocks of 64: about (rows + cols) * (B / 4 + 4) bytes.
+__host__ __device__ inline bool dtw_adapt_band_ok(uint32_t B) { return B == 64 || B == 128 || B == 256; }
+__host__ __device__ inline uint64_t dtw_adapt_diags(uint32_t rows, uint32_t cols) { return (uint64_t)rows + cols - 1; }
+// the first word of lo_d = the words of back-pointers
+__host__ __device__ inline uint64_t dtw_adapt_lo_first(uint32_t rows, uint32_t cols, uint32_t B) {
+    return (dtw_adapt_diags(rows, cols) + 15) / 16 * B;
+}
+__host__ __device__ inline uint64_t dtw_adapt_words(uint32_t rows, uint32_t cols, uint32_t B) {
+    return dtw_adapt_lo_first(rows, cols, B) + (dtw_adapt_diags(rows, cols) + 63) / 64 * 64;
+}
+
 struct DtwJob {
     uint64_t ev_off, km_off;      // first event / k-mer in the batch's arrays
     uint64_t crumb_off;           // first word of the alignment's back-pointers
@@ -74,6 +87,7 @@ struct DtwBatch {
     uint32_t n_jobs;
     uint32_t subseq;
     uint32_t band;                // 0: the full matrix; else the half-width W, subseq is UNC_DTW_NONE, and crumb_off is of the banded layout
+    uint32_t adaptive;            // != 0: band is the adaptive width B (dtw_adapt_band_ok), crumb_off is of the adaptive layout, no lines
     float dw, hw, vw;
     uint32_t *crumbs;
     float *lines;
@@ -94,6 +108,8 @@ void launch_dtw(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st)
 // and after each round's kernel, before anything is copied out and the next round reuses the buffers, the hook is handed the round.
 // What the caller gets is as without it: path_cap pairs at most, and UNC_DTW_PATH_TRUNCATED by path_cap.
 // model (may be null: the template's, kept per device for the life of the process): whose tables the costs are read from.
+// adaptive: band is the adaptive width B (the caller has checked dtw_adapt_band_ok and a global alignment): the adaptive layout,
+// the queue in descending anti-diagonals, no UNC_DTW_BAND_TOO_NARROW.
 struct DtwRoundHook {
     virtual ~DtwRoundHook() = default;
     // d_jobs: the round's jobs as the kernel saw them (path_cap = rows + cols - 1); n_rows: the sum of their rows; d_res is indexed
@@ -102,7 +118,8 @@ struct DtwRoundHook {
 };
 int dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
                    const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                   const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook = nullptr, const unc_model *model = nullptr);
+                   const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook = nullptr, const unc_model *model = nullptr,
+                   bool adaptive = false);
 // the template model's 3 x 1024 floats on `device` (uploaded once per device) and on the host; dtw_model_default: with its mean and
 // deviation over all k-mers (unc_model.h)
 int dtw_model_device(int device, const float **out);

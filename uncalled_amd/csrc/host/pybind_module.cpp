@@ -18,13 +18,21 @@ extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const 
 extern "C" int unc_dtw_band_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
                                   const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes,
                                   unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) __attribute__((weak));
+extern "C" int unc_dtw_adapt_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
+                                   const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes,
+                                   unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) __attribute__((weak));
 namespace {
 template <uint32_t COST> struct DtwOne {
     std::vector<std::pair<uint64_t, uint64_t>> path;
     float score_sum = 0, mean = 0;
+    uint32_t st = UNC_DTW_OK;
     // band (not in the reference's signature): 0 = the full matrix, W > 0 = unc_dtw_band_batch with that half-width
-    DtwOne(const std::vector<float> &means, const std::vector<uint16_t> &kmers, const unc_dtw_params_t &prms, uint32_t band = 0) {
-        if (!unc_dtw_batch || (band && !unc_dtw_band_batch)) throw std::runtime_error("this build of the library has no unc_dtw_batch");
+    // adaptive (neither): B > 0 = unc_dtw_adapt_batch with that width, an open end in the last column; status() tells UNC_DTW_REF_END
+    DtwOne(const std::vector<float> &means, const std::vector<uint16_t> &kmers, const unc_dtw_params_t &prms, uint32_t band = 0,
+           uint32_t adaptive = 0) {
+        if (!unc_dtw_batch || (band && !unc_dtw_band_batch) || (adaptive && !unc_dtw_adapt_batch))
+            throw std::runtime_error("this build of the library has no unc_dtw_batch");
+        if (band && adaptive) throw std::runtime_error("band and adaptive exclude each other");
         unc_dtw_params_t p = prms;
         p.cost = COST;
         const uint64_t ev_off[2] = {0, means.size()}, km_off[2] = {0, kmers.size()};
@@ -36,12 +44,14 @@ template <uint32_t COST> struct DtwOne {
         const uint16_t none_k = 0;
         const float *e = means.empty() ? &none_f : means.data();
         const uint16_t *k = kmers.empty() ? &none_k : kmers.data();
-        const int rc = band ? unc_dtw_band_batch(0, 1, e, ev_off, k, km_off, &p, band, 0, &r, pairs.data(), path_off, nullptr)
+        const int rc = adaptive ? unc_dtw_adapt_batch(0, 1, e, ev_off, k, km_off, &p, adaptive, 0, &r, pairs.data(), path_off, nullptr)
+                       : band ? unc_dtw_band_batch(0, 1, e, ev_off, k, km_off, &p, band, 0, &r, pairs.data(), path_off, nullptr)
                             : unc_dtw_batch(0, 1, e, ev_off, k, km_off, &p, 0, &r, pairs.data(), path_off, nullptr);
         if (rc != UNC_OK) throw std::runtime_error(unc_last_error());
         if (r.status == UNC_DTW_BAND_TOO_NARROW) throw std::runtime_error("the band is too narrow to reach the last cell");
         if (r.status == UNC_DTW_LEFT_BAND) throw std::runtime_error("the traceback left the band");
-        if (r.status != UNC_DTW_OK) throw std::runtime_error("the alignment does not fit the device's memory");
+        if (r.status != UNC_DTW_OK && r.status != UNC_DTW_REF_END) throw std::runtime_error("the alignment does not fit the device's memory");
+        st = r.status;
         score_sum = r.score; mean = r.mean_score;
         path.reserve(r.path_len);
         for (uint64_t k = 0; k < r.path_len; ++k) path.emplace_back(pairs[2 * k], pairs[2 * k + 1]);
@@ -49,11 +59,12 @@ template <uint32_t COST> struct DtwOne {
     std::vector<std::pair<uint64_t, uint64_t>> get_path() const { return path; }
     float score() const { return score_sum; }
     float mean_score() const { return mean; }
+    uint32_t status() const { return st; }
 };
 template <class T> void bind_dtw(py::class_<T> &c) {
-    c.def(py::init<const std::vector<float> &, const std::vector<uint16_t> &, const unc_dtw_params_t &, uint32_t>(), py::arg("means"),
-          py::arg("kmers"), py::arg("prms"), py::arg("band") = 0u)
-        .def("get_path", &T::get_path).def("score", &T::score).def("mean_score", &T::mean_score);
+    c.def(py::init<const std::vector<float> &, const std::vector<uint16_t> &, const unc_dtw_params_t &, uint32_t, uint32_t>(), py::arg("means"),
+          py::arg("kmers"), py::arg("prms"), py::arg("band") = 0u, py::arg("adaptive") = 0u)
+        .def("get_path", &T::get_path).def("score", &T::score).def("mean_score", &T::mean_score).def("status", &T::status);
 }
 }  // namespace
 

@@ -362,8 +362,15 @@ template <int COST> __global__ void __launch_bounds__(64) k_dtw_band(DtwBatch B)
 }
 
 }  // namespace
+}  // namespace unc
+
+// k_dtw_adapt, the band that follows the path, is compiled as part of this translation unit: it shares the cost and the tie rule above
+#include "k_dtw_adapt.hip"
+
+namespace unc {
 
 void launch_dtw(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st) {
+    if (b.adaptive) { launch_dtw_adapt(b, cost, grid, st); return; }
     if (b.band) {
         if (cost == UNC_DTW_R94D) hipLaunchKernelGGL(k_dtw_band<(int)UNC_DTW_R94D>, dim3(grid), dim3(64), 0, st, b);
         else hipLaunchKernelGGL(k_dtw_band<(int)UNC_DTW_R94P>, dim3(grid), dim3(64), 0, st, b);

@@ -31,8 +31,9 @@ __global__ void __launch_bounds__(64) k_align_segments(SegArgs A) {
         const unc_dtw_result_t R = A.res[q];
         unc_seg_info_t inf;
         inf.row_first = 0; inf.n_rows = 0; inf.status = UNC_SEG_NONE; inf.pad = 0;
-        // (the room on the device holds every pair, so the kernel's status is UNC_DTW_OK, or UNC_DTW_LEFT_BAND: a path without a start)
-        if (R.status != UNC_DTW_OK || R.path_len == 0 || R.path_len > (uint64_t)J.path_cap) {
+        // (the room on the device holds every pair, so the kernel's status is UNC_DTW_OK, UNC_DTW_REF_END: a whole path too, or
+        // UNC_DTW_LEFT_BAND: a path without a start)
+        if ((R.status != UNC_DTW_OK && R.status != UNC_DTW_REF_END) || R.path_len == 0 || R.path_len > (uint64_t)J.path_cap) {
             UNC_SIM_CHECK(R.path_len <= (uint64_t)J.path_cap);
             if (lane == 0) A.info[q] = inf;
             continue;

@@ -100,6 +100,7 @@ struct AlignRun : AlignCall {
     unc_params_t P;
     // whole_events (with segments or the event tap): the kept events whole, and which became which column
     bool want_seg = false, want_tap = false, raw_mode = false, whole_events = false;
+    bool adaptive = false;                  // UNC_ALIGN_ADAPTIVE: O.band is the adaptive width
     hipStream_t st = nullptr;
     std::vector<AlignQuery> hq;
     uint64_t n_gather = 0, n_cols = 0;
@@ -148,13 +149,15 @@ struct AlignRun : AlignCall {
             return fail(UNC_ERR_ARG, "%s: the accumulator is on device %d, the call on device %d", who, model_acc_device(acc), device);
         memset(&O, 0, sizeof O);
         if (opts) O = *opts;
-        if (O.flags & ~(UNC_ALIGN_DTW_PARAMS | UNC_ALIGN_NO_MASK | UNC_ALIGN_RAW | UNC_ALIGN_TARGET_MODEL))
+        if (O.flags & ~(UNC_ALIGN_DTW_PARAMS | UNC_ALIGN_NO_MASK | UNC_ALIGN_RAW | UNC_ALIGN_TARGET_MODEL | UNC_ALIGN_ADAPTIVE))
             return fail(UNC_ERR_ARG, "%s: unknown flags %#x", who, O.flags);
         prm = {UNC_DTW_NONE, UNC_DTW_R94D, 1.0f, 1.0f, 1.0f};        // dtw_test.cpp:76-78,162
         if (O.flags & UNC_ALIGN_DTW_PARAMS) prm = O.dtw;
         if (prm.subseq > UNC_DTW_COL) return fail(UNC_ERR_ARG, "%s: unknown subseq %u", who, prm.subseq);
         if (prm.cost > UNC_DTW_R94D) return fail(UNC_ERR_ARG, "%s: unknown cost %u", who, prm.cost);
         if (O.band && prm.subseq != UNC_DTW_NONE) return fail(UNC_ERR_ARG, "%s: the band is global only (subseq %u)", who, prm.subseq);
+        adaptive = (O.flags & UNC_ALIGN_ADAPTIVE) != 0;
+        if (adaptive && !dtw_adapt_band_ok(O.band)) return fail(UNC_ERR_ARG, "%s: an adaptive band of %u (64, 128 or 256)", who, O.band);
         if (params) P = *params;
         else unc_params_default(&P);
         if (P.window_length1 != UNC_WINDOW1 || P.window_length2 != UNC_WINDOW2)
@@ -342,7 +345,7 @@ struct AlignRun : AlignCall {
     // the DTW's rounds (with segments: k_align_segments on each), their times, and the results of the queries that were in one
     int run_dtw() {
         if (int rc = dtw_run_device(device, n_queries, d_levels.p, d_kmers, jobs.data(), skip.data(), &prm, O.band, workspace_bytes, dres.data(),
-                                    path, path_off, st, want_seg ? &hook : nullptr, model))
+                                    path, path_off, st, want_seg ? &hook : nullptr, model, adaptive))
             return rc;
         (void)unc_dtw_last_timing(&g_align_ms[3], nullptr, nullptr);
         const size_t per_round = hook.per_round();
@@ -382,7 +385,7 @@ struct AlignRun : AlignCall {
                 const uint32_t s = results[q].status;
                 unc_seg_info_t &inf = info[q];
                 // (a query that was in no round, or whose path has no start, has no rows: its record on the device may never have been written)
-                if (skip[q] || (s != UNC_DTW_OK && s != UNC_DTW_PATH_TRUNCATED)) { inf.row_first = 0; inf.n_rows = 0; inf.status = UNC_SEG_NONE; inf.pad = 0; }
+                if (skip[q] || (s != UNC_DTW_OK && s != UNC_DTW_PATH_TRUNCATED && s != UNC_DTW_REF_END)) { inf.row_first = 0; inf.n_rows = 0; inf.status = UNC_SEG_NONE; inf.pad = 0; }
                 if (!caller_seg && inf.status == UNC_SEG_TRUNCATED) inf.status = UNC_SEG_OK;       // (no records were asked for: none is missing)
                 // (with an accumulator or a pile-up the room on the device is not the caller's: the status goes by the caller's)
                 if (caller_seg && inf.status == UNC_SEG_OK && inf.n_rows > segs->seg_off[q + 1] - segs->seg_off[q]) inf.status = UNC_SEG_TRUNCATED;

@@ -71,12 +71,15 @@ extern "C" int unc_dtw_last_timing(float *ms_kernel, uint32_t *rounds, uint64_t 
 // The queue, the rounds and the launches over columns and k-mers that lie in device memory already (dtw_dev.h).
 int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
                         const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                        const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook, const unc_model *model) {
+                        const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook, const unc_model *model, bool adaptive) {
     g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
     std::vector<uint64_t> cells(n), words(n);
     for (uint32_t a = 0; a < n; ++a) {
         const uint32_t rows = jobs[a].rows, cols = jobs[a].cols;
-        if (band) {     // the banded layout: a wavefront's steps and the back-pointers of the strips' windows
+        if (adaptive) {     // a wavefront's chain is the anti-diagonals
+            cells[a] = dtw_adapt_diags(rows, cols);
+            words[a] = dtw_adapt_words(rows, cols, band);
+        } else if (band) {     // the banded layout: a wavefront's steps and the back-pointers of the strips' windows
             const uint32_t W = dtw_band_eff(rows, band);
             cells[a] = dtw_band_steps(rows, cols, W);
             words[a] = dtw_band_crumb_words(rows, cols, W);
@@ -97,7 +100,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
     std::vector<uint32_t> todo;
     for (uint32_t a : order) {
         if (skip && skip[a]) continue;
-        const bool narrow = band && !dtw_band_feasible(jobs[a].rows, jobs[a].cols, band);
+        const bool narrow = band && !adaptive && !dtw_band_feasible(jobs[a].rows, jobs[a].cols, band);
         if (narrow || words[a] * 4 > workspace_bytes) {
             res[a].score = 0; res[a].mean_score = 0; res[a].path_len = 0; res[a].pad = 0;
             res[a].status = narrow ? UNC_DTW_BAND_TOO_NARROW : UNC_DTW_TOO_LARGE;
@@ -133,7 +136,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
             caller_cap.push_back(j.path_cap);
             if (hook) j.path_cap = j.rows + j.cols - 1;          // (both below 2^31)
             w += words[todo[at]];
-            lines += 2 * dtw_line_floats(j.cols);
+            if (!adaptive) lines += 2 * dtw_line_floats(j.cols);
             pairs += j.path_cap;
             rows += j.rows;
             round.push_back(j);
@@ -147,7 +150,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
         HIPCHK(hipMemsetAsync(d_next.p, 0, sizeof(uint32_t), st));
         DtwBatch b{};
         b.events = d_events; b.kmers = d_kmers; b.model = d_model; b.jobs = d_jobs.p; b.n_jobs = nr;
-        b.subseq = prm->subseq; b.band = band; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
+        b.subseq = prm->subseq; b.band = band; b.adaptive = adaptive ? 1u : 0u; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
         b.crumbs = d_crumbs.p; b.lines = d_lines.p; b.path = dev_path ? d_path.p : nullptr; b.res = d_res.p; b.next = d_next.p;
         const uint32_t grid = std::min<uint32_t>(nr, (uint32_t)n_cu * 16u);
         HIPCHK(ev.record(0, st));
@@ -173,7 +176,7 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
             r.mean_score = r.score / (float)r.path_len;          // dtw.hpp:130-132
             // (with a hook the kernel had room for every pair, or was asked for a path the caller did not want: the status it gives
             // without one, k_dtw.hip -- UNC_DTW_LEFT_BAND first, then the caller's room)
-            if (hook && r.status == UNC_DTW_OK && path && r.path_len > caller_cap[k]) r.status = UNC_DTW_PATH_TRUNCATED;
+            if (hook && (r.status == UNC_DTW_OK || r.status == UNC_DTW_REF_END) && path && r.path_len > caller_cap[k]) r.status = UNC_DTW_PATH_TRUNCATED;
             res[j.out] = r;
             if (path) {
                 const uint64_t got = std::min<uint64_t>(r.path_len, caller_cap[k]);
@@ -184,10 +187,11 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
     return UNC_OK;
 }
 
-// unc_dtw_batch (band == 0) and unc_dtw_band_batch (band > 0: its own two rules are checked by the entry point)
+// unc_dtw_batch (band == 0), unc_dtw_band_batch (band > 0) and unc_dtw_adapt_batch (adaptive: band is B): the rules of a band are
+// checked by its entry point
 static int dtw_batch(int device, const unc_model *model, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
                      const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                     const uint64_t *path_off, void *stream) {
+                     const uint64_t *path_off, void *stream, bool adaptive = false) {
     // ---- arguments: everything is checked before the device is touched
     if (!events || !ev_off || !kmers || !km_off || !prm || !res) return fail(UNC_ERR_ARG, "unc_dtw_batch: null argument");
     if (path && !path_off) return fail(UNC_ERR_ARG, "unc_dtw_batch: path without path_off");
@@ -225,7 +229,7 @@ static int dtw_batch(int device, const unc_model *model, uint32_t n, const float
     HIPCHK(d_events.alloc(n_ev)); HIPCHK(d_kmers.alloc(n_km));
     HIPCHK(hipMemcpyAsync(d_events.p, events + ev_off[0], n_ev * sizeof(float), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_kmers.p, kmers + km_off[0], n_km * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    return dtw_run_device(device, n, d_events.p, d_kmers.p, jobs.data(), nullptr, prm, band, workspace_bytes, res, path, path_off, st, nullptr, model);
+    return dtw_run_device(device, n, d_events.p, d_kmers.p, jobs.data(), nullptr, prm, band, workspace_bytes, res, path, path_off, st, nullptr, model, adaptive);
 }
 
 extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
@@ -243,7 +247,16 @@ extern "C" int unc_dtw_band_batch(int device, uint32_t n, const float *events, c
     return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream);
 }
 
-// either of the two above, by `band`, with the costs of a model (null: the template's)
+extern "C" int unc_dtw_adapt_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
+                                   const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes,
+                                   unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) {
+    if (!dtw_adapt_band_ok(band)) return fail(UNC_ERR_ARG, "unc_dtw_adapt_batch: a band of %u (64, 128 or 256)", band);
+    if (prm && prm->subseq != UNC_DTW_NONE && prm->subseq <= UNC_DTW_COL)
+        return fail(UNC_ERR_ARG, "unc_dtw_adapt_batch: the adaptive band has a global start and an open end of its own (subseq %u)", prm->subseq);
+    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream, true);
+}
+
+// either of the first two above, by `band`, with the costs of a model (null: the template's)
 extern "C" int unc_dtw_model_batch(int device, const unc_model_t *model, uint32_t n, const float *events, const uint64_t *ev_off,
                                    const uint16_t *kmers, const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band,
                                    uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) {
