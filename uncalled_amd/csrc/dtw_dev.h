@@ -69,6 +69,40 @@ __host__ __device__ inline uint64_t dtw_adapt_words(uint32_t rows, uint32_t cols
     return dtw_adapt_lo_first(rows, cols, B) + (dtw_adapt_diags(rows, cols) + 63) / 64 * 64;
 }
 
+// ---- the layout in force, said once: which of the three kernels runs and its width.  What the host plans by goes through these
+// members; the kernels call the formulas above directly.
+enum class DtwKind : uint32_t { Full, Band, Adapt };      // k_dtw, k_dtw_band, k_dtw_adapt
+struct DtwLayout {
+    uint32_t width;               // Band: the half-width W; Adapt: the width B; Full: 0.  (First: where k_dtw_band has always read it)
+    DtwKind kind;
+    static DtwLayout full() { return {0, DtwKind::Full}; }
+    static DtwLayout band(uint32_t W) { return {W, DtwKind::Band}; }
+    static DtwLayout adapt(uint32_t B) { return {B, DtwKind::Adapt}; }
+    // steps of one wavefront's dependent chain: what the queue is ordered by
+    uint64_t chain(uint32_t rows, uint32_t cols) const {
+        return kind == DtwKind::Band ? dtw_band_steps(rows, cols, dtw_band_eff(rows, width))
+             : kind == DtwKind::Adapt ? dtw_adapt_diags(rows, cols) : (uint64_t)rows * cols;
+    }
+    // 32-bit words of one alignment's back-pointers (Adapt: and of its lo_d)
+    uint64_t words(uint32_t rows, uint32_t cols) const {
+        return kind == DtwKind::Band ? dtw_band_crumb_words(rows, cols, dtw_band_eff(rows, width))
+             : kind == DtwKind::Adapt ? dtw_adapt_words(rows, cols, width) : dtw_crumb_words(rows, cols);
+    }
+    // floats of one alignment's two lines
+    uint64_t line_floats(uint32_t cols) const { return kind == DtwKind::Adapt ? 0 : 2 * dtw_line_floats(cols); }
+    // false: the alignment gets UNC_DTW_BAND_TOO_NARROW and is not computed
+    bool feasible(uint32_t rows, uint32_t cols) const { return kind != DtwKind::Band || dtw_band_feasible(rows, cols, width); }
+};
+// The rules of a layout that a caller's arguments break (0: none), for the entry points to report in their own order and words.
+// DTW_MODE_WIDTH: a Band of 0, an Adapt not of 64, 128 or 256.  DTW_MODE_SUBSEQ: a band of either sort is global only, so a Band
+// or an Adapt with UNC_DTW_ROW or UNC_DTW_COL (an unknown subseq is the caller's to report, and a width of 0 is DTW_MODE_WIDTH's).
+enum : uint32_t { DTW_MODE_WIDTH = 1, DTW_MODE_SUBSEQ = 2 };
+inline uint32_t dtw_mode_faults(DtwLayout L, uint32_t subseq) {
+    const bool width_ok = L.kind == DtwKind::Full || (L.kind == DtwKind::Band ? L.width != 0 : dtw_adapt_band_ok(L.width));
+    const bool subseq_ok = L.kind == DtwKind::Full || L.width == 0 || subseq == UNC_DTW_NONE || subseq > UNC_DTW_COL;
+    return (width_ok ? 0u : DTW_MODE_WIDTH) | (subseq_ok ? 0u : DTW_MODE_SUBSEQ);
+}
+
 struct DtwJob {
     uint64_t ev_off, km_off;      // first event / k-mer in the batch's arrays
     uint64_t crumb_off;           // first word of the alignment's back-pointers
@@ -83,11 +117,10 @@ struct DtwBatch {
     const float *events;
     const uint16_t *kmers;
     const float *model;           // [3][1024]: mean, 2 * stdv^2, log(sqrt(pi * that)) of the template model
-    const DtwJob *jobs;           // descending cell count (with a band: descending steps)
+    const DtwJob *jobs;           // descending DtwLayout::chain
     uint32_t n_jobs;
-    uint32_t subseq;
-    uint32_t band;                // 0: the full matrix; else the half-width W, subseq is UNC_DTW_NONE, and crumb_off is of the banded layout
-    uint32_t adaptive;            // != 0: band is the adaptive width B (dtw_adapt_band_ok), crumb_off is of the adaptive layout, no lines
+    uint32_t subseq;              // (with a band of either sort: UNC_DTW_NONE)
+    DtwLayout layout;             // what crumb_off and line_off are of; launch_dtw picks the kernel by it
     float dw, hw, vw;
     uint32_t *crumbs;
     float *lines;
@@ -98,28 +131,37 @@ struct DtwBatch {
 
 void launch_dtw(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st);
 
-// unc_dtw.cpp: what unc_dtw_batch does once its columns and k-mers are in device memory -- the queue in descending cell count, the
-// rounds that fit the workspace, the launches and the copies of results and paths to the host.  jobs[a] names alignment a's first
-// column and first k-mer in d_events / d_kmers, its rows and columns, path_cap and out = a (the three offsets of a round are filled
-// here).  skip (may be null): alignments with skip[a] != 0 are left out and res[a] is not written.  The arguments are the caller's
-// to check.  band: 0 = the full matrix, else the half-width: back-pointers, rounds, UNC_DTW_TOO_LARGE and the queue (descending steps)
-// go by the banded layout, and an alignment whose band is too narrow gets UNC_DTW_BAND_TOO_NARROW.  unc_align.cpp hands over the levels its own kernels have written: they never visit the host.
-// hook (may be null): every alignment's path is then kept whole on the device (rows + cols - 1 pairs of room, whatever the caller's),
-// and after each round's kernel, before anything is copied out and the next round reuses the buffers, the hook is handed the round.
-// What the caller gets is as without it: path_cap pairs at most, and UNC_DTW_PATH_TRUNCATED by path_cap.
-// model (may be null: the template's, kept per device for the life of the process): whose tables the costs are read from.
-// adaptive: band is the adaptive width B (the caller has checked dtw_adapt_band_ok and a global alignment): the adaptive layout,
-// the queue in descending anti-diagonals, no UNC_DTW_BAND_TOO_NARROW.
+// hook: every alignment's path is kept whole on the device (rows + cols - 1 pairs of room, whatever the caller's), and after each
+// round's kernel, before anything is copied out and the next round reuses the buffers, the hook is handed the round.  What the caller
+// gets is as without it: path_cap pairs at most, and UNC_DTW_PATH_TRUNCATED by path_cap.
 struct DtwRoundHook {
     virtual ~DtwRoundHook() = default;
     // d_jobs: the round's jobs as the kernel saw them (path_cap = rows + cols - 1); n_rows: the sum of their rows; d_res is indexed
     // by DtwJob::out
     virtual int round(const DtwJob *d_jobs, uint32_t n_jobs, uint64_t n_rows, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) = 0;
 };
-int dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
-                   const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                   const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook = nullptr, const unc_model *model = nullptr,
-                   bool adaptive = false);
+
+// unc_dtw.cpp: what unc_dtw_batch does once its columns and k-mers are in device memory -- the queue in descending chain, the rounds
+// that fit the workspace, the launches and the copies of results and paths to the host.  The fields are the caller's to check
+// (dtw_mode_faults among the checks).  unc_align.cpp hands over the levels its own kernels have written: they never visit the host.
+struct DtwCall {
+    int device;                     // where everything below lies
+    hipStream_t st;                 // every copy and launch is queued here
+    uint32_t n;                     // alignments
+    const float *d_events;          // the batch's columns, on the device
+    const uint16_t *d_kmers;        // the batch's k-mers, on the device
+    const DtwJob *jobs;             // [n], host: first column and k-mer, rows, cols, path_cap, out = a (a round's three offsets are filled here)
+    const uint8_t *skip;            // null, or [n]: skip[a] != 0 leaves alignment a out and res[a] unwritten
+    const unc_dtw_params_t *prm;    // subseq, cost and the three weights
+    DtwLayout layout;               // which kernel, and what the queue, the rounds and UNC_DTW_TOO_LARGE go by
+    uint64_t workspace_bytes;       // back-pointers a round may hold; 0: half of the free device memory
+    unc_dtw_result_t *res;          // [n], host
+    uint32_t *path;                 // null (no paths wanted), or the caller's pairs on the host
+    const uint64_t *path_off;       // (with path) [n + 1]: alignment a's room is [path_off[a], path_off[a + 1])
+    DtwRoundHook *hook;             // null, or handed every round (above)
+    const unc_model *model;         // whose tables the costs are read from; null: the template's, kept per device for the life of the process
+};
+int dtw_run_device(const DtwCall &c);
 // the template model's 3 x 1024 floats on `device` (uploaded once per device) and on the host; dtw_model_default: with its mean and
 // deviation over all k-mers (unc_model.h)
 int dtw_model_device(int device, const float **out);

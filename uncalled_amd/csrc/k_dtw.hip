@@ -49,6 +49,40 @@ __device__ __forceinline__ void wave_first_min(float &v, uint32_t &idx) {
     }
 }
 
+// ---- the leaves that the three sweeps share (dtw_one and dtw_band_one here, dtw_adapt_one of k_dtw_adapt.hip): no loop of their own,
+// scalars in and scalars out -- an element of a per-lane array is handed over by value (pick4, k_dtw_adapt.hip).
+
+// one k-mer's row of the model's three tables
+struct ModelRow { float mu, v2, ln; };
+__device__ __forceinline__ ModelRow model_row(const float *model, uint32_t k) { return {model[k], model[1024 + k], model[2048 + k]}; }
+
+// a cell from its three predecessors, dtw.hpp:57-71: the three sums, and the reference's tie order D <= H, D <= V; H <= V
+struct DtwCell { float m; uint32_t mv; };
+__device__ __forceinline__ DtwCell dtw_cell(float dp, float hp, float vp, float cost, float dw, float hw, float vw) {
+    const float ds = __fadd_rn(dp, __fmul_rn(dw, cost));
+    const float hs = __fadd_rn(hp, __fmul_rn(hw, cost));
+    const float vs = __fadd_rn(vp, __fmul_rn(vw, cost));
+    if (ds <= hs && ds <= vs) return {ds, MOVE_D};
+    if (hs <= vs) return {hs, MOVE_H};
+    return {vs, MOVE_V};
+}
+
+// (Two pieces stay in the three tracebacks, because as helpers they changed the code around them and cost some kernel time: the step
+// from a move to the next (i, j), and the staging of the path 64 pairs at a time -- DESIGN.md, "Shared leaves")
+
+// the result, by lane 0.  mean_score: the host divides (score / (float)path_len, dtw.hpp:130-132)
+__device__ __forceinline__ void dtw_write_result(const DtwBatch &B, const DtwJob &J, float score, uint64_t path_len, uint32_t status) {
+    if (lane_id() == 0) B.res[J.out] = unc_dtw_result_t{score, 0.0f, path_len, status, 0};
+}
+
+// the queue: the index of the wavefront's next job; B.n_jobs or more: none is left.  (The index, not the job: a job filled in through
+// a reference cost the full-matrix kernel 10 VGPRs and two waves per SIMD)
+__device__ __forceinline__ uint32_t dtw_take_job(const DtwBatch &B) {
+    uint32_t q = 0;
+    if (lane_id() == 0) q = atomicAdd(B.next, 1u);
+    return uniform32(q);
+}
+
 template <int COST> __device__ void dtw_one(const DtwBatch &B, const DtwJob &J) {
     const uint32_t lane = (uint32_t)lane_id();
     const uint32_t rows = uniform32(J.rows), cols = uniform32(J.cols);
@@ -82,8 +116,8 @@ template <int COST> __device__ void dtw_one(const DtwBatch &B, const DtwJob &J) 
         float *lout = (s & 1u) ? line1 : line0;
         float mu = 0.0f, v2 = 1.0f, ln = 0.0f;
         if (row_ok) {
-            const uint32_t k = km[i];
-            mu = B.model[k]; v2 = B.model[1024 + k]; ln = B.model[2048 + k];
+            const ModelRow r = model_row(B.model, km[i]);
+            mu = r.mu; v2 = r.v2; ln = r.ln;
         }
         float cur = hinit;                                  // the lane's last value: H of its next cell
         float prev_up = i == 0 ? 0.0f : dinit;              // the V it took one step ago: D of its next cell
@@ -102,16 +136,8 @@ template <int COST> __device__ void dtw_one(const DtwBatch &B, const DtwJob &J) 
             if (lane == 0) { e_in = e0; up = up0; }
             e = e_in;
             const bool act = row_ok && t >= lane && t - lane < cols;
-            const float c = dtw_cost<COST>(e, mu, v2, ln);
-            const float ds = __fadd_rn(prev_up, __fmul_rn(dw, c));       // dtw.hpp:57-60
-            const float hs = __fadd_rn(cur, __fmul_rn(hw, c));
-            const float vs = __fadd_rn(up, __fmul_rn(vw, c));
-            float m;
-            uint32_t mv;
-            if (ds <= hs && ds <= vs) { m = ds; mv = MOVE_D; }           // :62-71
-            else if (hs <= vs) { m = hs; mv = MOVE_H; }
-            else { m = vs; mv = MOVE_V; }
-            if (act) { prev_up = up; cur = m; cw |= mv << (2u * (t & 15u)); }
+            const DtwCell c = dtw_cell(prev_up, cur, up, dtw_cost<COST>(e, mu, v2, ln), dw, hw, vw);
+            if (act) { prev_up = up; cur = c.m; cw |= c.mv << (2u * (t & 15u)); }
             if ((t & 15u) == 15u || t == n_steps - 1) {
                 UNC_SIM_CHECK((uint64_t)s * n_blocks * 64 + (uint64_t)(t >> 4) * 64 + lane < dtw_crumb_words(rows, cols));
                 cstrip[(uint64_t)(t >> 4) * 64 + lane] = cw;
@@ -179,22 +205,12 @@ template <int COST> __device__ void dtw_one(const DtwBatch &B, const DtwJob &J) 
         else if (j == 0 || mv == MOVE_V) --i;
         else { --i; --j; }
     }
-    if (lane == 0) {
-        unc_dtw_result_t r;
-        r.score = score;
-        r.mean_score = 0.0f;      // the host divides (score / (float)path_len, dtw.hpp:130-132)
-        r.path_len = p;
-        r.status = want_path && p > cap ? UNC_DTW_PATH_TRUNCATED : UNC_DTW_OK;
-        r.pad = 0;
-        B.res[J.out] = r;
-    }
+    dtw_write_result(B, J, score, p, want_path && p > cap ? UNC_DTW_PATH_TRUNCATED : UNC_DTW_OK);
 }
 
 template <int COST> __global__ void __launch_bounds__(64) k_dtw(DtwBatch B) {
     for (;;) {
-        uint32_t q = 0;
-        if (lane_id() == 0) q = atomicAdd(B.next, 1u);
-        q = uniform32(q);
+        const uint32_t q = dtw_take_job(B);
         if (q >= B.n_jobs) return;
         const DtwJob J = B.jobs[q];
         dtw_one<COST>(B, J);
@@ -214,7 +230,7 @@ template <int COST> __global__ void __launch_bounds__(64) k_dtw(DtwBatch B) {
 template <int COST> __device__ void dtw_band_one(const DtwBatch &B, const DtwJob &J) {
     const uint32_t lane = (uint32_t)lane_id();
     const uint32_t rows = uniform32(J.rows), cols = uniform32(J.cols);
-    const uint32_t W = dtw_band_eff(rows, uniform32(B.band));
+    const uint32_t W = dtw_band_eff(rows, uniform32(B.layout.width));
     const float dw = B.dw, hw = B.hw, vw = B.vw;
     const float *ev = B.events + J.ev_off;
     const uint16_t *km = B.kmers + J.km_off;
@@ -234,8 +250,8 @@ template <int COST> __device__ void dtw_band_one(const DtwBatch &B, const DtwJob
         float mu = 0.0f, v2 = 1.0f, ln = 0.0f;
         uint32_t lo = 1, hi = 0;
         if (row_ok) {
-            const uint32_t k = km[i];
-            mu = B.model[k]; v2 = B.model[1024 + k]; ln = B.model[2048 + k];
+            const ModelRow r = model_row(B.model, km[i]);
+            mu = r.mu; v2 = r.v2; ln = r.ln;
             lo = dtw_band_lo(i, rows, cols, W); hi = dtw_band_hi(i, rows, cols, W);
         }
         const uint32_t wlo = lane_value(lo, 0), llo = lane_value(lo, last_lane), whi = lane_value(hi, last_lane);
@@ -265,18 +281,10 @@ template <int COST> __device__ void dtw_band_one(const DtwBatch &B, const DtwJob
             e = e_in;
             const uint32_t j = wlo + t - lane;          // (wraps below the window: then above hi)
             const bool act = t >= lane && j >= lo && j <= hi;
-            const float c = dtw_cost<COST>(e, mu, v2, ln);
-            const float ds = __fadd_rn(prev_up, __fmul_rn(dw, c));
-            const float hs = __fadd_rn(cur, __fmul_rn(hw, c));
-            const float vs = __fadd_rn(up, __fmul_rn(vw, c));
-            float m;
-            uint32_t mv;
-            if (ds <= hs && ds <= vs) { m = ds; mv = MOVE_D; }
-            else if (hs <= vs) { m = hs; mv = MOVE_H; }
-            else { m = vs; mv = MOVE_V; }
+            const DtwCell c = dtw_cell(prev_up, cur, up, dtw_cost<COST>(e, mu, v2, ln), dw, hw, vw);
             prev_up = up;
-            cur = act ? m : DTW_MAX_COST;
-            if (act) cw |= mv << (2u * (t & 15u));
+            cur = act ? c.m : DTW_MAX_COST;
+            if (act) cw |= c.mv << (2u * (t & 15u));
             if ((t & 15u) == 15u || t == n_steps - 1) {
                 UNC_SIM_CHECK((uint64_t)s * n_blocks * 64 + (uint64_t)(t >> 4) * 64 + lane < dtw_band_crumb_words(rows, cols, W));
                 cstrip[(uint64_t)(t >> 4) * 64 + lane] = cw;
@@ -338,22 +346,12 @@ template <int COST> __device__ void dtw_band_one(const DtwBatch &B, const DtwJob
         const uint64_t at = (p & ~(uint64_t)63) + lane;
         if (want_path && lane < (uint32_t)(p & 63u) && at < cap) path[at] = make_uint2(pj, pi);
     }
-    if (lane == 0) {
-        unc_dtw_result_t r;
-        r.score = score;
-        r.mean_score = 0.0f;
-        r.path_len = p;
-        r.status = left ? UNC_DTW_LEFT_BAND : want_path && p > cap ? UNC_DTW_PATH_TRUNCATED : UNC_DTW_OK;
-        r.pad = 0;
-        B.res[J.out] = r;
-    }
+    dtw_write_result(B, J, score, p, left ? UNC_DTW_LEFT_BAND : want_path && p > cap ? UNC_DTW_PATH_TRUNCATED : UNC_DTW_OK);
 }
 
 template <int COST> __global__ void __launch_bounds__(64) k_dtw_band(DtwBatch B) {
     for (;;) {
-        uint32_t q = 0;
-        if (lane_id() == 0) q = atomicAdd(B.next, 1u);
-        q = uniform32(q);
+        const uint32_t q = dtw_take_job(B);
         if (q >= B.n_jobs) return;
         const DtwJob J = B.jobs[q];
         dtw_band_one<COST>(B, J);
@@ -364,20 +362,23 @@ template <int COST> __global__ void __launch_bounds__(64) k_dtw_band(DtwBatch B)
 }  // namespace
 }  // namespace unc
 
-// k_dtw_adapt, the band that follows the path, is compiled as part of this translation unit: it shares the cost and the tie rule above
+// k_dtw_adapt, the band that follows the path, is compiled as part of this translation unit: it shares the cost and the leaves above
 #include "k_dtw_adapt.hip"
 
 namespace unc {
 
 void launch_dtw(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st) {
-    if (b.adaptive) { launch_dtw_adapt(b, cost, grid, st); return; }
-    if (b.band) {
+    switch (b.layout.kind) {
+    case DtwKind::Adapt: launch_dtw_adapt(b, cost, grid, st); break;
+    case DtwKind::Band:
         if (cost == UNC_DTW_R94D) hipLaunchKernelGGL(k_dtw_band<(int)UNC_DTW_R94D>, dim3(grid), dim3(64), 0, st, b);
         else hipLaunchKernelGGL(k_dtw_band<(int)UNC_DTW_R94P>, dim3(grid), dim3(64), 0, st, b);
-        return;
+        break;
+    case DtwKind::Full:
+        if (cost == UNC_DTW_R94D) hipLaunchKernelGGL(k_dtw<(int)UNC_DTW_R94D>, dim3(grid), dim3(64), 0, st, b);
+        else hipLaunchKernelGGL(k_dtw<(int)UNC_DTW_R94P>, dim3(grid), dim3(64), 0, st, b);
+        break;
     }
-    if (cost == UNC_DTW_R94D) hipLaunchKernelGGL(k_dtw<(int)UNC_DTW_R94D>, dim3(grid), dim3(64), 0, st, b);
-    else hipLaunchKernelGGL(k_dtw<(int)UNC_DTW_R94P>, dim3(grid), dim3(64), 0, st, b);
 }
 
 }  // namespace unc

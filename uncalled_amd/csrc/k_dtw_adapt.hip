@@ -1,5 +1,6 @@
 // k_dtw_adapt: DTW within a band of B rows that follows the path, with an open end (unc_dtw_adapt_batch, include/uncalled_hip.h).
-// Compiled as part of k_dtw.hip's translation unit: the cost, the tie rule and the move codes are the ones above.
+// Compiled as part of k_dtw.hip's translation unit: the cost, the cell with its tie rule, the model's row, the result and the
+// queue are the leaves at that file's top.
 //
 // One wavefront per alignment, swept by anti-diagonals d = i + j.  On d the band holds the rows [lo_d, lo_d + B); after d it moves one
 // row down or stays (the next anti-diagonal then lies one column to the right), by the scores of its two end cells.  The B cells of an
@@ -65,8 +66,8 @@ template <int COST, int N> __device__ void dtw_adapt_one(const DtwBatch &B, cons
         cur[c] = DTW_MAX_COST; p2[c] = DTW_MAX_COST; e[c] = 0.0f; cw[c] = 0;
         mu[c] = 0.0f; v2[c] = 1.0f; ln[c] = 0.0f;
         if (s < BW / 2 && s < rows) {
-            const uint32_t k = km[s];
-            mu[c] = B.model[k]; v2[c] = B.model[1024 + k]; ln[c] = B.model[2048 + k];
+            const ModelRow r = model_row(B.model, km[s]);
+            mu[c] = r.mu; v2[c] = r.v2; ln[c] = r.ln;
         }
     }
     float rot_prev = lane == 0 ? 0.0f : DTW_MAX_COST;       // D of (0, 0): the start
@@ -102,8 +103,8 @@ template <int COST, int N> __device__ void dtw_adapt_one(const DtwBatch &B, cons
                 const uint32_t r = (nb & ~63u) + lane;
                 mu_reg = 0.0f; v2_reg = 1.0f; ln_reg = 0.0f;
                 if (r < rows) {
-                    const uint32_t k = km[r];
-                    mu_reg = B.model[k]; v2_reg = B.model[1024 + k]; ln_reg = B.model[2048 + k];
+                    const ModelRow m = model_row(B.model, km[r]);
+                    mu_reg = m.mu; v2_reg = m.v2; ln_reg = m.ln;
                 }
                 km_held = nb >> 6;
             }
@@ -131,18 +132,10 @@ template <int COST, int N> __device__ void dtw_adapt_one(const DtwBatch &B, cons
             const float hp = entered[c] ? DTW_MAX_COST : cur[c];                                    // i was in the band of d - 1
             const float vp = i != lo1 ? up[c] : DTW_MAX_COST;                                       // i - 1 was
             const float dp = (uint32_t)(i - 1 - lo2) < BW ? dg[c] : DTW_MAX_COST;                   // i - 1 was in the band of d - 2
-            const float x = dtw_cost<COST>(e[c], mu[c], v2[c], ln[c]);
-            const float ds = __fadd_rn(dp, __fmul_rn(dw, x));
-            const float hs = __fadd_rn(hp, __fmul_rn(hw, x));
-            const float vs = __fadd_rn(vp, __fmul_rn(vw, x));
-            float m;
-            uint32_t mv;
-            if (ds <= hs && ds <= vs) { m = ds; mv = MOVE_D; }
-            else if (hs <= vs) { m = hs; mv = MOVE_H; }
-            else { m = vs; mv = MOVE_V; }
+            const DtwCell x = dtw_cell(dp, hp, vp, dtw_cost<COST>(e[c], mu[c], v2[c], ln[c]), dw, hw, vw);
             p2[c] = cur[c];
-            cur[c] = present ? m : DTW_MAX_COST;
-            if (present) cw[c] |= mv << (2u * (d & 15u));
+            cur[c] = present ? x.m : DTW_MAX_COST;
+            if (present) cw[c] |= x.mv << (2u * (d & 15u));
         }
         if ((d & 15u) == 15u) {
 #pragma unroll
@@ -234,24 +227,15 @@ template <int COST, int N> __device__ void dtw_adapt_one(const DtwBatch &B, cons
         const uint64_t at = (p & ~(uint64_t)63) + lane;
         if (want_path && lane < (uint32_t)(p & 63u) && at < cap) path[at] = make_uint2(pj, pi);
     }
-    if (lane == 0) {
-        unc_dtw_result_t r;
-        r.score = score;
-        r.mean_score = 0.0f;
-        r.path_len = p;
-        r.status = left ? UNC_DTW_LEFT_BAND : want_path && p > cap ? UNC_DTW_PATH_TRUNCATED : ei == rows - 1 ? UNC_DTW_REF_END : UNC_DTW_OK;
-        r.pad = 0;
-        B.res[J.out] = r;
-    }
+    dtw_write_result(B, J, score, p,
+                     left ? UNC_DTW_LEFT_BAND : want_path && p > cap ? UNC_DTW_PATH_TRUNCATED : ei == rows - 1 ? UNC_DTW_REF_END : UNC_DTW_OK);
 }
 
 #undef UNC_PICK
 
 template <int COST, int N> __global__ void __launch_bounds__(64) k_dtw_adapt(DtwBatch B) {
     for (;;) {
-        uint32_t q = 0;
-        if (lane_id() == 0) q = atomicAdd(B.next, 1u);
-        q = uniform32(q);
+        const uint32_t q = dtw_take_job(B);
         if (q >= B.n_jobs) return;
         const DtwJob J = B.jobs[q];
         dtw_adapt_one<COST, N>(B, J);
@@ -264,10 +248,10 @@ template <int N> void launch_dtw_adapt_n(const DtwBatch &b, uint32_t cost, uint3
     else hipLaunchKernelGGL((k_dtw_adapt<(int)UNC_DTW_R94P, N>), dim3(grid), dim3(64), 0, st, b);
 }
 
-// b.band: 64, 128 or 256 (dtw_adapt_band_ok, checked by the host)
+// b.layout.width: 64, 128 or 256 (dtw_adapt_band_ok, checked by the host)
 void launch_dtw_adapt(const DtwBatch &b, uint32_t cost, uint32_t grid, hipStream_t st) {
-    if (b.band == 64) launch_dtw_adapt_n<1>(b, cost, grid, st);
-    else if (b.band == 128) launch_dtw_adapt_n<2>(b, cost, grid, st);
+    if (b.layout.width == 64) launch_dtw_adapt_n<1>(b, cost, grid, st);
+    else if (b.layout.width == 128) launch_dtw_adapt_n<2>(b, cost, grid, st);
     else launch_dtw_adapt_n<4>(b, cost, grid, st);
 }
 

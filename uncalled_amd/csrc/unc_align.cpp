@@ -100,7 +100,7 @@ struct AlignRun : AlignCall {
     unc_params_t P;
     // whole_events (with segments or the event tap): the kept events whole, and which became which column
     bool want_seg = false, want_tap = false, raw_mode = false, whole_events = false;
-    bool adaptive = false;                  // UNC_ALIGN_ADAPTIVE: O.band is the adaptive width
+    DtwLayout layout{};                     // the DTW stage's: O.band with UNC_ALIGN_ADAPTIVE is the adaptive width, without it the half-width
     hipStream_t st = nullptr;
     std::vector<AlignQuery> hq;
     uint64_t n_gather = 0, n_cols = 0;
@@ -155,9 +155,10 @@ struct AlignRun : AlignCall {
         if (O.flags & UNC_ALIGN_DTW_PARAMS) prm = O.dtw;
         if (prm.subseq > UNC_DTW_COL) return fail(UNC_ERR_ARG, "%s: unknown subseq %u", who, prm.subseq);
         if (prm.cost > UNC_DTW_R94D) return fail(UNC_ERR_ARG, "%s: unknown cost %u", who, prm.cost);
-        if (O.band && prm.subseq != UNC_DTW_NONE) return fail(UNC_ERR_ARG, "%s: the band is global only (subseq %u)", who, prm.subseq);
-        adaptive = (O.flags & UNC_ALIGN_ADAPTIVE) != 0;
-        if (adaptive && !dtw_adapt_band_ok(O.band)) return fail(UNC_ERR_ARG, "%s: an adaptive band of %u (64, 128 or 256)", who, O.band);
+        layout = (O.flags & UNC_ALIGN_ADAPTIVE) ? DtwLayout::adapt(O.band) : O.band ? DtwLayout::band(O.band) : DtwLayout::full();
+        const uint32_t faults = dtw_mode_faults(layout, prm.subseq);
+        if (faults & DTW_MODE_SUBSEQ) return fail(UNC_ERR_ARG, "%s: the band is global only (subseq %u)", who, prm.subseq);
+        if (faults & DTW_MODE_WIDTH) return fail(UNC_ERR_ARG, "%s: an adaptive band of %u (64, 128 or 256)", who, O.band);
         if (params) P = *params;
         else unc_params_default(&P);
         if (P.window_length1 != UNC_WINDOW1 || P.window_length2 != UNC_WINDOW2)
@@ -344,9 +345,11 @@ struct AlignRun : AlignCall {
 
     // the DTW's rounds (with segments: k_align_segments on each), their times, and the results of the queries that were in one
     int run_dtw() {
-        if (int rc = dtw_run_device(device, n_queries, d_levels.p, d_kmers, jobs.data(), skip.data(), &prm, O.band, workspace_bytes, dres.data(),
-                                    path, path_off, st, want_seg ? &hook : nullptr, model, adaptive))
-            return rc;
+        DtwCall c{};
+        c.device = device; c.st = st; c.n = n_queries; c.d_events = d_levels.p; c.d_kmers = d_kmers; c.jobs = jobs.data(); c.skip = skip.data();
+        c.prm = &prm; c.layout = layout; c.workspace_bytes = workspace_bytes; c.res = dres.data(); c.path = path; c.path_off = path_off;
+        c.hook = want_seg ? &hook : nullptr; c.model = model;
+        if (int rc = dtw_run_device(c)) return rc;
         (void)unc_dtw_last_timing(&g_align_ms[3], nullptr, nullptr);
         const size_t per_round = hook.per_round();
         float acc_ms = 0, pile_ms = 0;

@@ -1,6 +1,6 @@
-// Host side of the DTW entry points of include/uncalled_hip.h: argument checks, the queue of alignments in descending cell count
-// (with a band: descending steps), the split of a batch into rounds that fit the workspace, and BwaIndex::get_kmers on the packed
-// reference (host only).
+// Host side of the DTW entry points of include/uncalled_hip.h: argument checks, the queue of alignments in descending chain (cells,
+// or the steps of a band), the split of a batch into rounds that fit the workspace, and BwaIndex::get_kmers on the packed reference
+// (host only).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -68,80 +68,89 @@ extern "C" int unc_dtw_last_timing(float *ms_kernel, uint32_t *rounds, uint64_t 
     return UNC_OK;
 }
 
-// The queue, the rounds and the launches over columns and k-mers that lie in device memory already (dtw_dev.h).
-int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uint16_t *d_kmers, const DtwJob *jobs, const uint8_t *skip,
-                        const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                        const uint64_t *path_off, hipStream_t st, DtwRoundHook *hook, const unc_model *model, bool adaptive) {
-    g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
-    std::vector<uint64_t> cells(n), words(n);
-    for (uint32_t a = 0; a < n; ++a) {
-        const uint32_t rows = jobs[a].rows, cols = jobs[a].cols;
-        if (adaptive) {     // a wavefront's chain is the anti-diagonals
-            cells[a] = dtw_adapt_diags(rows, cols);
-            words[a] = dtw_adapt_words(rows, cols, band);
-        } else if (band) {     // the banded layout: a wavefront's steps and the back-pointers of the strips' windows
-            const uint32_t W = dtw_band_eff(rows, band);
-            cells[a] = dtw_band_steps(rows, cols, W);
-            words[a] = dtw_band_crumb_words(rows, cols, W);
-        } else {
-            cells[a] = (uint64_t)rows * cols;
-            words[a] = dtw_crumb_words(rows, cols);
-        }
-    }
-    if (workspace_bytes == 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        workspace_bytes = free_b / 2;
-    }
-    // the queue: descending cell count, so that the longest alignments start first and none sits alone at the tail
-    std::vector<uint32_t> order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells[x] > cells[y]; });
+namespace {
+// One call of dtw_run_device (dtw_dev.h): the call's record, and what the steps hand to each other
+struct DtwRun : DtwCall {
+    // plan_queue: the workspace resolved, every alignment's words, the queue and how far the rounds have taken it
+    uint64_t workspace = 0;
+    std::vector<uint64_t> words;
     std::vector<uint32_t> todo;
-    for (uint32_t a : order) {
-        if (skip && skip[a]) continue;
-        const bool narrow = band && !adaptive && !dtw_band_feasible(jobs[a].rows, jobs[a].cols, band);
-        if (narrow || words[a] * 4 > workspace_bytes) {
-            res[a].score = 0; res[a].mean_score = 0; res[a].path_len = 0; res[a].pad = 0;
-            res[a].status = narrow ? UNC_DTW_BAND_TOO_NARROW : UNC_DTW_TOO_LARGE;
-        } else todo.push_back(a);
-    }
-    if (todo.empty()) return UNC_OK;
-
+    size_t at = 0;
+    // set_up_device (d_crumbs, d_lines, d_jobs and d_path grow with the rounds)
     const float *d_model = nullptr;
-    if (int rc = model ? model_device(model, device, &d_model) : dtw_model_device(device, &d_model)) return rc;
-    DevBuf<float> d_lines;
-    DevBuf<uint32_t> d_crumbs, d_path, d_next;
-    DevBuf<DtwJob> d_jobs;
-    DevBuf<unc_dtw_result_t> d_res;
-    HIPCHK(d_res.alloc(n)); HIPCHK(d_next.alloc(1));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
-    DevEvents ev;       // (timing only) around a round's kernel
-    HIPCHK(ev.create(2));
-
+    int n_cu = 1;
+    DevBuf<float> d_lines; DevBuf<uint32_t> d_crumbs, d_path, d_next; DevBuf<DtwJob> d_jobs; DevBuf<unc_dtw_result_t> d_res;
+    DevEvents ev;                           // (timing only) around a round's kernel
+    // next_round: the round's jobs with their offsets, and its totals in words, floats, pairs and rows
     std::vector<DtwJob> round;
     std::vector<uint32_t> caller_cap;       // (with a hook: what the caller's room holds of each of the round's paths)
+    uint64_t w = 0, lines = 0, pairs = 0, rows = 0;
+    // read_back_round
     std::vector<uint32_t> h_path;
     std::vector<unc_dtw_result_t> h_res;
-    size_t at = 0;
-    while (at < todo.size()) {
-        // a round: the next alignments of the queue whose back-pointers fit the workspace together
+
+    explicit DtwRun(const DtwCall &c) : DtwCall(c) {}
+
+    // the queue: descending chain, so that the longest alignments start first and none sits alone at the tail.  What is left out
+    // gets its status here
+    int plan_queue() {
+        std::vector<uint64_t> chain(n);
+        words.resize(n);
+        for (uint32_t a = 0; a < n; ++a) {
+            chain[a] = layout.chain(jobs[a].rows, jobs[a].cols);
+            words[a] = layout.words(jobs[a].rows, jobs[a].cols);
+        }
+        workspace = workspace_bytes;
+        if (workspace == 0) {
+            size_t free_b = 0, total_b = 0;
+            HIPCHK(hipMemGetInfo(&free_b, &total_b));
+            workspace = free_b / 2;
+        }
+        std::vector<uint32_t> order(n);
+        std::iota(order.begin(), order.end(), 0u);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return chain[x] > chain[y]; });
+        for (uint32_t a : order) {
+            if (skip && skip[a]) continue;
+            const bool narrow = !layout.feasible(jobs[a].rows, jobs[a].cols);
+            if (narrow || words[a] * 4 > workspace) {
+                res[a].score = 0; res[a].mean_score = 0; res[a].path_len = 0; res[a].pad = 0;
+                res[a].status = narrow ? UNC_DTW_BAND_TOO_NARROW : UNC_DTW_TOO_LARGE;
+            } else todo.push_back(a);
+        }
+        return UNC_OK;
+    }
+
+    // what every round uses: the model's tables, the results, the queue's counter, the events and the CU count
+    int set_up_device() {
+        if (int rc = model ? model_device(model, device, &d_model) : dtw_model_device(device, &d_model)) return rc;
+        HIPCHK(d_res.alloc(n)); HIPCHK(d_next.alloc(1));
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, device));
+        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+        HIPCHK(ev.create(2));
+        return UNC_OK;
+    }
+
+    // a round: the next alignments of the queue whose back-pointers fit the workspace together (one at least)
+    void next_round() {
         round.clear(); caller_cap.clear();
-        uint64_t w = 0, lines = 0, pairs = 0, rows = 0;
-        while (at < todo.size() && (round.empty() || (w + words[todo[at]]) * 4 <= workspace_bytes)) {
+        w = 0; lines = 0; pairs = 0; rows = 0;
+        while (at < todo.size() && (round.empty() || (w + words[todo[at]]) * 4 <= workspace)) {
             DtwJob j = jobs[todo[at]];
             j.crumb_off = w; j.line_off = lines; j.path_off = pairs;
             caller_cap.push_back(j.path_cap);
             if (hook) j.path_cap = j.rows + j.cols - 1;          // (both below 2^31)
             w += words[todo[at]];
-            if (!adaptive) lines += 2 * dtw_line_floats(j.cols);
+            lines += layout.line_floats(j.cols);
             pairs += j.path_cap;
             rows += j.rows;
             round.push_back(j);
             ++at;
         }
+    }
+
+    // the round's buffers, its jobs on the device, the kernel between the two events, and the hook
+    int launch_round() {
         const uint32_t nr = (uint32_t)round.size();
         HIPCHK(d_crumbs.reserve(w)); HIPCHK(d_lines.reserve(lines)); HIPCHK(d_jobs.reserve(nr));
         const bool dev_path = path || hook;
@@ -150,19 +159,21 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
         HIPCHK(hipMemsetAsync(d_next.p, 0, sizeof(uint32_t), st));
         DtwBatch b{};
         b.events = d_events; b.kmers = d_kmers; b.model = d_model; b.jobs = d_jobs.p; b.n_jobs = nr;
-        b.subseq = prm->subseq; b.band = band; b.adaptive = adaptive ? 1u : 0u; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
+        b.subseq = prm->subseq; b.layout = layout; b.dw = prm->dw; b.hw = prm->hw; b.vw = prm->vw;
         b.crumbs = d_crumbs.p; b.lines = d_lines.p; b.path = dev_path ? d_path.p : nullptr; b.res = d_res.p; b.next = d_next.p;
         const uint32_t grid = std::min<uint32_t>(nr, (uint32_t)n_cu * 16u);
         HIPCHK(ev.record(0, st));
         launch_dtw(b, prm->cost, grid, st);
         HIPCHK(hipGetLastError());
         HIPCHK(ev.record(1, st));
-        if (hook)
-            if (int rc = hook->round(d_jobs.p, nr, rows, d_path.p, d_res.p, st)) return rc;
-        h_res.resize(n);
+        return hook ? hook->round(d_jobs.p, nr, rows, d_path.p, d_res.p, st) : UNC_OK;
+    }
+
+    // the round's results and paths on the host, its time, and what the caller gets of each
+    int read_back_round() {
         h_path.resize(path ? 2 * pairs : 0);
         // (the results of this round's alignments lie scattered over d_res: the whole array is small)
-        HIPCHK(hipMemcpyAsync(h_res.data(), d_res.p, (size_t)n * sizeof(unc_dtw_result_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(download(h_res, d_res.p, n, st));
         if (path && pairs) HIPCHK(hipMemcpyAsync(h_path.data(), d_path.p, 2 * pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         float ms = 0;
@@ -183,15 +194,29 @@ int unc::dtw_run_device(int device, uint32_t n, const float *d_events, const uin
                 memcpy(path + 2 * path_off[j.out], h_path.data() + 2 * j.path_off, got * 2 * sizeof(uint32_t));
             }
         }
+        return UNC_OK;
+    }
+};
+}  // namespace
+
+int unc::dtw_run_device(const DtwCall &c) {
+    g_last_ms = 0; g_last_rounds = 0; g_last_crumb_bytes = 0;
+    DtwRun s(c);
+    if (int rc = s.plan_queue()) return rc;
+    if (s.todo.empty()) return UNC_OK;
+    if (int rc = s.set_up_device()) return rc;
+    while (s.at < s.todo.size()) {
+        s.next_round();
+        if (int rc = s.launch_round()) return rc;
+        if (int rc = s.read_back_round()) return rc;
     }
     return UNC_OK;
 }
 
-// unc_dtw_batch (band == 0), unc_dtw_band_batch (band > 0) and unc_dtw_adapt_batch (adaptive: band is B): the rules of a band are
-// checked by its entry point
+// the body of the four entry points below: the rules of a layout (dtw_mode_faults) are reported by its entry point, in its words
 static int dtw_batch(int device, const unc_model *model, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers, const uint64_t *km_off,
-                     const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
-                     const uint64_t *path_off, void *stream, bool adaptive = false) {
+                     const unc_dtw_params_t *prm, DtwLayout layout, uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path,
+                     const uint64_t *path_off, void *stream) {
     // ---- arguments: everything is checked before the device is touched
     if (!events || !ev_off || !kmers || !km_off || !prm || !res) return fail(UNC_ERR_ARG, "unc_dtw_batch: null argument");
     if (path && !path_off) return fail(UNC_ERR_ARG, "unc_dtw_batch: path without path_off");
@@ -229,40 +254,47 @@ static int dtw_batch(int device, const unc_model *model, uint32_t n, const float
     HIPCHK(d_events.alloc(n_ev)); HIPCHK(d_kmers.alloc(n_km));
     HIPCHK(hipMemcpyAsync(d_events.p, events + ev_off[0], n_ev * sizeof(float), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_kmers.p, kmers + km_off[0], n_km * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    return dtw_run_device(device, n, d_events.p, d_kmers.p, jobs.data(), nullptr, prm, band, workspace_bytes, res, path, path_off, st, nullptr, model, adaptive);
+    DtwCall c{};
+    c.device = device; c.st = st; c.n = n; c.d_events = d_events.p; c.d_kmers = d_kmers.p; c.jobs = jobs.data();
+    c.prm = prm; c.layout = layout; c.workspace_bytes = workspace_bytes; c.res = res; c.path = path; c.path_off = path_off; c.model = model;
+    return dtw_run_device(c);
 }
 
 extern "C" int unc_dtw_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
                              const uint64_t *km_off, const unc_dtw_params_t *prm, uint64_t workspace_bytes, unc_dtw_result_t *res,
                              uint32_t *path, const uint64_t *path_off, void *stream) {
-    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, 0, workspace_bytes, res, path, path_off, stream);
+    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, DtwLayout::full(), workspace_bytes, res, path, path_off, stream);
 }
 
 extern "C" int unc_dtw_band_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
                                   const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes,
                                   unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) {
-    if (band == 0) return fail(UNC_ERR_ARG, "unc_dtw_band_batch: a band of 0 (unc_dtw_batch is the full matrix)");
-    if (prm && prm->subseq != UNC_DTW_NONE && prm->subseq <= UNC_DTW_COL)
-        return fail(UNC_ERR_ARG, "unc_dtw_band_batch: the band is global only (subseq %u)", prm->subseq);
-    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream);
+    const DtwLayout layout = DtwLayout::band(band);
+    const uint32_t faults = dtw_mode_faults(layout, prm ? prm->subseq : UNC_DTW_NONE);
+    if (faults & DTW_MODE_WIDTH) return fail(UNC_ERR_ARG, "unc_dtw_band_batch: a band of 0 (unc_dtw_batch is the full matrix)");
+    if (faults & DTW_MODE_SUBSEQ) return fail(UNC_ERR_ARG, "unc_dtw_band_batch: the band is global only (subseq %u)", prm->subseq);
+    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, layout, workspace_bytes, res, path, path_off, stream);
 }
 
 extern "C" int unc_dtw_adapt_batch(int device, uint32_t n, const float *events, const uint64_t *ev_off, const uint16_t *kmers,
                                    const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band, uint64_t workspace_bytes,
                                    unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) {
-    if (!dtw_adapt_band_ok(band)) return fail(UNC_ERR_ARG, "unc_dtw_adapt_batch: a band of %u (64, 128 or 256)", band);
-    if (prm && prm->subseq != UNC_DTW_NONE && prm->subseq <= UNC_DTW_COL)
+    const DtwLayout layout = DtwLayout::adapt(band);
+    const uint32_t faults = dtw_mode_faults(layout, prm ? prm->subseq : UNC_DTW_NONE);
+    if (faults & DTW_MODE_WIDTH) return fail(UNC_ERR_ARG, "unc_dtw_adapt_batch: a band of %u (64, 128 or 256)", band);
+    if (faults & DTW_MODE_SUBSEQ)
         return fail(UNC_ERR_ARG, "unc_dtw_adapt_batch: the adaptive band has a global start and an open end of its own (subseq %u)", prm->subseq);
-    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream, true);
+    return dtw_batch(device, nullptr, n, events, ev_off, kmers, km_off, prm, layout, workspace_bytes, res, path, path_off, stream);
 }
 
 // either of the first two above, by `band`, with the costs of a model (null: the template's)
 extern "C" int unc_dtw_model_batch(int device, const unc_model_t *model, uint32_t n, const float *events, const uint64_t *ev_off,
                                    const uint16_t *kmers, const uint64_t *km_off, const unc_dtw_params_t *prm, uint32_t band,
                                    uint64_t workspace_bytes, unc_dtw_result_t *res, uint32_t *path, const uint64_t *path_off, void *stream) {
-    if (band && prm && prm->subseq != UNC_DTW_NONE && prm->subseq <= UNC_DTW_COL)
+    const DtwLayout layout = band ? DtwLayout::band(band) : DtwLayout::full();
+    if (dtw_mode_faults(layout, prm ? prm->subseq : UNC_DTW_NONE) & DTW_MODE_SUBSEQ)
         return fail(UNC_ERR_ARG, "unc_dtw_model_batch: the band is global only (subseq %u)", prm->subseq);
-    return dtw_batch(device, model, n, events, ev_off, kmers, km_off, prm, band, workspace_bytes, res, path, path_off, stream);
+    return dtw_batch(device, model, n, events, ev_off, kmers, km_off, prm, layout, workspace_bytes, res, path, path_off, stream);
 }
 
 // ------------------------------------------------------------------ BwaIndex::get_kmers
