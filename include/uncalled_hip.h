@@ -434,7 +434,8 @@ int unc_dtw_band_batch(int device, uint32_t n, const float *events, const uint64
  *   traceback   the reference's (dtw.hpp:100-119) from the end cell to (0, 0).  If it is led to a cell that was not computed -- by
  *               non-finite scores, or through a cell all of whose predecessors were absent -- it stops: UNC_DTW_LEFT_BAND, path_len
  *               counts the pairs up to and including the last computed cell, those pairs are written.  If no cell of column C - 1 was
- *               computed (the band ran off the last row first) the status is UNC_DTW_LEFT_BAND with score 0 and path_len 0;
+ *               computed the status is UNC_DTW_LEFT_BAND with score 0 and path_len 0 (for valid inputs this does not occur: the last
+ *               column's row catches up with a band that stays once it holds the last row; tests/test_dtw_adapt_cpu.py sweeps it);
  *   statuses    UNC_DTW_REF_END: the end cell lies in row R - 1; everything is as with UNC_DTW_OK.  Where several apply:
  *               UNC_DTW_LEFT_BAND, then UNC_DTW_PATH_TRUNCATED (the first pair written is the end cell), then UNC_DTW_REF_END.
  * For finite events a cell's value is never below its full-matrix value, hence: if the path of the full-matrix alignment with the

@@ -54,11 +54,13 @@ SHAPES_64 = [(1, 1), (1, 40), (40, 1), (5, 5), (70, 70), (200, 300), (1, 63), (1
 
 
 def case_of_path_len(checker, means, want_len, cost, weights, band=64):
-    """the first of a seeded run of follow cases, 90 k-mers against 128 events and fewer (a path has one pair an event and one more
-    for every V move), whose path, by the checker, has exactly `want_len` pairs"""
+    """the first of a seeded run of follow cases -- 90 k-mers at B = 64, 1.5 B at the wider bands, so that the band has rows to move
+    to -- against `want_len` events and fewer (a path has one pair an event and one more for every V move), whose path, by the
+    checker, has exactly `want_len` pairs"""
+    rows = 90 if band == 64 else band + band // 2
     for cols in range(want_len, want_len - 40, -1):
         for seed in range(10):
-            ev, km = follow_case(np.random.default_rng(1000 + seed), means, 90, cols)
+            ev, km = follow_case(np.random.default_rng(1000 + seed), means, rows, cols)
             if checker.dtw(ev, km, cost, *weights, band)["path_len"] == want_len:
                 return ev, km
     raise AssertionError("no case with a path of %d pairs" % want_len)
@@ -86,18 +88,201 @@ def shape_batches(means, cost, weights, seed=41):
     return out
 
 
+# ------------------------------------------------------------------ 1b. the band's width edges, at every width
+EDGE_COLS = (1, 2, 63, 64, 65, 129)
+
+
+def edge_rows(B):
+    """around B / 2 (the initial fill ends; the band holds the last row from the start), around B (the first move down loads the
+    model's block at B / 2; the band comes to hold the last row after a few moves), and above"""
+    return (B // 2 - 1, B // 2, B // 2 + 1, B - 1, B, B + 1, B + B // 2 + 1)
+
+
+def edge_batches(means, cost, weights, B, seed=64):
+    """two batches of the 7 x 6 = 42 shapes edge_rows(B) x EDGE_COLS: the events follow the first two thirds of the k-mers (the end
+    is open), and all of them (the k-mers run out)"""
+    shapes = [(r, c) for r in edge_rows(B) for c in EDGE_COLS]
+    out = []
+    for name, all_rows in (("two thirds", False), ("all", True)):
+        rng = np.random.default_rng(seed)
+        evs, kms = zip(*[follow_case(rng, means, r, c, used=r if all_rows else None) for r, c in shapes])
+        out.append(batch(f"edges B {B}, events follow {name} of the k-mers, cost {cost} weights {weights}", evs, kms, cost, weights, B))
+    return out
+
+
+def check_edges(checker, means, B, lib=None):
+    """edge_batches at width B under both costs and both weight sets against the checker, and, by the checker alone, what the
+    alignments are there to reach (over the four combinations together: with dw = 2 hw the band of these shapes hardly moves)"""
+    flat = []
+    for cost in (R94P, R94D):
+        for weights in WEIGHT_SETS:
+            for b in edge_batches(means, cost, weights, B):
+                assert len(b["evs"]) == 42 and max(k.size for k in b["kms"]) == B + B // 2 + 1
+                _, _, want = check(checker, b, lib=lib)
+                flat += [(k.size, w) for k, w in zip(b["kms"], want)]
+    assert {w["status"] for _, w in flat} == {OK, REF_END}
+    assert any(w["lo"].max() > 0 for _, w in flat)                                     # a band that left row 0
+    assert any((w["lo"] == -B // 2).all() for _, w in flat)                            # a band that never moved
+    # rows > B: the band does not hold the last row at first and comes to hold it: the clamp switches on in mid-sweep
+    assert any(rows > B and w["lo"][0] + B - 1 < rows - 1 and w["lo"][-1] + B - 1 == rows - 1 for rows, w in flat)
+
+
+def n_done_case(checker, ev, km, B, cost, weights):
+    """-> the checker's result if the sweep ended early (an anti-diagonal without a present cell) and an end cell exists, else None"""
+    w = checker.dtw(ev, km, cost, *weights, B)
+    if w["lo"].size < ev.size + km.size - 1 and w["end_row"] is not None:
+        return w
+    return None
+
+
+def early_end_family(means, B):
+    """3 B k-mers against 140 events and fewer that follow the first 8 to 23 of them, then the first B / 4 and more: the last column
+    passes below the band"""
+    for cols in range(140, 76, -1):
+        for used in (8, 11, 14, 17, 20, 23) + tuple(range(B // 4, B, 4)):
+            yield follow_case(np.random.default_rng(2000 + used), means, 3 * B, cols, used=used)
+
+
+def case_of_n_done(checker, means, B, residue64, cost, weights, end_in_last_block=False):
+    """-> (ev, km, the checker's result) of the first case of early_end_family whose sweep ends early, at n_done < rows + cols - 1
+    anti-diagonals, with n_done % 64 == residue64 and, if asked for, the end cell's anti-diagonal in the last block of 64.  (An early
+    end comes after an ODD number of anti-diagonals -- tests/test_dtw_adapt_cpu.py states why -- so for an even residue this raises.)"""
+    for ev, km in early_end_family(means, B):
+        w = n_done_case(checker, ev, km, B, cost, weights)
+        if w is not None and w["lo"].size % 64 == residue64 and (not end_in_last_block or end_in_last_partial_block(w, ev.size)):
+            return ev, km, w
+    raise AssertionError("no case whose sweep ends early after a number of anti-diagonals that is %d modulo 64" % residue64)
+
+
+def full_sweep_case(means, B, residue64, seed=48):
+    """B / 2 k-mers (the band holds the last row from the start: the sweep runs to its end) against as many events, 65 or more, as
+    make rows + cols - 1 == residue64 modulo 64"""
+    rows = B // 2
+    cols = 65 + (residue64 - rows - 64) % 64
+    assert (rows + cols - 1) % 64 == residue64
+    return follow_case(np.random.default_rng(seed), means, rows, cols)
+
+
+N_DONE_RESIDUES = (0, 1, 15, 16, 17, 63)
+N_DONE_TIE_COLS = (65, 66, 73)
+
+
+def n_done_tie_case(means, B, cols):
+    """all-equal events, weights 0: every move is a tie, lo_d = -B / 2 + d // 2, and with 3 B rows the last column's row d - (cols - 1)
+    passes lo_d + B - 1 at d = B + 2 cols - 3: that many anti-diagonals are computed (63, 1 and 15 modulo 64 for 65, 66, 73 events)"""
+    return np.full(cols, means[77], np.float32), np.full(3 * B, 77, np.uint16), B + 2 * cols - 3
+
+
+def end_in_last_partial_block(w, cols):
+    """the end cell's anti-diagonal lies in the last block of 64 lo_d, and that block is not full"""
+    n_done = w["lo"].size
+    return n_done % 64 != 0 and (w["end_row"] + cols - 1) // 64 == (n_done - 1) // 64
+
+
+def check_early_end(checker, means, B, lib=None):
+    """n_done, the number of anti-diagonals computed, at every residue of N_DONE_RESIDUES modulo 64: the odd ones where the sweep ends
+    early, the even ones (no early end has them) where it runs to its end; both costs; at B > 64 also the deterministic ties"""
+    evs, kms, wants = [], [], []
+    cost, weights = R94D, (1.0, 1.0, 1.0)
+    for res64 in N_DONE_RESIDUES:
+        if res64 % 2:
+            ev, km, w = case_of_n_done(checker, means, B, res64, cost, weights, end_in_last_block=res64 == 63)
+            assert w["lo"].size < ev.size + km.size - 1
+        else:
+            ev, km = full_sweep_case(means, B, res64)
+            w = checker.dtw(ev, km, cost, *weights, B)
+            assert w["lo"].size == ev.size + km.size - 1
+        assert w["lo"].size % 64 == res64 and w["end_row"] is not None and w["status"] in (OK, REF_END)
+        evs.append(ev), kms.append(km), wants.append(w)
+    assert {w["lo"].size % 16 for w in wants} >= {0, 1, 15}
+    early = [(w, e.size) for w, e, k in zip(wants, evs, kms) if w["lo"].size < e.size + k.size - 1]
+    assert len(early) == 4 and any(end_in_last_partial_block(w, cols) for w, cols in early), [(w["lo"].size, w["end_row"], c) for w, c in early]
+    check(checker, batch(f"early end B {B}", evs, kms, cost, weights, B), lib=lib)
+    check(checker, batch(f"early end B {B} r94p", evs, kms, R94P, (2.0, 1.0, 100.0), B), lib=lib)
+    if B > 64:
+        evs, kms, n_dones = zip(*[n_done_tie_case(means, B, c) for c in N_DONE_TIE_COLS])
+        _, _, want = check(checker, batch(f"early end, ties, B {B}", evs, kms, R94P, (0.0, 0.0, 0.0), B), lib=lib)
+        for w, n_done, e, k in zip(want, n_dones, evs, kms):
+            assert w["lo"].size == n_done < e.size + k.size - 1 and w["end_row"] is not None
+            assert np.array_equal(w["lo"], -B // 2 + np.arange(n_done) // 2)
+        assert [n % 64 for n in n_dones] == [63, 1, 15]
+
+
+def check_path_residues(checker, means, B, lib=None):
+    """paths of 63, 64, 65 and 128 pairs, around the flush of 64 pairs, with two and four cells a lane, both costs and weight sets"""
+    for cost in (R94P, R94D):
+        for weights in WEIGHT_SETS:
+            evs, kms = zip(*[case_of_path_len(checker, means, n, cost, weights, B) for n in (63, 64, 65, 128)])
+            assert all(k.size == B + B // 2 for k in kms)
+            _, _, want = check(checker, batch(f"path lengths B {B} cost {cost} weights {weights}", evs, kms, cost, weights, B), lib=lib)
+            assert [w["path_len"] for w in want] == [63, 64, 65, 128]
+
+
+def sweep_without_last_column(checker, means):
+    """every shape of up to 40 x 40 at B = 64 with random events and with all-tie events, then taller shapes at every width with
+    events that follow k-mers far down the stretch (the band runs ahead of the last column) -> the number of alignments for which no
+    cell of the last column was computed, and the number looked at"""
+    rng = np.random.default_rng(49)
+    none = n = 0
+    for rows in range(1, 41):
+        km = rng.integers(0, 1024, rows).astype(np.uint16)
+        for cols in range(1, 41):
+            for ev, cost, weights in ((rng.uniform(60, 130, cols).astype(np.float32), R94D, (1.0, 1.0, 1.0)),
+                                      (np.full(cols, 90, np.float32), R94P, (0.0, 0.0, 0.0))):
+                none += checker.dtw(ev, km, cost, *weights, 64)["end_row"] is None
+                n += 1
+    for B in (64, 128, 256):
+        for rows, cols, skip in ((2 * B, 5, B), (2 * B, 17, B), (3 * B, 40, 2 * B), (3 * B, 33, B), (B + 9, 3, B // 2 + 9)):
+            km = rng.integers(0, 1024, rows).astype(np.uint16)
+            for ev, cost, weights in ((dc.follow(rng, means, km[skip:skip + cols], cols, 0.5), R94D, (1.0, 1.0, 1.0)),
+                                      (np.full(cols, 90, np.float32), R94P, (0.0, 0.0, 0.0))):
+                for tall in (km, np.concatenate([km[:1], km])):
+                    w = checker.dtw(ev, tall, cost, *weights, B)
+                    none += w["end_row"] is None
+                    n += 1
+    return none, n
+
+
 # ------------------------------------------------------------------ 2. events that are no numbers, and ties in every move
-def nonfinite_batch(means, rows=150, cols=140, band=64, cost=R94D, weights=(1.0, 1.0, 1.0), seed=42):
-    """one NaN, one +inf, one -inf event in the middle of an alignment of its own, and one alignment of all-equal events with weights
-    0: every score is 0, every move of the band a tie, so the band goes down on odd anti-diagonals and right on even ones"""
+def nonfinite_batch(means, rows=150, cols=140, band=64, cost=R94D, weights=(1.0, 1.0, 1.0), seed=42, where="middle"):
+    """one NaN, one +inf, one -inf event in an alignment of its own, in the middle (column cols // 2), at column 0 (the first load of
+    events feeds (0, 0)) or at column cols - 1 (no score of the last column compares: the end cell is its last computed cell)"""
     rng = np.random.default_rng(seed)
     base, km = follow_case(rng, means, rows, cols)
+    at = dict(middle=cols // 2, first=0, last=cols - 1)[where]
     evs = []
     for bad in (np.nan, np.inf, -np.inf):
         ev = base.copy()
-        ev[cols // 2] = bad
+        ev[at] = bad
         evs.append(ev)
-    return batch("non-finite events", evs, [km] * 3, cost, weights, band)
+    return batch(f"non-finite events, {where}", evs, [km] * 3, cost, weights, band)
+
+
+NONFINITE_COMBOS = ((R94D, (1.0, 1.0, 1.0)), (R94P, (2.0, 1.0, 100.0)), (R94P, (0.0, 0.0, 0.0)), (R94D, (0.0, 0.0, 0.0)))
+
+
+def check_nonfinite_ends(checker, means, lib=None):
+    """non-finite events at column 0 and at column cols - 1, B = 64 and 128, the cost and weight combinations of the test of the
+    middle column; then all-equal events with weights 1 at B = 256: the last column's ties go to the first smallest"""
+    for B in (64, 128):
+        for cost, weights in NONFINITE_COMBOS:
+            for where in ("first", "last"):
+                b = nonfinite_batch(means, band=B, cost=cost, weights=weights, where=where)
+                _, _, want = check(checker, b, lib=lib)
+                if where == "last":
+                    # NaN in the last column: the end row is that of the column's last computed cell, on anti-diagonal n_done - 1
+                    w, cols = want[0], b["evs"][0].size
+                    assert np.isnan(w["score"]) and w["end_row"] == w["lo"].size - 1 - (cols - 1) >= max(0, int(w["lo"][-1])), (w["end_row"], w["lo"].size)
+                    assert w["path"][0].tolist() == [cols - 1, w["end_row"]] or w["status"] == LEFT_BAND
+    for cost in (R94D, R94P):
+        b = all_equal_batch(means, rows=300, cols=140, band=256)
+        b = batch("all-equal events B 256", b["evs"], b["kms"], cost, (1.0, 1.0, 1.0), 256)
+        _, _, want = check(checker, b, lib=lib)
+        for ev, km, w in zip(b["evs"], b["kms"], want):
+            cells = checker.dtw(ev, km, cost, 1.0, 1.0, 1.0, 256, cells=True)["cells"]
+            last = sorted((i, v) for (i, j), v in cells.items() if j == ev.size - 1)
+            least = min(v for _, v in last)
+            assert sum(v == least for _, v in last) >= 2 and w["end_row"] == next(i for i, v in last if v == least), (w["end_row"], last[:3])
 
 
 def all_equal_batch(means, rows=150, cols=140, band=64):

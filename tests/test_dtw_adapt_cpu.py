@@ -1,13 +1,18 @@
 """CPU: the adaptive-band DTW with an open end below the GPU -- the checker (tests/dtw_adapt_check.c) anchored on tests/dtw_check.c
 and the reference's committed results, then k_dtw_adapt.hip, the planner and the align pipeline under the lanesim emulator (the
 existing Makefile.dtw / Makefile.align builds) against that checker: status, bits of the score, path_len and the whole path.
-tests/test_gpu_dtw_adapt.py repeats the emulator cases on the gfx950 library and adds the sizes only a GPU can hold.  Nothing here
+Section 2b takes the kernel to its width edges at B = 64, 128 and 256 (dtw_adapt_cases.py: rows around B / 2, B and above; sweeps
+that end early, at every residue of the two partial flushes; non-finite events at column 0 and column cols - 1; paths of 63, 64, 65
+and 128 pairs with two and four cells a lane) and states two properties of the sweep by the checker alone; section 4 takes the
+adaptive band through a custom model, the training accumulator, the pile-up, two rounds, the other align options and a path without
+a start (adapt_pipeline_cases.py).  tests/test_gpu_dtw_adapt.py repeats the emulator cases on the gfx950 library and adds the sizes only a GPU can hold.  Nothing here
 opens a GPU."""
 import subprocess
 
 import numpy as np
 import pytest
 
+import adapt_pipeline_cases as apc
 import align_cases as ac
 import dtw_adapt_cases as xc
 import dtw_cases as dc
@@ -168,9 +173,91 @@ def test_interface_under_the_emulator(checker, means, sim_dtw_lib, sim_align_lib
     xc.check_rounds_and_too_large(checker, means, lib=sim_dtw_lib)
 
 
+# ------------------------------------------------------------------ 2b. the band's width edges, two and four cells a lane
+def test_the_sweep_always_computes_a_cell_of_the_last_column(checker, means):
+    """The checker alone.  The last column's row d - (cols - 1) goes down one row an anti-diagonal and the band at most one, until it
+    holds the last row and stays: the row catches up before the sweep ends.  So for valid inputs "no cell of column C - 1 was
+    computed" (UNC_DTW_LEFT_BAND with score 0 and path_len 0) does not occur: every shape up to 40 x 40 at B = 64, and taller ones."""
+    none, n = xc.sweep_without_last_column(checker, means)
+    assert none == 0 and n >= 2 * 40 * 40
+
+
+def test_an_early_end_comes_after_an_odd_number_of_anti_diagonals(checker, means):
+    """The checker alone.  The sweep ends early at the first d whose last-column row lies below the band.  Then d - 1 had that row as
+    its only present cell (i_t == i_b), the move after it was a tie that went right, and ties go right after even d - 1: d, the
+    number of anti-diagonals computed, is odd.  So of n_done modulo 64, the residues 0 and 16 come only from sweeps that run to
+    their end (dtw_adapt_cases.full_sweep_case), and case_of_n_done finds nothing for them."""
+    seen = set()
+    for B in (64, 128, 256):
+        for ev, km in list(xc.early_end_family(means, B))[::7]:
+            for cost, weights in ((xc.R94D, (1.0, 1.0, 1.0)), (xc.R94P, (2.0, 1.0, 100.0))):
+                w = xc.n_done_case(checker, ev, km, B, cost, weights)
+                if w is not None:
+                    assert w["lo"].size % 2 == 1, (B, km.size, ev.size, w["lo"].size)
+                    seen.add(w["lo"].size % 64)
+    assert len(seen) >= 16
+    with pytest.raises(AssertionError, match="no case whose sweep ends early"):
+        xc.case_of_n_done(checker, means, 64, 16, xc.R94D, (1.0, 1.0, 1.0))
+
+
+@pytest.mark.lanesim
+@pytest.mark.parametrize("B", [64, 128, 256])
+def test_band_edges_under_the_emulator(checker, means, sim_dtw_lib, B):
+    xc.check_edges(checker, means, B, lib=sim_dtw_lib)
+
+
+@pytest.mark.lanesim
+@pytest.mark.parametrize("B", [64, 128, 256])
+def test_early_end_of_the_sweep_under_the_emulator(checker, means, sim_dtw_lib, B):
+    xc.check_early_end(checker, means, B, lib=sim_dtw_lib)
+
+
+@pytest.mark.lanesim
+def test_non_finite_events_at_the_first_and_last_column_under_the_emulator(checker, means, sim_dtw_lib):
+    xc.check_nonfinite_ends(checker, means, lib=sim_dtw_lib)
+
+
+@pytest.mark.lanesim
+@pytest.mark.parametrize("B", [128, 256])
+def test_path_length_residues_with_several_cells_a_lane_under_the_emulator(checker, means, sim_dtw_lib, B):
+    xc.check_path_residues(checker, means, B, lib=sim_dtw_lib)
+
+
 # ------------------------------------------------------------------ 3. the align pipeline
 @pytest.mark.lanesim
 def test_align_pipeline_on_the_example_read_under_the_emulator(checker, sim_align_lib):
     import pileup_cases as pc
     res = xc.check_pipeline(ac.Goldens(), pc.Ctx(sim_align_lib, EX_PREFIX), checker)
     assert set(int(s) for s in res["status"]) <= {OK, REF_END}
+
+
+# ------------------------------------------------------------------ 4. the adaptive band through model, training, pile-up and options
+@pytest.fixture(scope="module")
+def pipe(sim_align_lib):
+    return apc.Ctx(sim_align_lib, EX_PREFIX)
+
+
+@pytest.mark.lanesim
+def test_pipeline_with_a_custom_model_under_the_emulator(pipe):
+    apc.check_custom_model(pipe)
+
+
+@pytest.mark.lanesim
+@pytest.mark.parametrize("keep_shared", [False, True])
+def test_training_with_an_open_end_under_the_emulator(pipe, keep_shared):
+    apc.check_training(pipe, keep_shared)
+
+
+@pytest.mark.lanesim
+def test_pipeline_rounds_through_the_hook_under_the_emulator(pipe):
+    apc.check_rounds(pipe)
+
+
+@pytest.mark.lanesim
+def test_pipeline_options_with_the_adaptive_band_under_the_emulator(pipe):
+    apc.check_options(pipe)
+
+
+@pytest.mark.lanesim
+def test_a_path_without_a_start_in_the_pipeline_under_the_emulator(pipe):
+    apc.check_left_band(pipe)

@@ -1,13 +1,18 @@
 """GPU: the adaptive-band DTW with an open end on the gfx950 library against the checker (tests/dtw_adapt_check.c, anchored by
-tests/test_dtw_adapt_cpu.py): the emulator file's cases, then what only a GPU holds -- more alignments than the launch has
-wavefronts, anti-diagonal indices past 2^16 with linear memory, two threads, the host module, the command line.  Everything runs in
-this one process; the command-line test starts one child and waits for it."""
+tests/test_dtw_adapt_cpu.py): the emulator file's cases -- the shapes, the band's width edges at B = 64, 128 and 256 (rows around
+B / 2, B and above; sweeps that end early at every residue of the flushes; non-finite events at the first and the last column; path
+lengths around 64 with two and four cells a lane), the adaptive band through a custom model, the training accumulator, the pile-up,
+the rounds, the other options and a path without a start (tests/adapt_pipeline_cases.py) -- then what only a GPU holds: more
+alignments than the launch has wavefronts (small ones, and the edge shapes whose bands moved), anti-diagonal indices past 2^16 with
+linear memory, two threads, the host module, the command line.  Everything runs in this one process; each of the two command-line
+tests (`dtw --adaptive`, `train --adaptive`) starts one child and waits for it."""
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import adapt_pipeline_cases as apc
 import align_cases as ac
 import dtw_adapt_cases as xc
 import dtw_cases as dc
@@ -64,6 +69,25 @@ def test_align_pipeline_on_the_example_read(hip_lib, checker):
     xc.check_pipeline(ac.Goldens(), pc.Ctx(hip_lib, EX_PREFIX), checker)
 
 
+@pytest.mark.parametrize("B", [64, 128, 256])
+def test_band_edges(hip_lib, checker, means, B):
+    xc.check_edges(checker, means, B)
+
+
+@pytest.mark.parametrize("B", [64, 128, 256])
+def test_early_end_of_the_sweep(hip_lib, checker, means, B):
+    xc.check_early_end(checker, means, B)
+
+
+def test_non_finite_events_at_the_first_and_last_column(hip_lib, checker, means):
+    xc.check_nonfinite_ends(checker, means)
+
+
+@pytest.mark.parametrize("B", [128, 256])
+def test_path_length_residues_with_several_cells_a_lane(hip_lib, checker, means, B):
+    xc.check_path_residues(checker, means, B)
+
+
 def test_the_host_module_takes_the_keyword(hip_lib, checker, means):
     from uncalled_amd import _uncalled_amd as unc
     ev, km = xc.follow_case(np.random.default_rng(61), means, 150, 160)
@@ -76,6 +100,33 @@ def test_the_host_module_takes_the_keyword(hip_lib, checker, means):
         assert d.status() == OK and cls(ev.tolist(), km.tolist(), prm).get_path()[0] == (ev.size - 1, km.size - 1)
     with pytest.raises(RuntimeError):
         unc.DTWr94d(ev.tolist(), km.tolist(), prm, adaptive=96)
+
+
+# ------------------------------------------------------------------ 1b. the adaptive band through model, training, pile-up and options
+@pytest.fixture(scope="module")
+def pipe(hip_lib):
+    return apc.Ctx(hip_lib, EX_PREFIX)
+
+
+def test_pipeline_with_a_custom_model(pipe):
+    apc.check_custom_model(pipe)
+
+
+@pytest.mark.parametrize("keep_shared", [False, True])
+def test_training_with_an_open_end(pipe, keep_shared):
+    apc.check_training(pipe, keep_shared)
+
+
+def test_pipeline_rounds_through_the_hook(pipe):
+    apc.check_rounds(pipe)
+
+
+def test_pipeline_options_with_the_adaptive_band(pipe):
+    apc.check_options(pipe)
+
+
+def test_a_path_without_a_start_in_the_pipeline(pipe):
+    apc.check_left_band(pipe)
 
 
 # ------------------------------------------------------------------ 2. more alignments than wavefronts
@@ -95,6 +146,23 @@ def test_more_alignments_than_wavefronts(hip_lib, checker, means):
         res, paths = xc.run(b)
         assert capi.dtw_last_timing()[1] == 1
         xc.assert_equal_to_checker(res, paths, [done[d] for d in q["of"]], b["name"])
+
+
+def test_more_alignments_than_wavefronts_with_bands_that_moved(hip_lib, checker, means):
+    """the same queue cycling the 42 edge alignments at B = 128 and 256: a wavefront goes round the loop again with the rows, model
+    values and events of a band that moved left over in its registers"""
+    import torch
+    from uncalled_amd import capi
+    n = 3 * 16 * torch.cuda.get_device_properties(0).multi_processor_count + 7
+    for B in (128, 256):
+        e = xc.edge_batches(means, xc.R94D, (1.0, 1.0, 1.0), B)[0]
+        done = xc.wanted(checker, e)
+        assert len(done) == 42 and any(w["lo"].max() > -B // 2 + 16 for w in done)
+        of = [a % 42 for a in range(n)]
+        b = xc.batch(f"queue of edges B {B}", [e["evs"][d] for d in of], [e["kms"][d] for d in of], e["cost"], e["weights"], B)
+        res, paths = xc.run(b)
+        assert capi.dtw_last_timing()[1] == 1
+        xc.assert_equal_to_checker(res, paths, [done[d] for d in of], b["name"])
 
 
 # ------------------------------------------------------------------ 3. anti-diagonal indices past 2^16, linear memory
@@ -184,3 +252,68 @@ def test_the_cli_aligns_a_whole_read_from_its_hit(hip_lib, checker, tmp_path):
     assert f[:2] == [rid, "%.6g" % float(res[0]["dtw"]["mean_score"])] and (f[3:] == ["status 7"] if st == REF_END else len(f) == 3), f
     rows = [ln.split("\t") for ln in open(prefix + rid + ".txt").read().strip().split("\n")]
     assert [(int(r[0]), int(r[1])) for r in rows] == [tuple(map(int, p)) for p in paths[0][::-1]]
+
+
+def test_the_cli_trains_with_the_adaptive_band(hip_lib, tmp_path):
+    """the same PAF line fed to `python -m uncalled_amd train --adaptive 128 --iters 2 --min-obs 2 --max-events 2000` in one child
+    process (waited for): the saved model equals the same two iterations driven through capi on the query and stretch that
+    extend_paf_queries makes.  With --adaptive the query is the read from the hit to its END, some 5000 columns of the example read:
+    --max-events 2000 skips it (UNC_ALIGN_TOO_MANY) on both sides and the model stays the prior.  So the iterations behind the command
+    (train_model) run once more in this process without the limit, where the read is aligned and the model moves."""
+    from uncalled_amd import __main__ as cli
+    from uncalled_amd import _uncalled_amd as unc
+    from uncalled_amd import capi
+    ex = np.load(GOLD / "example_read.npz")
+    ix = capi.Index(EX_PREFIX)
+    raw = ex["signal"]
+    offsets = np.array([0, raw.size], np.uint64)
+    calib = capi.make_calib(1, float(ex["range"]), float(ex["offset"]), float(ex["digitisation"]))
+    hit = capi.Mapper(ix, n_slots=64).map_batch(raw, offsets, calib)[0]
+    cols = capi.hit_paf_cols(hit, ix.seq_names())
+    assert cols[1] != "*", cols
+    paf = tmp_path / "hit.paf"
+    paf.write_text("\t".join([str(ex["read_id"])] + [str(c) for c in cols]) + "\n")
+    out = tmp_path / "trained.txt"
+    cmd = [sys.executable, "-m", "uncalled_amd", "train", str(EX_PREFIX), str(GOLD / "example_read.fast5"), str(paf), "-o", str(out), "--adaptive", "128",
+           "--iters", "2", "--min-obs", "2", "--max-events", "2000"]
+    run = subprocess.run(cmd, cwd=str(ROOT), capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    rows = [ln for ln in run.stderr.split("\n") if ln.startswith("iteration ")]
+    assert len(rows) == 2
+    got = capi.Model.load(out)
+
+    queries = cli.load_paf_queries(str(paf))
+    rd = cli.load_query_reads(unc, str(GOLD / "example_read.fast5"), queries)
+    cli.clip_paf_queries(queries, rd)
+    cli.extend_paf_queries(queries, rd, ix)
+    assert len(rd) == 1
+    rid, samples, cal = rd[0]
+    q = queries[rid]
+    assert q["smp_en"] == len(samples) == raw.size
+    calib1 = capi.make_calib(1, 0, 0, 1)
+    calib1[0] = cal
+    stretch = [(ix.seq_names().index(q["ref"]), q["ref_st"], q["ref_en"], q["fwd"])]
+    refseq = capi.RefSeq(ix, EX_PREFIX)
+
+    def two_iterations(max_events):
+        model, used, statuses = capi.Model.default(), [], []
+        for _ in range(2):
+            acc = capi.ModelAcc()
+            res = capi.align_ref_batch(refseq, np.asarray(samples, np.int16), np.array([0, len(samples)], np.uint64), calib1,
+                                       [(0, q["smp_st"], q["smp_en"])], stretch, opts=capi.align_opts(max_events=max_events, adaptive=128),
+                                       model=model, accumulate=acc)
+            statuses.append(int(res["status"][0]))
+            used.append(int(acc.read()[0].sum()))
+            model, _ = acc.finish(model, 2)
+        return model, used, statuses
+
+    model, used, statuses = two_iterations(2000)
+    assert ("iteration 1: %d records used" % used[0]) in rows[0] and ("iteration 2: %d records used" % used[1]) in rows[1]
+    assert got.pairs().tobytes() == model.pairs().tobytes()
+    assert statuses == [capi.ALIGN_TOO_MANY] * 2 and used == [0, 0] and got.pairs().tobytes() == capi.Model.default().pairs().tobytes()
+    # without the limit, in this process
+    lines = []
+    trained = cli.train_model(ix, str(EX_PREFIX), rd, queries, None, 2, 2, False, 0, 0, 2048, 0, lambda *a: lines.append(a), 128)
+    model, used, statuses = two_iterations(0)
+    assert all(s in (OK, REF_END) for s in statuses) and used[0] > 1000 and [ln[1] for ln in lines] == used
+    assert trained.pairs().tobytes() == model.pairs().tobytes() != capi.Model.default().pairs().tobytes()
