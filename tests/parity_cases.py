@@ -398,35 +398,58 @@ def assert_rt_taps_equal(a, ring_a, b, ring_b, what):
     assert np.array_equal(ring_a[:n].view(np.uint32), ring_b[:n].view(np.uint32)), (what, "ring")
 
 
-def case_chunked_stage_tap(lib, oracle_lib, example, goldens, n_reads=8):
+def case_chunked_stage_tap(lib, oracle_lib, example, goldens, n_reads=8, chunk_len=4000, cut=None):
     """Below the PAF of the chunked path: after every read of a channel the EventDetector's counters, the EventProfiler's
     25-event window (mean / varsum / mask countdown / queued events) and the rolling 6000-event Normalizer (mean / varsum /
     write position / ring contents) of the device equal the oracle's bit for bit -- a masking or normalisation slip that
-    cancelled out in the coordinates would show here.  (tests/test_oracle.py pins the oracle's tap against the reference's.)"""
+    cancelled out in the coordinates would show here.  (tests/test_oracle.py pins the oracle's tap against the reference's.)
+    chunk_len: samples per chunk.  With 4000 the channel's state is always stored and loaded at the same phase of the detector's
+    16-slot ring of sums and of its 13-sample window; 37 is a multiple of neither, so the hand-over from chunk to chunk meets every
+    phase of both (with `cut`, the samples a read is cut to, such a run stays short; max_chunks stays at its default of 10^6, so
+    it is never the host that ends a read)."""
     from uncalled_amd.realtime import MapPoolOrd
     po = oracle_lib
     dev_index = _index(lib, example)
     oix = po.Index(example["prefix"])
-    pool = MapPoolOrd(dev_index, n_channels=1)
-    om = po.Mapper(oix)
+    p = capi.default_params(lib)
+    p.chunk_time = chunk_len / p.sample_rate
+    pool = MapPoolOrd(dev_index, n_channels=1, params=p)
+    assert pool.chunk_len == chunk_len
+    om = po.Mapper(oix, to_oracle_params(p))
     off = goldens["sim_offsets"]
     reads = [(example["signal"], (example["range"], example["offset"], example["digitisation"]))]
     for i in range(n_reads - 1):
         reads.append((goldens["sim_signal"][int(off[i]):int(off[i + 1])], (CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION)))
+    reads = [(raw[:cut], cal) for raw, cal in reads]
     for i, (raw, cal) in enumerate(reads):
         pool.add_read(0, i, raw, cal, key=i)
     done = 0
     rounds = 0
+    phases = (set(), set())
     while pool.running():
         for key, r in pool.update():
             raw, cal = reads[key]
-            om.chunk_read(po.calibrate(raw, *cal), 4000)
+            om.chunk_read(po.calibrate(raw, *cal), chunk_len)
             (ta, ra), (tb, rb) = pool.rt.tap_channel(0), om.rt_tap()
             assert_rt_taps_equal(ta, ra, tb, rb, "read %d" % key)
+            # the read went past the point where the profiler releases events: the tap has a normaliser to compare
+            assert int(tb["prof_n"]) == 25 and int(tb["norm_n"]) > 0 and int(tb["det_total_events"]) > 25, (key, tb)
+            if cut is not None:
+                # the device's detector took every sample of every chunk the read was given (t starts at 1); each chunk but the
+                # last handed the state over, at these phases of the 16-slot ring and of the 13-sample window
+                used = int(pool.chunks_used[key])
+                assert int(ta["det_t"]) == min(used * chunk_len, len(raw)) + 1, (key, ta["det_t"], used)
+                for k in range(1, used):
+                    phases[0].add(k * chunk_len % 16)
+                    phases[1].add(k * chunk_len % 13)
             done += 1
         rounds += 1
         assert rounds < 1000
-    assert done == n_reads and int(tb["norm_n"]) == 6000       # (the ring has wrapped by then)
+    assert done == n_reads
+    if cut is None:
+        assert int(tb["norm_n"]) == 6000       # (the ring has wrapped by then)
+    else:
+        assert len(phases[0]) == 16 and len(phases[1]) == 13, phases       # a read may be decided early: the run as a whole met every phase
 
 
 def fuzz_reference(tmp_path):

@@ -167,6 +167,11 @@ def test_chunked_stage_tap(sim_lib, oracle_lib, example, goldens):
     pc.case_chunked_stage_tap(sim_lib, oracle_lib, example, goldens, n_reads=6)
 
 
+def test_chunked_stage_tap_37_sample_chunks(sim_lib, oracle_lib, example, goldens):
+    """the same taps when a chunk ends at every phase of the detector's ring: two reads of 3000 samples in chunks of 37"""
+    pc.case_chunked_stage_tap(sim_lib, oracle_lib, example, goldens, n_reads=2, chunk_len=37, cut=3000)
+
+
 def test_chunked_variants(sim_lib, oracle_lib, example, goldens):
     pc.case_chunked_variants(sim_lib, oracle_lib, example, goldens, n_channels=2, n_reads=3)     # 6 reads on the GPU
 

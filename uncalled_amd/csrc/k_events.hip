@@ -12,6 +12,9 @@
 // pairs need in registers, computes the sixteen t-statistics independently and only then runs the sixteen FSM steps.
 // A wavefront carries `reads_per_wave` reads (64, or fewer so that a batch spreads over more wavefronts).
 // (k_rt_events below, one chunk per lane, keeps its 16-slot ring of sums in LDS.)
+// Both kernels are made of the same leaves, each of the reference's expressions written once: tstat_at (compute_tstat),
+// peak_detect, close_event (create_event) over the detector's record EvState; the chunked path adds prof_add / prof_release
+// (EventProfiler::add_event) and roll_push (Normalizer::push) over the records Prof and Roll (unc_dev_types.h).
 // All float expressions are written one IEEE operation at a time and the file is compiled with
 // -ffp-contract=off: the reference is built without FMA (setup.py:121).
 #include <hip/hip_runtime.h>
@@ -24,14 +27,6 @@ namespace unc {
 
 constexpr int RING = 16;   // >= 13 = 1 + 2*window_length2 (event_detector.cpp:30); power of two
 
-struct Detector {
-    float threshold;
-    uint32_t window_length, masked_to;
-    int32_t peak_pos;
-    float peak_value;
-    bool valid_peak;
-};
-
 // event_detector.cpp:221-279 as straight-line code: 64 lanes follow 64 reads whose detectors are in different states at every
 // sample, so every branch of the written-out form below is taken by some lane and the wavefront pays for all of them plus the
 // exec-mask bookkeeping in between (round 3, profiles/r03_ab_k_events.log: 31.6 -> 27.4 ms per 50 k reads); here both arms are computed and selected (the arithmetic is the same single operations:
@@ -41,6 +36,7 @@ __device__ __forceinline__ bool peak_detect(Detector &det, Detector *long_det, f
     const bool act = !(det.masked_to >= buf_mid);
     const bool idle = det.peak_pos == -1;                       // no candidate yet: following the minimum
     const float pv = det.peak_value;
+    const bool valid = det.valid_peak != 0;                     // (a word in the record; 0 / 1 here, so k_events keeps it in a lane mask)
     // -- idle arm
     const bool a_lt = cur < pv;
     const bool a_rise = !a_lt && (__fsub_rn(cur, pv) > peak_height);
@@ -51,7 +47,7 @@ __device__ __forceinline__ bool peak_detect(Detector &det, Detector *long_det, f
     const float b_pv = b_gt ? cur : pv;
     const int32_t b_pos = b_gt ? (int32_t)buf_mid : det.peak_pos;
     const bool b_over = b_pv > det.threshold;
-    const bool b_valid = det.valid_peak || ((__fsub_rn(b_pv, cur) > peak_height) && b_over);
+    const bool b_valid = valid || ((__fsub_rn(b_pv, cur) > peak_height) && b_over);
     const bool b_emit = b_valid && ((buf_mid - (uint32_t)b_pos) > det.window_length / 2);
     const bool trk = act && !idle;
     if (long_det != nullptr) {
@@ -59,14 +55,14 @@ __device__ __forceinline__ bool peak_detect(Detector &det, Detector *long_det, f
         long_det->masked_to = m ? (uint32_t)b_pos + det.window_length : long_det->masked_to;
         long_det->peak_pos = m ? -1 : long_det->peak_pos;
         long_det->peak_value = m ? FLT_MAX : long_det->peak_value;
-        long_det->valid_peak = m ? false : long_det->valid_peak;
+        long_det->valid_peak = m ? false : long_det->valid_peak != 0;
     }
     const float n_pv = idle ? a_pv : (b_emit ? cur : b_pv);
     const int32_t n_pos = idle ? a_pos : (b_emit ? -1 : b_pos);
-    const bool n_valid = idle ? det.valid_peak : (b_emit ? false : b_valid);
+    const bool n_valid = idle ? valid : (b_emit ? false : b_valid);
     det.peak_value = act ? n_pv : pv;
     det.peak_pos = act ? n_pos : det.peak_pos;
-    det.valid_peak = act ? n_valid : det.valid_peak;
+    det.valid_peak = act ? n_valid : valid;
     return trk && b_emit;
 }
 
@@ -118,19 +114,15 @@ template <uint32_t W, bool FAST> __device__ __forceinline__ float div_w(float x,
 }
 constexpr bool EV_FAST_DIV = UNC_EXACT_DIV_CONST != 0;
 
-// event_detector.cpp:174-219 with the ring addressed by ABSOLUTE position (slot = pos & 15).
-// `st_pos` is the position the reference's `(buf_mid - w) % 13` lands on (it wraps for
-// buf_mid < w, where slot (2^32 + buf_mid - w) % 13 == buf_mid + 6 still holds C[buf_mid + 6]).
+// compute_tstat (event_detector.cpp:174-219) from the cumulative sums S and sums of squares Q at three places: `i` holds
+// C[buf_mid], `st` C[buf_mid - w] and `en` C[buf_mid + w].  Where the three lie is the caller's business (a register window,
+// a ring in LDS), and so are the reference's special cases for the first samples.
 template <uint32_t W, bool FAST>
-__device__ __forceinline__ float tstat_ring(const double *sum, const double *sumsq, int lane, uint32_t buf_mid, bool &bad) {
-    constexpr uint32_t w = W;
-    uint32_t st_pos = buf_mid >= w ? buf_mid - w : buf_mid + 6;
-    uint32_t i = (buf_mid & (RING - 1)) * WAVE + lane, st = (st_pos & (RING - 1)) * WAVE + lane,
-             en = ((buf_mid + w) & (RING - 1)) * WAVE + lane;
-    double sum1 = sum[i] - sum[st];
-    double sumsq1 = sumsq[i] - sumsq[st];
-    float sum2 = (float)(sum[en] - sum[i]);
-    float sumsq2 = (float)(sumsq[en] - sumsq[i]);
+__device__ __forceinline__ float tstat_at(const double *S, const double *Q, uint32_t i, uint32_t st, uint32_t en, bool &bad) {
+    double sum1 = S[i] - S[st];
+    double sumsq1 = Q[i] - Q[st];
+    float sum2 = (float)(S[en] - S[i]);
+    float sumsq2 = (float)(Q[en] - Q[i]);
     float mean1 = (float)div_w<W, FAST>(sum1, bad);
     float mean2 = div_w<W, FAST>(sum2, bad);
     float m1sq = __fmul_rn(mean1, mean1), q2 = div_w<W, FAST>(sumsq2, bad), m2sq = __fmul_rn(mean2, mean2);
@@ -138,6 +130,17 @@ __device__ __forceinline__ float tstat_ring(const double *sum, const double *sum
     combined_var = fmaxf(combined_var, FLT_MIN);
     float delta_mean = __fsub_rn(mean2, mean1);
     return __fdiv_rn(fabsf(delta_mean), sqrt_rn(div_w<W, FAST>(combined_var, bad)));
+}
+
+// the ring addressed by ABSOLUTE position (slot = pos & 15).  `st_pos` is the position the reference's `(buf_mid - w) % 13`
+// lands on (it wraps for buf_mid < w, where slot (2^32 + buf_mid - w) % 13 == buf_mid + 6 still holds C[buf_mid + 6]).
+template <uint32_t W, bool FAST>
+__device__ __forceinline__ float tstat_ring(const double *sum, const double *sumsq, int lane, uint32_t buf_mid, bool &bad) {
+    constexpr uint32_t w = W;
+    uint32_t st_pos = buf_mid >= w ? buf_mid - w : buf_mid + 6;
+    uint32_t i = (buf_mid & (RING - 1)) * WAVE + lane, st = (st_pos & (RING - 1)) * WAVE + lane,
+             en = ((buf_mid + w) & (RING - 1)) * WAVE + lane;
+    return tstat_at<W, FAST>(sum, sumsq, i, st, en, bad);
 }
 template <uint32_t W>
 __device__ __forceinline__ float tstat(const double *sum, const double *sumsq, int lane, uint32_t t, uint32_t buf_mid) {
@@ -152,68 +155,77 @@ __device__ __forceinline__ float tstat(const double *sum, const double *sumsq, i
 constexpr int EB = 8;                 // samples per block of the fast path
 constexpr int WIN = 12 + EB;          // window of cumulative sums: positions base-11 .. base+EB (13 = the reference's ring)
 
-// compute_tstat (event_detector.cpp:174-219) for the sample whose newest cumulative sum sits at window index `ni`:
-// buf_mid = ni - 6, the two windows end / start there.  `st` = index of C[buf_mid - w] (the caller resolves the
-// reference's wrap for the first samples).
+// the t-statistic of the sample whose newest cumulative sum sits at window index `ni`: buf_mid = ni - 6, the two windows
+// end / start there.  `st` = index of C[buf_mid - w] (the caller resolves the reference's wrap for the first samples).
 template <uint32_t W, bool FAST>
 __device__ __forceinline__ float tstat_win(const double *C, const double *Q, int ni, int st, bool &bad) {
-    const int i = ni - 6, en = i + (int)W;
-    double sum1 = C[i] - C[st];
-    double sumsq1 = Q[i] - Q[st];
-    float sum2 = (float)(C[en] - C[i]);
-    float sumsq2 = (float)(Q[en] - Q[i]);
-    float mean1 = (float)div_w<W, FAST>(sum1, bad);
-    float mean2 = div_w<W, FAST>(sum2, bad);
-    float m1sq = __fmul_rn(mean1, mean1), q2 = div_w<W, FAST>(sumsq2, bad), m2sq = __fmul_rn(mean2, mean2);
-    float combined_var = (float)(((div_w<W, FAST>(sumsq1, bad) - (double)m1sq) + (double)q2) - (double)m2sq);
-    combined_var = fmaxf(combined_var, FLT_MIN);
-    float delta_mean = __fsub_rn(mean2, mean1);
-    return __fdiv_rn(fabsf(delta_mean), sqrt_rn(div_w<W, FAST>(combined_var, bad)));
+    return tstat_at<W, FAST>(C, Q, ni - 6, st, ni - 6 + (int)W, bad);
 }
 
-struct EvRun {                        // what EventDetector carries from sample to sample
-    Detector sd, ld;
-    uint32_t t, evt_st, total_events, n_kept, over;      // over: an event found the read's room in `means` full (reported, never silent)
-    double evt_st_sum, mean_sum;
-    float len_sum;
-    double evt_st_sumsq;              // (FULL only)
+// EventDetector::reset, event_detector.cpp:47-77 (the sums are the caller's)
+__device__ __forceinline__ void ev_reset(EvState &E, const unc_params_t &P) {
+    E.sd = Detector{P.threshold1, P.window_length1, 0u, -1, FLT_MAX, 0u};
+    E.ld = Detector{P.threshold2, P.window_length2, 0u, -1, FLT_MAX, 0u};
+    E.t = 1; E.evt_st = 0; E.total_events = 0; E.len_sum = 0.0f; E.evt_st_sum = 0.0; E.evt_st_sumsq = 0.0;
+}
+
+// create_event (event_detector.cpp:296-319) for the event that a peak at buf_mid ends, at position evt_end(buf_mid);
+// csum = C[evt_en], csq = Q[evt_en].  (stdv, which only k_events<true> reports, is its caller's; what it needs of the state
+// as it was is returned: raw_mean, the mean as it is before calibrate, and deltasqr, the event's sum of squares.)
+struct EvClosed { float mean, raw_mean, deltasqr; uint32_t start, length; };
+__device__ __forceinline__ uint32_t evt_end(uint32_t buf_mid) { return buf_mid - UNC_WINDOW1 + 1; }
+__device__ __forceinline__ EvClosed close_event(EvState &E, uint32_t buf_mid, double csum, double csq) {
+    const uint32_t evt_en = evt_end(buf_mid);
+    EvClosed ev;
+    ev.start = E.evt_st;
+    ev.length = (uint32_t)(float)(evt_en - E.evt_st);
+    ev.raw_mean = (float)((csum - E.evt_st_sum) / (double)ev.length);
+    ev.deltasqr = (float)(csq - E.evt_st_sumsq);
+    E.evt_st = evt_en;
+    E.evt_st_sum = csum;
+    E.evt_st_sumsq = csq;
+    E.len_sum = __fadd_rn(E.len_sum, (float)ev.length);
+    E.total_events++;
+    ev.mean = __fmul_rn(__fadd_rn(ev.raw_mean, 0.0f), 1.0f);   // calibrate(): cal_offset_=0, cal_coef_=1
+    return ev;
+}
+// add_sample's answer: the events that reach the mapper (event_detector.cpp:107-108).  A macro and not a function: as the
+// condition of the caller's `if` the two comparisons stay two branches, which is the code k_events had; returned from a
+// function, however spelled, they become one value and the batch kernel's schedule moves.
+#define MEAN_IN_RANGE(P, mean) ((mean) >= (P).min_mean && (mean) <= (P).max_mean)
+
+struct EvRun {                        // a read's detector and what k_events collects from it
+    EvState det;
+    uint32_t n_kept, over;            // over: an event found the read's room in `means` full (reported, never silent)
+    double mean_sum;
 };
 
-// both peak detectors on one sample's t-statistics, then create_event (event_detector.cpp:101-110,296-319); csum = C[evt_en].
+// both peak detectors on one sample's t-statistics, then close_event (add_sample, event_detector.cpp:101-110); csum = C[evt_en].
 // FULL: the whole Event, not its mean alone -- csq = Q[evt_en], and `events` receives start, length and stdv beside the mean
 template <bool FULL>
 __device__ __forceinline__ void fsm_step(EvRun &E, const unc_params_t &P, float t1, float t2, uint32_t buf_mid, double csum, double csq,
                                          float *means, unc_event_t *events, uint32_t mcap) {
-    const bool p1 = peak_detect(E.sd, &E.ld, t1, buf_mid, P.peak_height);
-    const bool p2 = peak_detect(E.ld, nullptr, t2, buf_mid, P.peak_height);
+    const bool p1 = peak_detect(E.det.sd, &E.det.ld, t1, buf_mid, P.peak_height);
+    const bool p2 = peak_detect(E.det.ld, nullptr, t2, buf_mid, P.peak_height);
     if (p1 || p2) {
-        const uint32_t evt_en = buf_mid - UNC_WINDOW1 + 1;
-        const uint32_t length = (uint32_t)(float)(evt_en - E.evt_st);
-        float mean = (float)((csum - E.evt_st_sum) / (double)length);
+        const EvClosed c = close_event(E.det, buf_mid, csum, csq);
         unc_event_t ev;
         if constexpr (FULL) {
             // event_detector.cpp:304-306,309: a double difference rounded to float, the variance in float (the mean as it is before
             // calibrate), the correctly rounded root (sqrt_rn above), calibrate last
-            const float deltasqr = (float)(csq - E.evt_st_sumsq);
-            const float var = __fsub_rn(__fdiv_rn(deltasqr, (float)length), __fmul_rn(mean, mean));
+            const float var = __fsub_rn(__fdiv_rn(c.deltasqr, (float)c.length), __fmul_rn(c.raw_mean, c.raw_mean));
             ev.stdv = __fmul_rn(__fadd_rn(sqrt_rn(fmaxf(var, 0.0f)), 0.0f), 1.0f);
-            ev.start = E.evt_st;
-            ev.length = length;
-            E.evt_st_sumsq = csq;
+            ev.start = c.start;
+            ev.length = c.length;
         }
-        E.evt_st = evt_en;
-        E.evt_st_sum = csum;
-        E.len_sum = __fadd_rn(E.len_sum, (float)length);
-        E.total_events++;
-        mean = __fmul_rn(__fadd_rn(mean, 0.0f), 1.0f);   // calibrate(): cal_offset_=0, cal_coef_=1
-        if (mean >= P.min_mean && mean <= P.max_mean) {
+        if (MEAN_IN_RANGE(P, c.mean)) {
             if (E.n_kept < mcap) {
                 if constexpr (FULL) {
-                    ev.mean = mean;
+                    ev.mean = c.mean;
                     events[E.n_kept] = ev;
                 }
-                means[E.n_kept++] = mean;
-                E.mean_sum += (double)mean;              // Normalizer::set_signal's first sum, in index order
+                means[E.n_kept++] = c.mean;
+                E.mean_sum += (double)c.mean;            // Normalizer::set_signal's first sum, in index order
             } else E.over = 1u;
         }
     }
@@ -243,12 +255,9 @@ __global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint3
     unc_event_t *events = nullptr;
     if constexpr (FULL) events = events_of(full...) + moff;
 
-    // EventDetector::reset, event_detector.cpp:47-77
     EvRun E;
-    E.sd = Detector{P.threshold1, P.window_length1, 0u, -1, FLT_MAX, false};
-    E.ld = Detector{P.threshold2, P.window_length2, 0u, -1, FLT_MAX, false};
-    E.t = 1; E.evt_st = 0; E.total_events = 0; E.n_kept = 0; E.over = 0; E.evt_st_sum = 0.0; E.mean_sum = 0.0; E.len_sum = 0.0f;
-    if constexpr (FULL) E.evt_st_sumsq = 0.0;
+    ev_reset(E.det, P);
+    E.n_kept = 0; E.over = 0; E.mean_sum = 0.0;
     double C[WIN], Q[WIN];            // C[i] = cumulative sum at position (next sample's position) - 12 + i
 #pragma unroll
     for (int i = 0; i < WIN; ++i) { C[i] = 0.0; Q[i] = 0.0; }
@@ -262,11 +271,11 @@ __global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint3
     auto step1 = [&](float s) {
         C[12] = C[11] + (double)s;
         Q[12] = Q[11] + (double)__fmul_rn(s, s);
-        E.t++;
-        const uint32_t buf_mid = E.t - 7;
+        E.det.t++;
+        const uint32_t buf_mid = E.det.t - 7;
         bool bad = false;      // (head and tail samples: the division itself)
-        const float t1 = E.t <= 2 * UNC_WINDOW1 ? 0.0f : tstat_win<UNC_WINDOW1, false>(C, Q, 12, buf_mid >= UNC_WINDOW1 ? 6 - UNC_WINDOW1 : 12, bad);
-        const float t2 = E.t <= 2 * UNC_WINDOW2 ? 0.0f : tstat_win<UNC_WINDOW2, false>(C, Q, 12, buf_mid >= UNC_WINDOW2 ? 6 - UNC_WINDOW2 : 12, bad);
+        const float t1 = E.det.t <= 2 * UNC_WINDOW1 ? 0.0f : tstat_win<UNC_WINDOW1, false>(C, Q, 12, buf_mid >= UNC_WINDOW1 ? 6 - UNC_WINDOW1 : 12, bad);
+        const float t2 = E.det.t <= 2 * UNC_WINDOW2 ? 0.0f : tstat_win<UNC_WINDOW2, false>(C, Q, 12, buf_mid >= UNC_WINDOW2 ? 6 - UNC_WINDOW2 : 12, bad);
         fsm_step<FULL>(E, P, t1, t2, buf_mid, C[4], Q[4], means, events, mcap);
 #pragma unroll
         for (int i = 0; i < 12; ++i) { C[i] = C[i + 1]; Q[i] = Q[i + 1]; }
@@ -304,8 +313,8 @@ __global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint3
         }
 #pragma unroll
         for (int j = 0; j < EB; ++j) {
-            E.t++;
-            fsm_step<FULL>(E, P, t1[j], t2[j], E.t - 7, C[4 + j], Q[4 + j], means, events, mcap);
+            E.det.t++;
+            fsm_step<FULL>(E, P, t1[j], t2[j], E.det.t - 7, C[4 + j], Q[4 + j], means, events, mcap);
         }
 #pragma unroll
         for (int i = 0; i < 12; ++i) { C[i] = C[i + EB]; Q[i] = Q[i + EB]; }
@@ -328,45 +337,73 @@ __global__ __launch_bounds__(64) void k_events(DevReads R, unc_params_t P, uint3
     }
     unc_evt_info_t inf;
     inf.n_events = n_kept;
-    inf.total_events = E.total_events;
-    inf.len_sum = E.len_sum;
+    inf.total_events = E.det.total_events;
+    inf.len_sum = E.det.len_sum;
     inf.scale = scale;
     inf.shift = shift;
     inf.pad = E.over;        // 1: the read has more events than its room in `means` (the host fails the call loudly)
     R.info[r] = inf;
 }
 
-}  // namespace unc
-
-namespace unc {
 // ---------------------------------------------------------------------------------------------------
 // Chunked (realtime / MAP_ORD) path: Mapper::process_chunk (mapper.cpp:307-367) for one chunk per channel,
 // one lane per channel, with the per-channel state a Mapper keeps between chunks held in HBM (RtChan):
 // the streaming detector, the 25-event EventProfiler window (event_profiler.hpp:71-104: events are released
 // 24 late and masked while the window's stdv < 5) and the rolling 6000-event Normalizer
 // (normalizer.cpp:46-75), which deliberately survives across reads (mapper.cpp:225-226).
-__device__ __forceinline__ bool roll_push(float *signal, uint32_t size, double &mean, double &varsum, uint32_t &n, uint32_t &rd,
-                                          uint32_t &wr, uint32_t &full, float newevt) {
-    if (full) return false;
-    const double oldevt = (double)signal[wr];
-    signal[wr] = newevt;
-    if (n == size) {
-        const double oldmean = mean;
-        mean += ((double)newevt - oldevt) / (double)size;
-        varsum += ((double)newevt + oldevt - oldmean - mean) * ((double)newevt - oldevt);
+// Normalizer::push (normalizer.cpp:46-75) on a ring of `size` values
+__device__ __forceinline__ bool roll_push(Roll &r, float *signal, uint32_t size, float newevt) {
+    if (r.full) return false;
+    const double oldevt = (double)signal[r.wr];
+    signal[r.wr] = newevt;
+    if (r.n == size) {
+        const double oldmean = r.mean;
+        r.mean += ((double)newevt - oldevt) / (double)size;
+        r.varsum += ((double)newevt + oldevt - oldmean - r.mean) * ((double)newevt - oldevt);
     } else {
-        n++;
-        const double dt1 = (double)newevt - mean;
-        mean += dt1 / (double)n;
-        const double dt2 = (double)newevt - mean;
-        varsum += dt1 * dt2;
+        r.n++;
+        const double dt1 = (double)newevt - r.mean;
+        r.mean += dt1 / (double)r.n;
+        const double dt2 = (double)newevt - r.mean;
+        r.varsum += dt1 * dt2;
     }
-    wr = wr + 1 == size ? 0 : wr + 1;
-    full = wr == rd ? 1u : 0u;
+    r.wr = r.wr + 1 == size ? 0 : r.wr + 1;
+    r.full = r.wr == r.rd ? 1u : 0u;
     return true;
 }
-__device__ __forceinline__ uint32_t roll_unread(uint32_t n, uint32_t rd, uint32_t wr) {
-    return rd < wr ? wr - rd : (n - rd) + wr;   // Normalizer::unread_size, normalizer.cpp:131-134
+__device__ __forceinline__ uint32_t roll_unread(const Roll &r) {
+    return r.rd < r.wr ? r.wr - r.rd : (r.n - r.rd) + r.wr;   // Normalizer::unread_size, normalizer.cpp:131-134
+}
+// what a read starts with and what every chunk starts with (update() has popped every event of the chunk before: the read
+// pointer has caught up): Normalizer::skip_unread(0)
+__device__ __forceinline__ void roll_skip_unread(Roll &r) { r.rd = r.wr; r.full = 0; }
+
+// EventProfiler::add_event (event_profiler.hpp:71-104) as two leaves; its two conditions (enough unread events in the window; the
+// profiler full and nothing masked) stand in the caller's loop as they do in the reference, each with its `continue`.  One leaf
+// returning bool put the result in a value and the loop branched four times more (profiles/k_events_records_parent_vs_branch.txt).
+// prof_add: the event enters the window and the queue.  pw_signal: the window's values, evq: the queue of the same events
+__device__ __forceinline__ void prof_add(Prof &p, float *pw_signal, float *evq, float mean) {
+    roll_push(p.win, pw_signal, PROF_WIN, mean);
+    uint32_t qi = p.q_head + p.q_len; if (qi >= PROF_WIN + 1) qi -= PROF_WIN + 1;
+    evq[qi] = mean;
+    p.q_len++;
+}
+// prof_release: the mask countdown from the window's stdv, then the oldest event leaves a full window; its mean (the one added
+// PROF_WIN - 1 events ago), or 0 while the window fills
+__device__ __forceinline__ float prof_release(Prof &p, const float *evq) {
+    const float win_stdv = (float)sqrt(p.win.varsum / (double)p.win.n);
+    if (win_stdv < 5.0f) p.to_mask = PROF_WIN - 1;      // win_stdv_min, event_profiler.cpp:7
+    else if (p.to_mask > 0) p.to_mask--;
+    float released = 0.0f;
+    if (p.win.full) {
+        released = evq[p.q_head];
+        p.q_head = p.q_head + 1 == PROF_WIN + 1 ? 0 : p.q_head + 1;
+        p.q_len--;
+        p.win.rd = p.win.rd + 1 == PROF_WIN ? 0 : p.win.rd + 1;   // window_.pop()
+        p.win.full = 0;
+        p.prof_full = 1;
+    }
+    return released;
 }
 
 // lanes_per_wave: how many lanes of a wavefront follow a channel.  The lanes of a wavefront are different channels in different
@@ -385,41 +422,25 @@ __global__ __launch_bounds__(64) void k_rt_events(const int16_t *raw, const floa
     RtChan *C = chans + cd.channel;
     float *ring = norm_ring + (size_t)cd.channel * NORM_LEN;
 
-    // ---- load (or reset) the per-channel state
-    uint32_t t, evt_st, total_events, n_pushed, ring0, status = 0;
-    double evt_st_sum, evt_st_sumsq;
-    float len_sum;
-    Detector sd, ld;
-    double n_mean = C->n_mean, n_varsum = C->n_varsum;
-    uint32_t n_n = C->n_n, n_rd = C->n_rd, n_wr = C->n_wr, n_full = C->n_full;
-    double pw_mean, pw_varsum;
-    uint32_t pw_n, pw_rd, pw_wr, pw_full, q_head, q_len, prof_full, to_mask;
+    // ---- load (or reset) the per-channel state: each record whole
+    EvState det;
+    Prof prof;
+    RtRead rd;
+    Roll norm = C->norm;        // deliberately survives across reads (mapper.cpp:225-226)
+    roll_skip_unread(norm);
     if (cd.new_read) {
         // Mapper::reset (mapper.cpp:219-246): evdt_.reset(), evt_prof_.reset(), norm_.skip_unread()
         s_sum[lane] = 0.0; s_sumsq[lane] = 0.0;
-        t = 1; evt_st = 0; total_events = 0; evt_st_sum = evt_st_sumsq = 0.0; len_sum = 0.0f;
-        sd = Detector{P.threshold1, P.window_length1, 0u, -1, FLT_MAX, false};
-        ld = Detector{P.threshold2, P.window_length2, 0u, -1, FLT_MAX, false};
-        pw_mean = pw_varsum = 0.0; pw_n = pw_rd = pw_wr = pw_full = 0; q_head = q_len = 0; prof_full = 0; to_mask = 0;
+        ev_reset(det, P);
+        prof = Prof{};
         C->pw_signal[0] = 0.0f;
-        n_rd = n_wr;            // skip_unread(0): drop whatever the previous read left unread
-        n_full = 0;
-        ring0 = n_wr;
-        n_pushed = 0;
+        rd = RtRead{norm.wr, 0u, 0u};
     } else {
 #pragma unroll
         for (int i = 0; i < RING; ++i) { s_sum[i * WAVE + lane] = C->sum[i]; s_sumsq[i * WAVE + lane] = C->sumsq[i]; }
-        t = C->t; evt_st = C->evt_st; total_events = C->total_events; evt_st_sum = C->evt_st_sum; evt_st_sumsq = C->evt_st_sumsq;
-        len_sum = C->len_sum;
-        sd = Detector{C->sd.threshold, C->sd.window_length, C->sd.masked_to, C->sd.peak_pos, C->sd.peak_value, C->sd.valid_peak != 0};
-        ld = Detector{C->ld.threshold, C->ld.window_length, C->ld.masked_to, C->ld.peak_pos, C->ld.peak_value, C->ld.valid_peak != 0};
-        pw_mean = C->pw_mean; pw_varsum = C->pw_varsum; pw_n = C->pw_n; pw_rd = C->pw_rd; pw_wr = C->pw_wr; pw_full = C->pw_full;
-        q_head = C->q_head; q_len = C->q_len; prof_full = C->prof_full; to_mask = C->to_mask;
-        ring0 = C->ring0; n_pushed = C->n_pushed; status = C->status;
-        // every event of the previous chunk has been popped by the time the next chunk is added (a chunk is only
-        // added once Mapper::chunk_mapped(), realtime_pool.cpp:133-138): the read pointer has caught up
-        n_rd = n_wr;
-        n_full = 0;
+        det = C->det;
+        prof = C->prof;
+        rd = C->read;
     }
 
     // samples: stored int16 + the channel's calibration, or floats taken as they are (Chunk keeps floats, chunk.cpp:27-66)
@@ -432,78 +453,52 @@ __global__ __launch_bounds__(64) void k_rt_events(const int16_t *raw, const floa
             const uint16_t ru = (uint16_t)rp[k];
             s = __fdiv_rn(__fmul_rn(cd.cal_range, __fadd_rn((float)(int)ru, cd.cal_offset)), cd.cal_digit);
         }
-        const uint32_t cur = (t & (RING - 1)) * WAVE + lane, prv = ((t - 1) & (RING - 1)) * WAVE + lane;
+        // EventDetector::add_sample (event_detector.cpp:83-112)
+        const uint32_t cur = (det.t & (RING - 1)) * WAVE + lane, prv = ((det.t - 1) & (RING - 1)) * WAVE + lane;
         const float ss = __fmul_rn(s, s);
         s_sum[cur] = s_sum[prv] + (double)s;
         s_sumsq[cur] = s_sumsq[prv] + (double)ss;
-        t++;
-        const uint32_t buf_mid = t - 7;
-        const float t1 = tstat<UNC_WINDOW1>(s_sum, s_sumsq, lane, t, buf_mid);
-        const float t2 = tstat<UNC_WINDOW2>(s_sum, s_sumsq, lane, t, buf_mid);
-        const bool p1 = peak_detect(sd, &ld, t1, buf_mid, P.peak_height);
-        const bool p2 = peak_detect(ld, nullptr, t2, buf_mid, P.peak_height);
+        det.t++;
+        const uint32_t buf_mid = det.t - 7;
+        const float t1 = tstat<UNC_WINDOW1>(s_sum, s_sumsq, lane, det.t, buf_mid);
+        const float t2 = tstat<UNC_WINDOW2>(s_sum, s_sumsq, lane, det.t, buf_mid);
+        const bool p1 = peak_detect(det.sd, &det.ld, t1, buf_mid, P.peak_height);
+        const bool p2 = peak_detect(det.ld, nullptr, t2, buf_mid, P.peak_height);
         if (!(p1 || p2)) continue;
-        const uint32_t evt_en = buf_mid - UNC_WINDOW1 + 1;
-        const uint32_t eb = (evt_en & (RING - 1)) * WAVE + lane;
-        const uint32_t length = (uint32_t)(float)(evt_en - evt_st);
-        const double csum = s_sum[eb], csq = s_sumsq[eb];
-        float mean = (float)((csum - evt_st_sum) / (double)length);
-        evt_st = evt_en; evt_st_sum = csum; evt_st_sumsq = csq;
-        len_sum = __fadd_rn(len_sum, (float)length);
-        total_events++;
-        mean = __fmul_rn(__fadd_rn(mean, 0.0f), 1.0f);
-        if (!(mean >= P.min_mean && mean <= P.max_mean)) continue;
-        // EventProfiler::add_event
-        roll_push(C->pw_signal, PROF_WIN, pw_mean, pw_varsum, pw_n, pw_rd, pw_wr, pw_full, mean);
-        {
-            uint32_t qi = q_head + q_len; if (qi >= PROF_WIN + 1) qi -= PROF_WIN + 1;
-            C->evq[qi] = mean;
-            q_len++;
-        }
-        if (roll_unread(pw_n, pw_rd, pw_wr) <= PROF_WIN / 2) continue;
-        const float win_stdv = (float)sqrt(pw_varsum / (double)pw_n);
-        if (win_stdv < 5.0f) to_mask = PROF_WIN - 1;      // win_stdv_min, event_profiler.cpp:7
-        else if (to_mask > 0) to_mask--;
-        float next_mean = 0.0f;
-        if (pw_full) {
-            next_mean = C->evq[q_head];
-            q_head = q_head + 1 == PROF_WIN + 1 ? 0 : q_head + 1;
-            q_len--;
-            pw_rd = pw_rd + 1 == PROF_WIN ? 0 : pw_rd + 1;   // window_.pop()
-            pw_full = 0;
-            prof_full = 1;
-        }
-        if (!(prof_full && to_mask == 0)) continue;
+        const uint32_t eb = (evt_end(buf_mid) & (RING - 1)) * WAVE + lane;
+        const EvClosed ev = close_event(det, buf_mid, s_sum[eb], s_sumsq[eb]);
+        if (!MEAN_IN_RANGE(P, ev.mean)) continue;
+        prof_add(prof, C->pw_signal, C->evq, ev.mean);
+        if (roll_unread(prof.win) <= PROF_WIN / 2) continue;
+        const float next_mean = prof_release(prof, C->evq);
+        if (!(prof.prof_full && prof.to_mask == 0)) continue;
         // norm_.push(evt_mean), mapper.cpp:336-351.  A full ring (>= 6000 unread events) cannot happen when every
         // chunk is mapped before the next one is added; it is reported instead of reproducing the #SKIP path.
-        if (!roll_push(ring, NORM_LEN, n_mean, n_varsum, n_n, n_rd, n_wr, n_full, next_mean)) { status |= UNC_READ_NORM_FULL; break; }
-        n_pushed++;
+        if (!roll_push(norm, ring, NORM_LEN, next_mean)) { rd.status |= UNC_READ_NORM_FULL; break; }
+        rd.n_pushed++;
     }
 
     // ---- save state
 #pragma unroll
     for (int i = 0; i < RING; ++i) { C->sum[i] = s_sum[i * WAVE + lane]; C->sumsq[i] = s_sumsq[i * WAVE + lane]; }
-    C->t = t; C->evt_st = evt_st; C->total_events = total_events; C->evt_st_sum = evt_st_sum; C->evt_st_sumsq = evt_st_sumsq;
-    C->len_sum = len_sum;
-    C->sd = RtDetector{sd.threshold, sd.window_length, sd.masked_to, sd.peak_pos, sd.peak_value, sd.valid_peak ? 1u : 0u};
-    C->ld = RtDetector{ld.threshold, ld.window_length, ld.masked_to, ld.peak_pos, ld.peak_value, ld.valid_peak ? 1u : 0u};
-    C->pw_mean = pw_mean; C->pw_varsum = pw_varsum; C->pw_n = pw_n; C->pw_rd = pw_rd; C->pw_wr = pw_wr; C->pw_full = pw_full;
-    C->q_head = q_head; C->q_len = q_len; C->prof_full = prof_full; C->to_mask = to_mask;
-    C->n_mean = n_mean; C->n_varsum = n_varsum; C->n_n = n_n; C->n_rd = n_rd; C->n_wr = n_wr; C->n_full = n_full;
-    C->ring0 = ring0; C->n_pushed = n_pushed; C->status = status;
+    C->det = det;
+    C->prof = prof;
+    C->norm = norm;
+    C->read = rd;
 
     // Normalizer::at: scale / shift from the rolling statistics after the whole chunk has been pushed
     float scale = 0.0f, shift = 0.0f;
-    if (n_n > 0) {
-        scale = (float)((double)tgt_stdv / sqrt(n_varsum / (double)n_n));
-        shift = (float)((double)tgt_mean - (double)scale * n_mean);
+    if (norm.n > 0) {
+        scale = (float)((double)tgt_stdv / sqrt(norm.varsum / (double)norm.n));
+        shift = (float)((double)tgt_mean - (double)scale * norm.mean);
     }
     unc_evt_info_t inf;
-    inf.n_events = n_pushed; inf.total_events = total_events; inf.len_sum = len_sum; inf.scale = scale; inf.shift = shift;
-    inf.pad = status;
+    inf.n_events = rd.n_pushed; inf.total_events = det.total_events; inf.len_sum = det.len_sum; inf.scale = scale; inf.shift = shift;
+    inf.pad = rd.status;
     info[ci] = inf;
-    ring0_out[ci] = ring0;
+    ring0_out[ci] = rd.ring0;
 }
+#undef MEAN_IN_RANGE
 }  // namespace unc
 
 #include "unc_kernels.h"

@@ -190,29 +190,39 @@ struct DevScratch {
 constexpr uint32_t NORM_LEN = 6000;   // Normalizer::PRMS_DEF.len, normalizer.cpp:4-8
 constexpr uint32_t PROF_WIN = 25;     // EventProfiler::PRMS_DEF.win_len, event_profiler.cpp:4-10
 
-struct RtDetector { float threshold; uint32_t window_length, masked_to; int32_t peak_pos; float peak_value; uint32_t valid_peak; };
-
-struct alignas(16) RtChan {
-    // EventDetector (event_detector.hpp:106-128); cumulative sums by absolute position & 15
-    double sum[16], sumsq[16];
-    double evt_st_sum, evt_st_sumsq;
+// The records below are what k_events.hip works on; the kernels carry them in registers, and a channel's copy is loaded and
+// stored whole.
+// one of EventDetector's two peak detectors (event_detector.hpp:99-108)
+struct Detector { float threshold; uint32_t window_length, masked_to; int32_t peak_pos; float peak_value; uint32_t valid_peak; };
+// what EventDetector carries from sample to sample beside its ring of sums (event_detector.hpp:106-128)
+struct EvState {
+    Detector sd, ld;
     uint32_t t, evt_st, total_events;
     float len_sum;
-    RtDetector sd, ld;
-    // EventProfiler (event_profiler.hpp:35-48): rolling 25-window + the queued event means
-    double pw_mean, pw_varsum;
-    float pw_signal[PROF_WIN + 3];
-    float evq[PROF_WIN + 3];
-    uint32_t pw_n, pw_rd, pw_wr, pw_full, q_head, q_len, prof_full, to_mask;
-    // Normalizer in rolling mode (normalizer.hpp:74-79); the 6000-float ring lives in DevRt::norm_ring
-    double n_mean, n_varsum;
-    uint32_t n_n, n_rd, n_wr, n_full, n_empty;
-    // current read
+    double evt_st_sum, evt_st_sumsq;
+};
+// Normalizer in rolling mode (normalizer.hpp:74-79) without its ring of values
+struct Roll { double mean, varsum; uint32_t n, rd, wr, full; };
+// EventProfiler (event_profiler.hpp:35-48): the rolling 25-event window and the queue of the same events
+struct Prof { Roll win; uint32_t q_head, q_len, prof_full, to_mask; };
+// the read a channel is on
+struct RtRead {
     uint32_t ring0;        // ring slot holding event 0 of this read
     uint32_t n_pushed;     // events pushed for this read so far
     uint32_t status;       // UNC_READ_* bits
-    uint32_t pad[2];
 };
+
+struct alignas(16) RtChan {
+    double sum[16], sumsq[16];       // the detector's cumulative sums by absolute position & 15
+    EvState det;
+    Prof prof;
+    float pw_signal[PROF_WIN + 3];   // prof.win's values
+    float evq[PROF_WIN + 3];         // prof's queue
+    Roll norm;                       // its 6000-float ring lives in unc_rt::d_ring
+    RtRead read;
+    uint32_t pad_[5];                // unc_rt_device_bytes() counts this record: its size stays what it was
+};
+static_assert(sizeof(RtChan) == 672 && sizeof(RtChan) % 16 == 0, "RtChan: one 16-byte aligned record per channel");
 
 struct RtChunkDesc {       // one chunk = one channel's next <= 4000 samples (Chunk, chunk.hpp:32-59)
     uint64_t offset;       // into the raw int16 array

@@ -1924,10 +1924,13 @@ extern "C" int unc_rt_tap_channel(unc_rt_t *rt, uint32_t channel, unc_rt_tap_t *
     HIPCHK(hipMemcpy(&c, rt->d_chans.p + channel, sizeof c, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(ring, rt->d_ring.p + (size_t)channel * NORM_LEN, (size_t)NORM_LEN * 4, hipMemcpyDeviceToHost));
     memset(out, 0, sizeof *out);
-    out->det_t = c.t; out->det_total_events = c.total_events; out->det_len_sum = c.len_sum;
-    out->norm_n = c.n_n; out->norm_wr = c.n_wr; out->norm_mean = c.n_mean; out->norm_varsum = c.n_varsum;
-    out->prof_n = c.pw_n; out->prof_to_mask = c.to_mask; out->prof_queued = c.q_len; out->prof_mean = c.pw_mean; out->prof_varsum = c.pw_varsum;
-    for (uint32_t i = 0; i < c.q_len && i < 28; ++i) out->prof_queue[i] = c.evq[(c.q_head + i) % (PROF_WIN + 1)];
+    const EvState &det = c.det;
+    const Prof &prof = c.prof;
+    const Roll &norm = c.norm;
+    out->det_t = det.t; out->det_total_events = det.total_events; out->det_len_sum = det.len_sum;
+    out->norm_n = norm.n; out->norm_wr = norm.wr; out->norm_mean = norm.mean; out->norm_varsum = norm.varsum;
+    out->prof_n = prof.win.n; out->prof_to_mask = prof.to_mask; out->prof_queued = prof.q_len; out->prof_mean = prof.win.mean; out->prof_varsum = prof.win.varsum;
+    for (uint32_t i = 0; i < prof.q_len && i < 28; ++i) out->prof_queue[i] = c.evq[(prof.q_head + i) % (PROF_WIN + 1)];
     return UNC_OK;
 }
 
