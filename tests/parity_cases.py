@@ -386,16 +386,24 @@ def case_chunked_variants(lib, oracle_lib, example, goldens, n_channels=2, n_rea
             assert (pool.chunks_used[i], bool(got[i]["ended"])) == fate[i], (ov, chunk_len, i)       # chunks the read was given, Paf::ENDED
 
 
-def assert_rt_taps_equal(a, ring_a, b, ring_b, what):
-    """stage tap of the chunked path (unc_rt_tap_t layout): detector counters, profiler window + queue, rolling normaliser + ring"""
-    for f in ("det_t", "det_total_events", "det_len_sum", "norm_n", "norm_wr", "prof_n", "prof_to_mask", "prof_queued"):
+def assert_rt_taps_equal(a, ring_a, b, ring_b, what, nan_is_nan=False):
+    """stage tap of the chunked path (unc_rt_tap_t layout): detector counters, profiler window + queue, rolling normaliser + ring.
+    nan_is_nan: where BOTH sides hold a NaN the two count as equal whatever their bits (the sign of a NaN an operation generates is
+    the platform's); everything else stays bit for bit"""
+    def same(x, y):
+        x, y = np.atleast_1d(x), np.atleast_1d(y)
+        eq = x.view("u%d" % x.itemsize) == y.view("u%d" % y.itemsize)
+        return bool(np.all(eq | (np.isnan(x) & np.isnan(y)) if nan_is_nan else eq))
+    for f in ("det_t", "det_total_events", "norm_n", "norm_wr", "prof_n", "prof_to_mask", "prof_queued"):
         assert a[f] == b[f], (what, f, a[f], b[f])
+    assert a["det_len_sum"] == b["det_len_sum"] or (nan_is_nan and same(np.float32(a["det_len_sum"]), np.float32(b["det_len_sum"]))), \
+        (what, "det_len_sum", a["det_len_sum"], b["det_len_sum"])
     for f in ("norm_mean", "norm_varsum", "prof_mean", "prof_varsum"):
-        assert np.float64(a[f]).tobytes() == np.float64(b[f]).tobytes(), (what, f, a[f], b[f])
+        assert same(np.float64(a[f]), np.float64(b[f])), (what, f, a[f], b[f])
     q = int(a["prof_queued"])
-    assert np.array_equal(a["prof_queue"][:q].view(np.uint32), b["prof_queue"][:q].view(np.uint32)), (what, "prof_queue")
+    assert same(a["prof_queue"][:q], b["prof_queue"][:q]), (what, "prof_queue")
     n = int(a["norm_n"])
-    assert np.array_equal(ring_a[:n].view(np.uint32), ring_b[:n].view(np.uint32)), (what, "ring")
+    assert same(ring_a[:n], ring_b[:n]), (what, "ring")
 
 
 def case_chunked_stage_tap(lib, oracle_lib, example, goldens, n_reads=8, chunk_len=4000, cut=None):
@@ -1058,6 +1066,25 @@ def case_event_mean_bounds(lib, oracle_lib, example):
         assert int(info["total_events"][0]) > int(info["n_events"][0])     # events beyond the bounds were detected and dropped
 
 
+def zero_pa_signal(cal, rng, n_parts=120):
+    """runs of 2 to 15 samples, in turn: exactly 0 pA, one negative level, a mixture of the two, ordinary levels -- stored int16 samples
+    for the calibration `cal` (an integer negative offset: the stored value -offset is 0 pA)"""
+    z = int(-cal[1])                               # the stored value of 0 pA
+    parts = []
+    for k in range(n_parts):
+        kind = k % 4
+        ln = int(rng.integers(2, 16))
+        if kind == 0:
+            parts.append(np.full(ln, z))
+        elif kind == 1:
+            parts.append(np.full(ln, int(rng.integers(max(0, z - 40), z))))
+        elif kind == 2:
+            parts.append(rng.integers(max(0, z - 3), z + 1, ln))
+        else:
+            parts.append(rng.integers(z + 150, z + 400, ln))
+    return np.concatenate(parts).astype(np.int16)
+
+
 def case_zero_pa_windows(lib, oracle_lib, example):
     """Integer negative offsets: runs of samples at exactly 0 pA, runs of negative pA and mixtures of the two inside one t-statistic
     window (the sums of a window are then exactly zero or of either sign: the exact division's fallback, k_events.hip div_w), between
@@ -1067,20 +1094,8 @@ def case_zero_pa_windows(lib, oracle_lib, example):
     rng = np.random.default_rng(13)
     for name in ("promethion", "minion_b"):
         cal = REGIMES[name]
-        z = int(-cal[1])                               # the stored value of 0 pA
-        parts = []
-        for k in range(120):
-            kind = k % 4
-            ln = int(rng.integers(2, 16))
-            if kind == 0:
-                parts.append(np.full(ln, z))
-            elif kind == 1:
-                parts.append(np.full(ln, int(rng.integers(max(0, z - 40), z))))
-            elif kind == 2:
-                parts.append(rng.integers(max(0, z - 3), z + 1, ln))
-            else:
-                parts.append(rng.integers(z + 150, z + 400, ln))
-        r = np.concatenate(parts).astype(np.int16)
+        z = int(-cal[1])
+        r = zero_pa_signal(cal, rng)
         for p in (capi.default_params(lib), _wide_bounds(lib)):
             m = capi.Mapper(_index(lib, example), params=p, n_slots=2)
             for pad in (0, 1, 5, 13):
@@ -1184,8 +1199,18 @@ class _ShuffledRt:
 
     def __init__(self, rt, po, rng, f32):
         self.rt, self.po, self.rng, self.f32, self.params = rt, po, rng, f32, rt.params
+        self.call_sizes, self.mixed_calls = [], 0      # chunks per call; calls that held UNC_RT_FIRST chunks beside continuing ones
+
+    def tap_channel(self, channel):
+        return self.rt.tap_channel(channel)
+
+    def close(self):
+        self.rt.close()
 
     def process_chunks(self, chunks, raw):
+        first = (chunks["flags"] & capi.RT_FIRST) != 0
+        self.call_sizes.append(int(chunks.size))
+        self.mixed_calls += int(first.any() and not first.all())
         p = self.rng.permutation(chunks.size)
         ch = chunks[p].copy()
         if self.f32:
@@ -1203,12 +1228,15 @@ class _ShuffledRt:
 
 
 def case_chunked_per_channel_calibration(lib, oracle_lib, example, goldens, n_channels=3, reads_per_channel=2, shuffle=False, f32=False,
-                                         cut=None, seed=31):
+                                         cut=None, seed=31, params=None, taps=False, min_mapped=0.6, out=None):
     """The chunked path with a calibration per channel AND per read (a channel's successive reads differ: a value kept from the
     channel's first read shows), reads re-digitised for them.  shuffle: every round's chunks in a random order and random channels left
     out of some rounds -- no channel's sequence changes, so a mix-up of the active-chunk index and the channel (descriptors, slot map,
     event-means offsets) shows.  f32: the chunks as floats with nonsense calibrations, which that entry ignores.  Each channel against
-    one oracle Mapper fed the same reads in the same order (on the host's threads)."""
+    one oracle Mapper fed the same reads in the same order (on the host's threads).  params: other parameters than the defaults (the
+    chunk length is chunk_time * sample_rate).  taps: after every finished read the channel's stage tap against the tap its oracle
+    Mapper had after the same read.  min_mapped: the share of the reads the oracle must map (reads cut short rarely do).  out: a dict
+    that receives every read's RT_RESULT record ("results") and what the calls carried ("call_sizes", "mixed_calls")."""
     from concurrent.futures import ThreadPoolExecutor
     from tests.helpers import REGIMES, redigitise
     from uncalled_amd.realtime import MapPoolOrd
@@ -1227,20 +1255,23 @@ def case_chunked_per_channel_calibration(lib, oracle_lib, example, goldens, n_ch
             src = goldens["sim_signal"][int(off[k % n_src]):int(off[k % n_src + 1])]
             raw = redigitise(src[:cut] if cut else src, REGIMES["minion"], cal)
             reads[k] = (ch, raw, cal)
-    pool = MapPoolOrd(dev_index, n_channels=n_channels)
+    pool = MapPoolOrd(dev_index, n_channels=n_channels, params=params)
     rng = np.random.default_rng(seed)
     pool.rt = _ShuffledRt(pool.rt, po, rng, f32) if (shuffle or f32) else pool.rt
     for k, (ch, raw, cal) in reads.items():
         pool.add_read(ch, k, raw, cal, key=k)
+    oracle_taps = {}                              # key -> (tap, ring) of the channel's oracle Mapper after that read
 
     def oracle_channel(ch):
-        om = po.Mapper(oix)
-        out = {}
+        om = po.Mapper(oix, to_oracle_params(params) if params is not None else None)
+        done = {}
         for k in range(ch * reads_per_channel, (ch + 1) * reads_per_channel):
             _, raw, cal = reads[k]
             h, used = om.chunk_read(po.calibrate(raw, *cal), pool.chunk_len)
-            out[k] = (h, used, om.rt_ended())
-        return out
+            done[k] = (h, used, om.rt_ended())
+            if taps:
+                oracle_taps[k] = om.rt_tap()
+        return done
     import os
     with ThreadPoolExecutor(max_workers=max(1, min(16, len(os.sched_getaffinity(0))))) as ex:
         futs = [ex.submit(oracle_channel, ch) for ch in range(n_channels)]
@@ -1259,12 +1290,18 @@ def case_chunked_per_channel_calibration(lib, oracle_lib, example, goldens, n_ch
         try:
             for key, r in pool.update():
                 got[key] = r
+                if taps:      # (the channel's next read starts with the next round: this is its state after read `key`)
+                    (ta, ra), (tb, rb) = pool.rt.tap_channel(reads[key][0]), oracle_taps[key]
+                    assert_rt_taps_equal(ta, ra, tb, rb, "channel %d read %d" % (reads[key][0], key))
         finally:
             for ch, q in held.items():
                 pool.queues[ch] = q
         rounds += 1
         assert rounds < 4000
     assert not shuffle or skipped > 0
+    if out is not None:
+        out["results"] = {k: got[k].tobytes() for k in sorted(got)}
+        out["call_sizes"], out["mixed_calls"] = list(getattr(pool.rt, "call_sizes", [])), getattr(pool.rt, "mixed_calls", 0)
     ref_names, dev_names = oix.ref_names(), dev_index.seq_names()
     for k in reads:
         h, (o, used, ended) = got[k]["hit"], want[k]
@@ -1275,9 +1312,260 @@ def case_chunked_per_channel_calibration(lib, oracle_lib, example, goldens, n_ch
         assert got[k]["state"] == (capi.RT_MAPPED if o["mapped"] else capi.RT_FAILED), k
         assert (pool.chunks_used[k], bool(got[k]["ended"])) == (used, ended), k
     mapped = sum(int(want[k][0]["mapped"]) for k in reads)
-    assert mapped >= 0.6 * len(reads), (mapped, len(reads))
+    assert mapped >= min_mapped * len(reads), (mapped, len(reads))
     assert all(reads[k][1].size > pool.chunk_len for k in reads) and any(want[k][1] > 1 for k in reads)     # reads of several chunks
     return mapped, len(reads)
+
+
+# ---- k_rt_events at the edges of a channel's state, and on lanes past 0 (UNC_RT_EVENT_LANES: channels per wavefront)
+
+class _F32Rt:
+    """stands in for a MapPoolOrd's capi.Realtime: the reads' samples are floats already and go through unc_rt_process_chunks_f32"""
+
+    def __init__(self, rt):
+        self.rt, self.params = rt, rt.params
+
+    def tap_channel(self, channel):
+        return self.rt.tap_channel(channel)
+
+    def close(self):
+        self.rt.close()
+
+    def process_chunks(self, chunks, sig):
+        return self.rt.process_chunks_f32(chunks, np.asarray(sig, dtype=np.float32))
+
+
+def early_end_reads(goldens, cut=3000):
+    """reads of 1, 12, 13, 40, 120, 250 and 400 samples (case_events_edge_cases' steps of five samples plus noise), then an ordinary
+    simulated read cut to `cut` samples -> [(int16 samples, calibration)]"""
+    rng = np.random.default_rng(17)
+    cal = (CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION)
+    reads = []
+    for ln in (1, 12, 13, 40, 120, 250, 400):
+        reads.append((np.repeat(rng.integers(330, 680, ln // 5 + 1), 5)[:ln].astype(np.int16) + rng.integers(-6, 7, ln).astype(np.int16), cal))
+    off = goldens["sim_offsets"]
+    return reads + [(goldens["sim_signal"][int(off[0]):int(off[1])][:cut], cal)]
+
+
+def zero_pa_reads(n_parts=400):
+    """{regime: (int16 samples, calibration)}: zero_pa_signal of about 400 runs under the two calibrations with an integer negative offset"""
+    from tests.helpers import REGIMES
+    rng = np.random.default_rng(13)
+    return {name: (zero_pa_signal(REGIMES[name], rng, n_parts), REGIMES[name]) for name in ("promethion", "minion_b")}
+
+
+NOT_NUMBERS = (("nan", np.nan), ("+inf", np.inf), ("-inf", -np.inf))
+
+
+def not_a_number_reads(oracle_lib, goldens, n=3000, at=1500):
+    """{kind: float32 signal}: a simulated read of 3000 samples, calibrated, with one NaN / +inf / -inf at sample 1500; "plain": without"""
+    off = goldens["sim_offsets"]
+    base = oracle_lib.calibrate(goldens["sim_signal"][int(off[1]):int(off[2])][:n], CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION)
+    assert base.size == n
+    sigs = {"plain": base}
+    for kind, v in NOT_NUMBERS:
+        sigs[kind] = base.copy()
+        sigs[kind][at] = v
+    # finite samples whose windows are not: three of 1.5e19 pA and three of -1.5e19.  Each square (2.25e38) is a float, the sum of two
+    # is not, so a window's sum of squares is +inf as a float while the cumulative sums stay finite doubles -- the one operand for which
+    # the three-operation division of k_events.hip gives another answer (NaN) than the division it stands for (inf): tstat()'s `bad`
+    sigs["huge"] = base.copy()
+    sigs["huge"][at:at + 6] = [1.5e19] * 3 + [-1.5e19] * 3
+    return sigs
+
+
+def chunked_reads_against_oracle(lib, oracle_lib, example, params, chunk_len, channels, f32=False, nan_is_nan=False):
+    """The chunked path below the PAF on reads given per channel: channels[ch] = the channel's reads in order, each (int16 samples,
+    calibration) or a float32 signal (then f32 must be set: the float entry takes the samples as they are; with f32 and int16 reads the
+    samples are calibrated here).  After EVERY read the channel's stage tap against its oracle Mapper's after the same read, and
+    every result (PAF columns, work counters, notes, state, chunks used, ENDED) against the oracle's.  One Realtime object, closed
+    at the end.  -> {(channel, i): (oracle hit, oracle tap)}"""
+    from uncalled_amd.realtime import MapPoolOrd
+    po = oracle_lib
+    dev_index = _index(lib, example)
+    oix = po.Index(example["prefix"])
+    p = params if params is not None else capi.default_params(lib)
+    p.chunk_time = chunk_len / p.sample_rate
+    nonsense = (float("nan"), 3.0e38, 0.0)         # the calibration the float entry must ignore
+    want = {}
+    for ch, reads in enumerate(channels):
+        om = po.Mapper(oix, to_oracle_params(p))
+        for i, r in enumerate(reads):
+            sig = r if isinstance(r, np.ndarray) else po.calibrate(r[0], *r[1])
+            assert sig.dtype == np.float32 and (f32 or not isinstance(r, np.ndarray))
+            h, used = om.chunk_read(sig, chunk_len)
+            want[(ch, i)] = (h, used, om.rt_ended(), om.rt_tap())
+    pool = MapPoolOrd(dev_index, n_channels=len(channels), params=p)
+    try:
+        assert pool.chunk_len == chunk_len
+        if f32:
+            pool.rt = _F32Rt(pool.rt)
+        for ch, reads in enumerate(channels):
+            for i, r in enumerate(reads):
+                if f32:     # (past add_read, which takes int16: MapPoolOrd cuts and concatenates whatever the queue holds)
+                    sig = r if isinstance(r, np.ndarray) else po.calibrate(r[0], *r[1])
+                    pool.queues[ch].append((i, sig, nonsense, (ch, i)))
+                else:
+                    pool.add_read(ch, i, r[0], r[1], key=(ch, i))
+        names, ref_names = dev_index.seq_names(), oix.ref_names()
+        got, rounds = {}, 0
+        while pool.running():
+            for key, r in pool.update():
+                got[key] = r
+                h, (o, used, ended, (tb, rb)) = r["hit"], want[key]
+                ta, ra = pool.rt.tap_channel(key[0])
+                assert_rt_taps_equal(ta, ra, tb, rb, "channel %d read %d" % key, nan_is_nan=nan_is_nan)
+                assert int(h["status"]) == 0, key
+                assert capi.hit_paf_cols(h, names) == po.hit_paf_cols(o, ref_names), key
+                for f in ("event_i", "n_nbr", "n_sa", "n_lf", "notes"):
+                    assert int(h[f]) == int(o[f]), (key, f)
+                assert r["state"] == (capi.RT_MAPPED if o["mapped"] else capi.RT_FAILED), key
+                assert (pool.chunks_used[key], bool(r["ended"])) == (used, ended), key
+            rounds += 1
+            assert rounds < 4000
+        assert sorted(got) == sorted(want)
+    finally:
+        pool.rt.close()
+    return {k: (v[0], v[3][0]) for k, v in want.items()}
+
+
+LANES_CHANNELS, LANES_CUT, LANES_CHUNK = 7, 3000, 37
+
+
+def case_rt_event_lanes(lib, oracle_lib, example, goldens, monkeypatch, lanes, f32):
+    """k_rt_events with `lanes` channels per wavefront (UNC_RT_EVENT_LANES, read when the pool is created): seven channels, two reads
+    each cut to 3000 samples, chunks of 37 samples, rounds shuffled and thinned -- wavefronts of 3 + 3 + 1 or 2 + 2 + 2 + 1 channels whose
+    last one is half full in some rounds and not in others, or one wavefront for all; a channel's second read starts (the new_read
+    branch) while its lane neighbours reload their state mid-read; neighbours sit at different phases of the 16-slot ring of sums.
+    Every read's stage tap and result against the oracle, and every RT_RESULT record byte for byte against the same reads with one
+    channel per wavefront.  What the calls carried is checked, so that the case cannot pass on one lane."""
+    p = capi.default_params(lib)
+    p.chunk_time = LANES_CHUNK / p.sample_rate
+    kw = dict(n_channels=LANES_CHANNELS, reads_per_channel=2, shuffle=True, f32=f32, cut=LANES_CUT, params=p, taps=True, min_mapped=0.0)
+    key = ("rt_event_lanes_1", id(lib), f32)
+    if key not in _cache:
+        monkeypatch.setenv("UNC_RT_EVENT_LANES", "1")
+        one = {}
+        case_chunked_per_channel_calibration(lib, oracle_lib, example, goldens, out=one, **kw)
+        _cache[key] = one["results"]
+    monkeypatch.setenv("UNC_RT_EVENT_LANES", str(lanes))
+    out = {}
+    case_chunked_per_channel_calibration(lib, oracle_lib, example, goldens, out=out, **kw)
+    monkeypatch.delenv("UNC_RT_EVENT_LANES")
+    assert out["results"] == _cache[key]
+    sizes = out["call_sizes"]
+    assert max(sizes) >= 2 and len(set(sizes)) > 1, sizes           # several channels in a call, and not always as many
+    if lanes == 3:
+        assert any(n % 3 for n in sizes) and any(n > 3 and n % 3 == 0 for n in sizes), sizes    # a half-full last wavefront comes and goes
+    if lanes == 2:
+        assert any(n % 2 for n in sizes) and any(n % 2 == 0 for n in sizes), sizes
+    assert out["mixed_calls"] > 0                                    # UNC_RT_FIRST chunks beside continuing ones
+    return out
+
+
+def case_rt_event_lanes_refused(lib, example, monkeypatch):
+    """UNC_RT_EVENT_LANES: 1 to 64 or nothing; anything else fails the creation with UNC_ERR_ARG and a message that names the variable"""
+    dev_index = _index(lib, example)
+    for bad in ("0", "65", "-1", "3x", "two", " "):
+        monkeypatch.setenv("UNC_RT_EVENT_LANES", bad)
+        with pytest.raises(capi.UncalledHipError, match="UNC_RT_EVENT_LANES"):
+            capi.Realtime(dev_index, 1)
+    for good in ("", "1", "64"):
+        monkeypatch.setenv("UNC_RT_EVENT_LANES", good)
+        capi.Realtime(dev_index, 1).close()
+    monkeypatch.delenv("UNC_RT_EVENT_LANES")
+
+
+def case_chunked_reads_that_end_early(lib, oracle_lib, example, goldens, monkeypatch, lanes=None):
+    """Reads that end before the profiler's 25-event window fills, or before anything reaches the rolling normaliser (norm.n == 0:
+    scale and shift stay 0; the profiler's queue is never popped), one after the other on ONE channel in chunks of 37 samples, then an
+    ordinary read that inherits what they left: tap after every read and every result against the oracle.  lanes: channels per
+    wavefront (UNC_RT_EVENT_LANES) -- then a second channel runs an ordinary read on the lane beside."""
+    reads = early_end_reads(goldens)
+    channels = [reads]
+    if lanes is not None:
+        monkeypatch.setenv("UNC_RT_EVENT_LANES", str(lanes))
+        off = goldens["sim_offsets"]
+        channels.append([(goldens["sim_signal"][int(off[2]):int(off[3])][:3000], reads[-1][1])])
+    try:
+        want = chunked_reads_against_oracle(lib, oracle_lib, example, None, 37, channels)
+    finally:
+        if lanes is not None:
+            monkeypatch.delenv("UNC_RT_EVENT_LANES")
+    early_end_premises([want[(0, i)][1] for i in range(len(reads))])
+
+
+def early_end_premises(taps):
+    """what the reads of early_end_reads must be for the oracle, or the case tests nothing: taps = the oracle's after each of them"""
+    short = taps[:-1]
+    assert sum(int(t["prof_n"]) < 25 and int(t["norm_n"]) == 0 for t in short) >= 3, [(int(t["prof_n"]), int(t["norm_n"])) for t in short]
+    assert any(int(t["prof_n"]) == 25 for t in short), [int(t["prof_n"]) for t in short]
+    assert int(taps[-1]["norm_n"]) > 25, int(taps[-1]["norm_n"])
+
+
+ZERO_PA_CHUNKED = [(wide, chunk_len, f32) for wide in (False, True) for chunk_len in (37, 4000) for f32 in (False, True)]
+
+
+def case_chunked_zero_pa_windows(lib, oracle_lib, example, wide, chunk_len, f32):
+    """case_zero_pa_windows' signal, lengthened, through the chunked path: t-statistic windows whose sums are exactly zero, negative, or
+    of mixed sign send tstat() of k_rt_events to the division itself (`bad` -> tstat_ring<W, false>), as k_events' blocks are sent there.
+    Two channels, one per calibration; default mean bounds (most of these events are dropped before the profiler) and none; chunks of
+    37 and of 4000 samples; the int16 entry and the float entry.  Taps and results against the oracle."""
+    po = oracle_lib
+    reads = zero_pa_reads()
+    p = _wide_bounds(lib) if wide else capi.default_params(lib)
+    want = chunked_reads_against_oracle(lib, po, example, p, chunk_len, [[reads[name]] for name in reads], f32=f32)
+    for ch, name in enumerate(reads):
+        raw, cal = reads[name]
+        zero_pa_premises(po, lib, raw, cal, name)
+        tap = want[(ch, 0)][1]
+        if not wide:       # events were detected and dropped for their means before the profiler saw them
+            assert int(tap["det_total_events"]) > int(tap["norm_n"]) + 25, (name, int(tap["det_total_events"]), int(tap["norm_n"]))
+
+
+def zero_pa_premises(po, lib, raw, cal, name):
+    ev = po.detect_events(po.calibrate(raw, *cal), to_oracle_params(_wide_bounds(lib)))[0]
+    assert (ev["mean"] == 0).any() and (ev["mean"] < 0).any(), name
+
+
+def case_chunked_samples_that_are_no_numbers(lib, oracle_lib, example, goldens):
+    """The float entry takes samples as they are: one NaN, +inf or -inf at sample 1500 of a 3000-sample read in chunks of 400 -- the
+    sums of the detector's ring are no numbers from there on (inf - inf for the infinities), no t-statistic compares true, no event
+    closes, and the read, which maps within 2000 samples when it is left alone, is given all its chunks and fails.  Each kind first on
+    a fresh channel (channels 0 to 2), where a plain read follows and starts from the state the poisoned one left, and behind a read
+    that mapped (channels 3 to 5).  Channels 6 and 7: the same with six finite samples of +-1.5e19 pA, whose windows' sums of squares
+    are infinite as floats (not_a_number_reads).  Taps and results against the oracle; NaN against NaN where both hold one."""
+    sigs = not_a_number_reads(oracle_lib, goldens)
+    channels = [[sigs[kind], sigs["plain"]] for kind, _ in NOT_NUMBERS] + [[sigs["plain"], sigs[kind]] for kind, _ in NOT_NUMBERS]
+    channels += [[sigs["huge"], sigs["plain"]], [sigs["plain"], sigs["huge"]]]
+    want = chunked_reads_against_oracle(lib, oracle_lib, example, None, 400, channels, f32=True, nan_is_nan=True)
+    plain = want[(3, 0)][1]
+    for ch in range(3):        # the poisoned read went on to its end (8 chunks' samples), and closed fewer events than the plain one
+        tap = want[(ch, 0)][1]
+        assert int(tap["det_t"]) == 3001 and int(tap["det_total_events"]) < int(plain["det_total_events"]), (ch, tap)
+
+
+def ring_wrap_reads(goldens):
+    """[(int16 samples, calibration)]: zero_pa_signal of 5200 runs -- under mean bounds that drop nothing more than 6000 of its events
+    reach the rolling normaliser, whose ring of 6000 wraps -- and behind it the reads of early_end_reads"""
+    from tests.helpers import REGIMES
+    cal = REGIMES["promethion"]
+    return [(zero_pa_signal(cal, np.random.default_rng(19), 5200), cal)] + early_end_reads(goldens)
+
+
+def ring_wrap_premises(taps):
+    """the oracle's taps after the reads of ring_wrap_reads: the ring is full and has wrapped after the first, and stays where it is
+    through the reads that push nothing"""
+    assert int(taps[0]["norm_n"]) == 6000 and int(taps[0]["det_total_events"]) > 6500 and 0 < int(taps[0]["norm_wr"]) < 3000, taps[0]
+    assert sum(int(t["norm_wr"]) == int(taps[0]["norm_wr"]) for t in taps[1:]) >= 3, [int(t["norm_wr"]) for t in taps]
+
+
+def case_chunked_ring_wraps_then_short_reads(lib, oracle_lib, example, goldens):
+    """One read that pushes more events than the rolling normaliser's ring holds (the write position passes the place the read pointer
+    was left at: roll_skip_unread at every chunk's start is what keeps the ring from counting as full), through the float entry in
+    chunks of 4000 samples; then the reads that end early, whose scale and shift come from a full ring they add nothing to."""
+    want = chunked_reads_against_oracle(lib, oracle_lib, example, _wide_bounds(lib), 4000, [ring_wrap_reads(goldens)], f32=True)
+    ring_wrap_premises([want[k][1] for k in sorted(want)])
 
 
 # ---------------------------------------------------------------- the FM layer (fm_dev.h, k_taps.hip) against tests/fm_naive.py

@@ -330,6 +330,36 @@ def test_chunked_512_channels_per_channel_calibration(hip_lib, oracle_lib, examp
     print(f"512 channels: {mapped} of {n} reads mapped")
 
 
+@pytest.mark.parametrize("f32", [False, True])
+@pytest.mark.parametrize("lanes", [2, 3, 64])
+def test_rt_event_lanes(hip_lib, oracle_lib, example, goldens, monkeypatch, lanes, f32):
+    """k_rt_events with 2, 3 and 64 channels per wavefront: everything in it that depends on the lane, which calls of at most 2048
+    chunks never run past lane 0"""
+    pc.case_rt_event_lanes(hip_lib, oracle_lib, example, goldens, monkeypatch, lanes, f32)
+
+
+def test_rt_event_lanes_refused(hip_lib, example, monkeypatch):
+    pc.case_rt_event_lanes_refused(hip_lib, example, monkeypatch)
+
+
+@pytest.mark.parametrize("lanes", [None, 64])
+def test_chunked_reads_that_end_early(hip_lib, oracle_lib, example, goldens, monkeypatch, lanes):
+    pc.case_chunked_reads_that_end_early(hip_lib, oracle_lib, example, goldens, monkeypatch, lanes)
+
+
+@pytest.mark.parametrize("wide,chunk_len,f32", pc.ZERO_PA_CHUNKED)
+def test_chunked_zero_pa_windows(hip_lib, oracle_lib, example, wide, chunk_len, f32):
+    pc.case_chunked_zero_pa_windows(hip_lib, oracle_lib, example, wide, chunk_len, f32)
+
+
+def test_chunked_samples_that_are_no_numbers(hip_lib, oracle_lib, example, goldens):
+    pc.case_chunked_samples_that_are_no_numbers(hip_lib, oracle_lib, example, goldens)
+
+
+def test_chunked_ring_wraps_then_short_reads(hip_lib, oracle_lib, example, goldens):
+    pc.case_chunked_ring_wraps_then_short_reads(hip_lib, oracle_lib, example, goldens)
+
+
 def test_staging_buffers_reused_after_begin(hip_lib, oracle_lib, example, goldens):
     """`offsets` and `calib` are copied by unc_map_batch_begin (include/uncalled_hip.h): in page-locked memory (unc_host_alloc), begun on
     a stream with another mapper's batch queued ahead, and overwritten -- other calibrations, read boundaries moved by a few samples --

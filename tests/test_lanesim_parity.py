@@ -296,3 +296,33 @@ def test_chunked_per_channel_calibration(sim_lib, oracle_lib, example, goldens, 
 def test_chunked_per_channel_calibration_many_channels(sim_lib, oracle_lib, example, goldens):
     """the 512-channel case of the GPU suite on 20 channels (reads cut to 6000 samples), rounds shuffled"""
     pc.case_chunked_per_channel_calibration(sim_lib, oracle_lib, example, goldens, n_channels=20, reads_per_channel=2, shuffle=True, cut=6000)
+
+
+@pytest.mark.parametrize("f32", [False, True])
+@pytest.mark.parametrize("lanes", [2, 3, 64])
+def test_rt_event_lanes(sim_lib, oracle_lib, example, goldens, monkeypatch, lanes, f32):
+    """k_rt_events with 2, 3 and 64 channels per wavefront: everything in it that depends on the lane, which calls of at most 2048
+    chunks never run past lane 0"""
+    pc.case_rt_event_lanes(sim_lib, oracle_lib, example, goldens, monkeypatch, lanes, f32)
+
+
+def test_rt_event_lanes_refused(sim_lib, example, monkeypatch):
+    pc.case_rt_event_lanes_refused(sim_lib, example, monkeypatch)
+
+
+@pytest.mark.parametrize("lanes", [None, 64])
+def test_chunked_reads_that_end_early(sim_lib, oracle_lib, example, goldens, monkeypatch, lanes):
+    pc.case_chunked_reads_that_end_early(sim_lib, oracle_lib, example, goldens, monkeypatch, lanes)
+
+
+@pytest.mark.parametrize("wide,chunk_len,f32", pc.ZERO_PA_CHUNKED)
+def test_chunked_zero_pa_windows(sim_lib, oracle_lib, example, wide, chunk_len, f32):
+    pc.case_chunked_zero_pa_windows(sim_lib, oracle_lib, example, wide, chunk_len, f32)
+
+
+def test_chunked_samples_that_are_no_numbers(sim_lib, oracle_lib, example, goldens):
+    pc.case_chunked_samples_that_are_no_numbers(sim_lib, oracle_lib, example, goldens)
+
+
+def test_chunked_ring_wraps_then_short_reads(sim_lib, oracle_lib, example, goldens):
+    pc.case_chunked_ring_wraps_then_short_reads(sim_lib, oracle_lib, example, goldens)

@@ -275,6 +275,88 @@ def test_chunked_stage_tap_equals_live_reference(oracle_lib, ref_lib, example, g
     assert int(a["norm_n"]) == 6000
 
 
+def _channel_equals_live_reference(po, pr, ix, sigs, chunk_len, params=None, nan_is_nan=False, what=""):
+    """one oracle Mapper and one of the reference's, the same reads chunk by chunk on both: after every read the PAF columns, the work
+    counters, the chunks used, Paf::ENDED and the stage tap (pr.set_params is the caller's) -> the oracle's taps"""
+    from tests.parity_cases import assert_rt_taps_equal
+    om, rm = po.Mapper(ix, params), pr.Mapper()
+    taps = []
+    for i, sig in enumerate(sigs):
+        (h, hu), (r, ru) = om.chunk_read(sig, chunk_len), rm.chunk_read(sig, chunk_len, i)
+        assert po.hit_paf_cols(h, ix.ref_names()) == r.paf_cols(), (what, i)
+        assert (hu, int(h["event_i"]), int(h["n_nbr"]), int(h["n_sa"]), int(h["n_lf"])) == (ru, r.event_i, r.n_nbr, r.n_sa, r.n_lf), (what, i)
+        assert om.rt_ended() == bool(pr.lib().ref_last_ended()), (what, i)
+        (a, ra), (b, rb) = om.rt_tap(), rm.rt_tap()
+        assert_rt_taps_equal(a, ra, b, rb, "%s read %d" % (what, i), nan_is_nan=nan_is_nan)
+        taps.append(a)
+    return taps
+
+
+def test_chunked_reads_that_end_early_equal_live_reference(oracle_lib, ref_lib, example, goldens):
+    """The reads of parity_cases.case_chunked_reads_that_end_early (1 to 400 samples in chunks of 37, then an ordinary one, on one
+    Mapper): reads that end before the EventProfiler's window fills or before anything reaches the Normalizer, and what the next
+    read inherits -- the oracle's taps and answers are the reference's."""
+    from tests.parity_cases import early_end_premises, early_end_reads
+    po, pr = oracle_lib, ref_lib
+    pr.init(example["prefix"])
+    sigs = [po.calibrate(raw, *cal) for raw, cal in early_end_reads(goldens)]
+    early_end_premises(_channel_equals_live_reference(po, pr, po.Index(example["prefix"]), sigs, 37, what="early end"))
+
+
+@pytest.mark.parametrize("wide", [False, True])
+def test_chunked_zero_pa_windows_equal_live_reference(oracle_lib, ref_lib, example, wide):
+    """The signals of parity_cases.case_chunked_zero_pa_windows (t-statistic windows whose sums are zero or negative) through the
+    reference's chunk path, default mean bounds and none, chunks of 37 and of 4000 samples."""
+    from tests.parity_cases import zero_pa_reads
+    po, pr = oracle_lib, ref_lib
+    pr.init(example["prefix"])
+    p = po.default_params()
+    if wide:
+        p.min_mean, p.max_mean = -3.0e38, 3.0e38
+    ix = po.Index(example["prefix"])
+    try:
+        pr.set_params(p)
+        for name, (raw, cal) in zero_pa_reads().items():
+            for chunk_len in (37, 4000):
+                tap, = _channel_equals_live_reference(po, pr, ix, [po.calibrate(raw, *cal)], chunk_len, p, what="%s %d" % (name, chunk_len))
+                assert int(tap["det_total_events"]) > 400 and (wide or int(tap["det_total_events"]) > int(tap["norm_n"]) + 25), (name, tap)
+    finally:
+        pr.set_params(po.default_params())
+
+
+def test_chunked_samples_that_are_no_numbers_equal_live_reference(oracle_lib, ref_lib, example, goldens):
+    """A NaN, +inf or -inf at sample 1500 of a 3000-sample read in chunks of 400 (parity_cases.case_chunked_samples_that_are_no_numbers):
+    on a fresh Mapper with a plain read behind it, and behind a plain read.  Where the oracle and the reference disagreed here the
+    oracle would be the one to change: the device follows the reference."""
+    from tests.parity_cases import NOT_NUMBERS, not_a_number_reads
+    po, pr = oracle_lib, ref_lib
+    pr.init(example["prefix"])
+    ix = po.Index(example["prefix"])
+    sigs = not_a_number_reads(po, goldens)
+    for kind, _ in NOT_NUMBERS:
+        for order in ((kind, "plain"), ("plain", kind)):
+            taps = _channel_equals_live_reference(po, pr, ix, [sigs[k] for k in order], 400, nan_is_nan=True, what="%s, %s" % order)
+            assert int(taps[order.index(kind)]["det_t"]) == 3001       # the poisoned read is given every chunk: it never maps
+    for order in (("huge", "plain"), ("plain", "huge")):
+        _channel_equals_live_reference(po, pr, ix, [sigs[k] for k in order], 400, nan_is_nan=True, what="%s, %s" % order)
+
+
+def test_chunked_ring_wraps_then_short_reads_equal_live_reference(oracle_lib, ref_lib, example, goldens):
+    """parity_cases.case_chunked_ring_wraps_then_short_reads: one read that wraps the Normalizer's ring of 6000, then reads that push
+    nothing, on one Mapper without mean bounds."""
+    from tests.parity_cases import ring_wrap_premises, ring_wrap_reads
+    po, pr = oracle_lib, ref_lib
+    pr.init(example["prefix"])
+    p = po.default_params()
+    p.min_mean, p.max_mean = -3.0e38, 3.0e38
+    try:
+        pr.set_params(p)
+        sigs = [po.calibrate(raw, *cal) for raw, cal in ring_wrap_reads(goldens)]
+        ring_wrap_premises(_channel_equals_live_reference(po, pr, po.Index(example["prefix"]), sigs, 4000, p, what="ring wrap"))
+    finally:
+        pr.set_params(po.default_params())
+
+
 def test_chunked_flags_carry_over_equals_live_reference(oracle_lib, tmp_path):
     """sources_added_ survives Mapper::new_read: with a small max_paths the reads of one channel influence each other.  The
     oracle against the reference on the scenario where that changes the work counters (tests/parity_cases.py carry_over_data).

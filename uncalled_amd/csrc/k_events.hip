@@ -504,9 +504,10 @@ __global__ __launch_bounds__(64) void k_rt_events(const int16_t *raw, const floa
 #include "unc_kernels.h"
 namespace unc {
 void launch_rt_events(const int16_t *raw, const float *raw_pa, const RtChunkDesc *chunks, uint32_t n_chunks, RtChan *chans, float *norm_ring,
-                      const unc_params_t &P, float tgt_mean, float tgt_stdv, unc_evt_info_t *info, uint32_t *ring0_out, hipStream_t st) {
-    // as few channels per wavefront as a grid of 2048 wavefronts allows (512 channels: one each)
-    uint32_t lpw = (n_chunks + 2047u) / 2048u;
+                      const unc_params_t &P, float tgt_mean, float tgt_stdv, unc_evt_info_t *info, uint32_t *ring0_out, hipStream_t st,
+                      uint32_t lanes_per_wave) {
+    // as few channels per wavefront as a grid of 2048 wavefronts allows (512 channels: one each), unless the caller names a number
+    uint32_t lpw = lanes_per_wave ? lanes_per_wave : (n_chunks + 2047u) / 2048u;
     if (lpw < 1u) lpw = 1u;
     if (lpw > (uint32_t)WAVE) lpw = WAVE;
     hipLaunchKernelGGL(k_rt_events, dim3((n_chunks + lpw - 1) / lpw), dim3(WAVE), 0, st, raw, raw_pa, chunks, n_chunks, chans, norm_ring, P,

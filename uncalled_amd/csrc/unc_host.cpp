@@ -1757,6 +1757,7 @@ struct unc_rt {
     unc_params_t P;
     uint32_t n_channels = 0;
     uint32_t team = 8;            // wavefronts per channel in k_map (UNC_RT_TEAM)
+    uint32_t event_lanes = 0;     // channels per wavefront in k_rt_events (UNC_RT_EVENT_LANES), 0 = launch_rt_events' own rule
     Scratch sc;
     Pool pool;                    // nodes of the channels' seed-cluster grids (a channel keeps its chunks until its read is decided)
     DevBuf<RtChan> d_chans;
@@ -1820,6 +1821,19 @@ static uint32_t rt_team_size() {
 #endif
     const long v = e ? atol(e) : 8;
     return v >= 8 ? 8u : v >= 4 ? 4u : v >= 2 ? 2u : 1u;
+}
+
+// channels per wavefront of k_rt_events: launch_rt_events' own rule (0) unless UNC_RT_EVENT_LANES names 1 .. 64.  One channel per
+// wavefront is what a flow cell's 512 channels get; the variable puts several on one at the sizes of a test
+static int rt_event_lanes(uint32_t *out) {
+    const char *e = getenv("UNC_RT_EVENT_LANES");
+    *out = 0;
+    if (!e || !e[0]) return UNC_OK;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (*end || v < 1 || v > (long)WAVE) return fail(UNC_ERR_ARG, "UNC_RT_EVENT_LANES=%s: 1 to %d channels per wavefront, or unset", e, (int)WAVE);
+    *out = (uint32_t)v;
+    return UNC_OK;
 }
 
 // The channels' node pool: 16 chunks (12 288 nodes) per channel on average, 64 on references of 2^26 rows and more (a read there
@@ -1891,12 +1905,15 @@ extern "C" int unc_rt_create(const unc_index_t *ix, const unc_params_t *p, uint3
     if (!(p->chunk_time > 0.0f) || !(p->sample_rate > 0.0f) || (double)p->chunk_time * (double)p->sample_rate > 2.0 * (double)NORM_LEN)
         return fail(UNC_ERR_ARG, "chunk_time * sample_rate = %.0f samples: chunks of more than %u samples are not supported (mapper.cpp:336-351, "
                                  "the #SKIP branch of the reference, is out of scope)", (double)p->chunk_time * (double)p->sample_rate, 2u * NORM_LEN);
+    uint32_t event_lanes = 0;
+    if (int rc = rt_event_lanes(&event_lanes)) return rc;
     HIPCHK(hipSetDevice(ix->device));
     unc_rt *rt = new unc_rt();
     struct Guard { unc_rt *p; ~Guard() { if (p) unc_rt_free(p); } } guard{rt};
     rt->ix = ix; rt->P = *p; rt->n_channels = n_channels;
     { const char *e = getenv("UNC_RT_PROFILE"); rt->profile = e && e[0] == '1'; }
     rt->team = rt_team_size();
+    rt->event_lanes = event_lanes;
     size_t bytes = 0;
     if (int rc = alloc_rt_slots_and_pool(rt, rt_sizes(*p, ix->dev, n_channels), &bytes)) return rc;
     if (int rc = alloc_rt_arrays(rt, &bytes)) return rc;
@@ -2022,7 +2039,7 @@ static int rt_launch(unc_rt *rt, const RtPlan &plan, const int16_t *raw, const f
     HIPCHK(hipMemcpyAsync(rt->d_moff.p, plan.moff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     HIPCHK(rt->ev.record(0, st));
     launch_rt_events(d_raw, d_pa, rt->d_desc.p, n, rt->d_chans.p, rt->d_ring.p, rt->P, rt->ix->model_mean, rt->ix->model_stdv, rt->d_info.p,
-                     rt->d_ring0.p, st);
+                     rt->d_ring0.p, st, rt->event_lanes);
     HIPCHK(rt->ev.record(1, st));
     MapArgs a = map_args(rt->ix, rt->P, rt->sc.v, rt->pool.v, rt_reads(rt, n), rt->d_results.p, rt->d_next.p);
     a.resume = 1; a.slot_map = rt->d_slotmap.p;      // block b goes on with the read of channel slot_map[b], from the channel's ring

@@ -9,7 +9,8 @@ void launch_events(const DevReads &rd, const unc_params_t &P, hipStream_t st, ui
 // the variant that also writes every kept event whole (mean, stdv, start, length) to events[moff[r] ..]: the alignment path's, for segments
 void launch_events_full(const DevReads &rd, const unc_params_t &P, unc_event_t *events, hipStream_t st, uint32_t reads_per_wave = 0);
 void launch_rt_events(const int16_t *raw, const float *raw_pa, const RtChunkDesc *chunks, uint32_t n_chunks, RtChan *chans, float *norm_ring,
-                      const unc_params_t &P, float tgt_mean, float tgt_stdv, unc_evt_info_t *info, uint32_t *ring0_out, hipStream_t st);
+                      const unc_params_t &P, float tgt_mean, float tgt_stdv, unc_evt_info_t *info, uint32_t *ring0_out, hipStream_t st,
+                      uint32_t lanes_per_wave = 0);      // 0: as few channels per wavefront as a grid of 2048 wavefronts allows
 void launch_map(const MapArgs &a, uint32_t grid, hipStream_t st, bool profile = false, uint32_t team = 1);   // team: chunked path only, wavefronts per channel
 void launch_sched_init(const DevSched &S, hipStream_t st);
 void launch_xcd_probe(uint32_t *out, uint32_t n_blocks, hipStream_t st);
