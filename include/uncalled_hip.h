@@ -807,6 +807,49 @@ int unc_pileup_stats(const unc_pileup_t *pu, const unc_model_t *model, uint64_t 
 typedef struct { uint64_t n_a, n_b; double mean_a, mean_b, sd_a, sd_b, se2, t; } unc_pileup_cmp_t;
 int unc_pileup_compare(const unc_pileup_t *a, const unc_pileup_t *b, uint64_t n, const uint64_t *bins, unc_pileup_cmp_t *out);
 
+/* ---- level histograms of a pile-up and the two-sample Kolmogorov-Smirnov distance.  A modified base often widens or splits a
+ * position's level distribution while its mean barely moves; three moments cannot show that.  A pile-up can carry a second table: 64
+ * buckets of uint32_t for every bin (256 bytes a bin beside the 40, and 8 for the bin's centre), attached to an EMPTY pile-up by
+ * unc_pileup_hist_enable.  Histograms are meant for REGIONS: a whole bacterial genome's are gigabytes, and a table of 2^30 bins or more
+ * is refused outright.  unc_pileup_create and its flags are as they were, and a pile-up without a histogram behaves bit for bit as before
+ * in every entry point.
+ * Width and centres: w = llrint((double)width * 2^20), 1 <= w <= 2^31, is the bucket width in the fixed point of q; a bin's centre is
+ * c = llrint((double)model_mean(kmer) * 2^20), kmer the 5-mer unc_pileup_stats reports for the bin (the forward 5-mer at the bin's
+ * position, reverse-complemented for the minus strand; model NULL: the r9.4 template).  The centres are written once, when the
+ * histogram is attached, by a kernel that reads the packed reference on the device; the host keeps w and the model's 1024 centres.
+ * Bucket rule: a record that reaches n_added lands in exactly one bucket of its bin: with t = q - c + 32 * w (signed, 64 bits) bucket
+ * t < 0 ? 0 : min(t / w, 63).  Bucket 32 begins at the centre, buckets 0 and 63 take everything beyond.  Records that are shared and
+ * skipped, dropped or outside touch no bucket.  For every bin the sum of its 64 buckets equals its n, as long as n < 2^32 (a bucket
+ * wraps modulo 2^32).  All integers: like the table, the histograms do not depend on the records' order, the calls or the rounds.
+ * unc_pileup_add and unc_align_pileup_call feed the histogram of a pile-up that has one (k_pileup_hist_accum, a launch behind every
+ * k_pileup_accum over the same records, inside the span unc_pileup_last_timing reports); unc_pileup_reset zeroes it and keeps it
+ * attached (with its centres); unc_pileup_device_bytes includes it; unc_pileup_merge adds it too, and refuses with UNC_ERR_ARG, both
+ * pile-ups unchanged, when one side has a histogram and the other none, or when w or the 1024 centres differ.
+ * unc_pileup_hist_enable: UNC_ERR_ARG, before anything on the device is allocated or written, when the pile-up holds records
+ * (n_added, n_dropped or n_outside is not 0), when it has a histogram already, when width is not finite or w is out of range, or when
+ * one of the model's 1024 means is not finite or has |mean| >= 2048.  UNC_ERR_NOMEM when the table does not fit; the pile-up is then
+ * as it was, without a histogram. */
+int unc_pileup_hist_enable(unc_pileup_t *pu, const unc_model_t *model, float width);
+/* the 64 buckets of n listed bins, gathered on the device: out_counts[64 i ..]; and their centres c.  UNC_ERR_ARG for a pile-up without
+ * a histogram and for a bin that does not exist */
+int unc_pileup_hist_gather(const unc_pileup_t *pu, uint64_t n, const uint64_t *bins, uint32_t *out_counts);
+int unc_pileup_hist_centres(const unc_pileup_t *pu, uint64_t n, const uint64_t *bins, int64_t *out_q);
+/* The two-sample Kolmogorov-Smirnov distance of two pile-ups' histograms over listed bins, on the device (k_pileup_ks: a wavefront a
+ * bin, a lane a bucket), exact.  With A(k), B(k) the counts of buckets 0 .. k of the bin in a and b, n_a = A(63), n_b = B(63):
+ *   num = max over k of |A(k) * n_b - B(k) * n_a|   (unsigned 64-bit products; neither can overflow below)
+ *   bucket = the lowest k that attains it;  sign = +1 if A(k) * n_b > B(k) * n_a there, -1 if it is less, 0 if num == 0
+ * and on the host in double, one rounding per written operation:
+ *   d = (double)num / ((double)n_a * (double)n_b)        ks = d * sqrt(((double)n_a * (double)n_b) / ((double)n_a + (double)n_b))
+ * d is the distance of the two empirical distributions at bucket resolution, ks the statistic scaled by the effective sample size.  No
+ * p-values, for unc_pileup_compare's reason.  A bin may be listed twice; a and b may be the same object (num == 0 everywhere).
+ * UNC_ERR_ARG, and then out is untouched: either pile-up has no histogram; the regions, the device, w or the centres differ; a listed
+ * bin does not exist; a listed bin has n_a == 0, n_b == 0 or an n >= 2^32 (n read from the pile-up's own word: a bucket may have
+ * wrapped). */
+typedef struct { uint64_t n_a, n_b, num; uint32_t bucket; int32_t sign; double d, ks; } unc_pileup_ks_t;   /* 48 bytes */
+int unc_pileup_ks(const unc_pileup_t *a, const unc_pileup_t *b, uint64_t n, const uint64_t *bins, unc_pileup_ks_t *out);
+/* kernel milliseconds of k_pileup_ks in the calling thread's last unc_pileup_ks (HIP events on the stream) */
+int unc_pileup_ks_last_timing(float *ms);
+
 /* ---- repeat masking: replaces masking/mask_internal.sh + masking/mask_kmers.py (jellyfish) and masking/mask_external.sh (bowtie,
  * bedtools, samtools), which the reference's masking/README.md recommends for references with intergenic eukaryotic DNA.
  * A reference is one byte per base: 0..3 = A C G T (either case), everything else 4 = "not a base"; a masked base becomes 4.

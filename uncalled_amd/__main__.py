@@ -536,6 +536,7 @@ def _adaptive(args):
 
 PILEUP_COLUMNS = ("contig", "pos", "strand", "kmer", "cov", "mean", "stdv", "dwell", "model_mean", "model_stdv", "z")
 PILEUP_CONTROL_COLUMNS = ("ctl_cov", "ctl_mean", "ctl_stdv", "t")
+PILEUP_KS_COLUMNS = ("ks_d", "ks", "ks_bucket")
 
 
 def parse_region(text, names, index):
@@ -564,9 +565,10 @@ def pileup_fill(unc, index, prefix, refseq, pileup, fast5, paf, model, args):
     return done
 
 
-def write_pileup(out, names, pileup, control, min_cov, model):
-    """one line per covered bin, by bin index; floats as %.17g, which names a double exactly"""
-    out.write("\t".join(PILEUP_COLUMNS + (PILEUP_CONTROL_COLUMNS if control is not None else ())) + "\n")
+def write_pileup(out, names, pileup, control, min_cov, model, ks=False):
+    """one line per covered bin, by bin index; floats as %.17g, which names a double exactly.  ks: both pile-ups carry histograms, and
+    three columns more give their Kolmogorov-Smirnov distance (every covered bin holds min_cov >= 1 records in both)"""
+    out.write("\t".join(PILEUP_COLUMNS + (PILEUP_CONTROL_COLUMNS if control is not None else ()) + (PILEUP_KS_COLUMNS if ks else ())) + "\n")
     bins = pileup.covered(min_cov, other=control)
     rid, pos, fwd = pileup.locate(bins)
     st = pileup.stats(bins, model)
@@ -575,12 +577,15 @@ def write_pileup(out, names, pileup, control, min_cov, model):
     if control is not None:       # Welch's t needs two records on either side
         both = [i for i in range(len(bins)) if st["n"][i] >= 2 and cs["n"][i] >= 2]
         t = dict(zip(both, pileup.compare(control, bins[both])["t"])) if both else {}
+    kd = pileup.ks(control, bins) if ks else None
     for i in range(len(bins)):
         line = "%s\t%d\t%s\t%s\t%d\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g" % (
             names[int(rid[i])], int(pos[i]), "+" if fwd[i] else "-", kmer_str(st["kmer"][i]), int(st["n"][i]), st["mean"][i], st["sd"][i],
             st["dwell"][i], st["model_mean"][i], st["model_stdv"][i], st["z"][i])
         if control is not None:
             line += "\t%d\t%.17g\t%.17g\t%.17g" % (int(cs["n"][i]), cs["mean"][i], cs["sd"][i], t.get(i, float("nan")))
+        if ks:
+            line += "\t%.17g\t%.17g\t%d" % (kd["d"][i], kd["ks"][i], int(kd["bucket"][i]))
         out.write(line + "\n")
     return len(bins)
 
@@ -597,6 +602,9 @@ def pileup_cmd(args):
     if min_cov < 1:
         sys.stderr.write("Error: --min-cov must be at least 1\n")
         sys.exit(1)
+    if args.ks and not args.control:
+        sys.stderr.write("Error: --ks compares two samples: it needs --control\n")
+        sys.exit(1)
     index = capi.Index(args.index_prefix, device=args.device)
     names = index.seq_names()
     regions = [parse_region(r, names, index) for r in args.region] if args.region else None
@@ -607,11 +615,13 @@ def pileup_cmd(args):
     for pu, (fast5, paf), what in ((pileup, (args.fast5, args.paf), "sample"), (control, args.control or (None, None), "control")):
         if pu is None:
             continue
+        if args.ks:
+            pu.enable_hist(args.ks_width, model)
         done = pileup_fill(unc, index, args.index_prefix, refseq, pu, fast5, paf, model, args)
         sys.stderr.write("%s: %d alignments, %d records added, %d dropped, %d outside the regions\n" % (
             (what, done) + tuple(pu.counters()[i] for i in (2, 0, 1))))
     with open(args.out, "w") as out:
-        n = write_pileup(out, names, pileup, control, min_cov, model)
+        n = write_pileup(out, names, pileup, control, min_cov, model, args.ks)
     sys.stderr.write("%d bins with at least %d records written to %s\n" % (n, min_cov, args.out))
 
 
@@ -788,12 +798,19 @@ def get_parser():
                       "the result does not depend on the order or the batching). One line per position and strand with at least MIN_COV "
                       "records: contig, pos, strand, kmer, cov, mean, stdv, dwell (samples), the model's mean and stdv for the k-mer, and "
                       "z = (mean - model_mean) / model_stdv * sqrt(cov). With --control: positions covered in both samples, the control's "
-                      "cov, mean, stdv, and Welch's t of the two means (nan where either sample has fewer than two records there). Floats are printed as %.17g.")
+                      "cov, mean, stdv, and Welch's t of the two means (nan where either sample has fewer than two records there). With --ks as well: "
+                      "ks_d, the two-sample Kolmogorov-Smirnov distance of the two samples' level histograms at the position (64 buckets of "
+                      "KS_WIDTH levels, bucket 32 beginning at the model's mean), ks = ks_d * sqrt(cov * ctl_cov / (cov + ctl_cov)), and "
+                      "ks_bucket, the bucket where the two cumulative distributions lie furthest apart. Floats are printed as %.17g.")
     p.add_argument("index_prefix", type=str, help="BWA prefix of the reference (needs the .pac)")
     p.add_argument("fast5", type=str, help="fast5 file that holds the reads")
     p.add_argument("paf", type=str, help="PAF file, such as `map` writes")
     p.add_argument("-o", "--out", type=str, required=True, help="The TSV file to write")
     p.add_argument("--control", nargs=2, metavar=("FAST5", "PAF"), default=None, help="A second sample to compare with")
+    p.add_argument("--ks", action="store_true", help="With --control: level histograms for both samples (256 bytes of GPU memory more per "
+                   "position and strand: use --region) and three columns ks_d, ks, ks_bucket")
+    p.add_argument("--ks-width", type=float, default=0.25, metavar="W", help="Width of a histogram bucket in normalised levels (default 0.25: "
+                   "the 64 buckets span the model's mean -8 .. +8; the default is a choice that nobody has measured against data)")
     p.add_argument("--region", action="append", default=None, metavar="NAME:ST-EN", help="Pile up only inside these bases of the reference "
                    "(repeatable; regions may not overlap; default: every sequence, whole -- 80 bytes of GPU memory per base)")
     p.add_argument("--min-cov", type=int, default=None, help="Records a position needs to be written (default 1, with --control 2)")

@@ -171,6 +171,9 @@ PILEUP_STAT = np.dtype([("n", "<u8"), ("mean", "<f8"), ("sd", "<f8"), ("dwell", 
 PILEUP_CMP = np.dtype([("n_a", "<u8"), ("n_b", "<u8"), ("mean_a", "<f8"), ("mean_b", "<f8"), ("sd_a", "<f8"), ("sd_b", "<f8"), ("se2", "<f8"),
                        ("t", "<f8")])
 PILEUP_WORDS = np.dtype([("n", "<u8"), ("S", "<i8"), ("SS_lo", "<u8"), ("SS_hi", "<u8"), ("D", "<u8")])
+# unc_pileup_ks_t; the buckets of a bin's histogram
+PILEUP_KS = np.dtype([("n_a", "<u8"), ("n_b", "<u8"), ("num", "<u8"), ("bucket", "<u4"), ("sign", "<i4"), ("d", "<f8"), ("ks", "<f8")])
+PILEUP_HIST_BUCKETS = 64
 
 
 class AlignCall(C.Structure):
@@ -338,6 +341,12 @@ def load(path=None):
         L.unc_pileup_merge.argtypes = [vp, vp]
         L.unc_pileup_stats.argtypes = [vp, vp, u64, vp, vp]
         L.unc_pileup_compare.argtypes = [vp, vp, u64, vp, vp]
+    if hasattr(L, "unc_pileup_hist_enable"):
+        L.unc_pileup_hist_enable.argtypes = [vp, vp, C.c_float]
+        L.unc_pileup_hist_gather.argtypes = [vp, u64, vp, vp]
+        L.unc_pileup_hist_centres.argtypes = [vp, u64, vp, vp]
+        L.unc_pileup_ks.argtypes = [vp, vp, u64, vp, vp]
+        L.unc_pileup_ks_last_timing.argtypes = [C.POINTER(C.c_float)]
     if hasattr(L, "unc_mask_create"):                 # (the emulator builds of the other features do not hold the masking entry points)
         L.unc_mask_create.argtypes = [C.c_int, vp, u64, vp, u32, C.POINTER(vp)]
         L.unc_mask_free.argtypes = [vp]; L.unc_mask_free.restype = None
@@ -1035,6 +1044,39 @@ class Pileup:
         """kernel milliseconds of k_pileup_accum in the calling thread's last add() or alignment call"""
         ms = C.c_float()
         self.L.unc_pileup_last_timing(C.byref(ms))
+        return ms.value
+
+    def enable_hist(self, width, model=None):
+        """attaches a level histogram to this (empty) pile-up: 64 buckets of `width` levels a bin, bucket 32 beginning at the model's
+        mean for the bin's k-mer (model None: the r9.4 template).  Meant for regions: 256 bytes a bin"""
+        _check(self.L, self.L.unc_pileup_hist_enable(self.h, model.h if model is not None else None, float(width)))
+
+    def hist(self, bins):
+        """the histograms of the listed bins -> uint32[n, 64]"""
+        b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+        out = np.zeros((b.size, PILEUP_HIST_BUCKETS), dtype=np.uint32)
+        _check(self.L, self.L.unc_pileup_hist_gather(self.h, b.size, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def hist_centres(self, bins):
+        """the centres of the listed bins' histograms, rint(model mean * 2^20) -> int64[n]"""
+        b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+        out = np.zeros(b.size, dtype=np.int64)
+        _check(self.L, self.L.unc_pileup_hist_centres(self.h, b.size, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def ks(self, other, bins):
+        """-> PILEUP_KS records: the two-sample Kolmogorov-Smirnov distance of this pile-up's and `other`'s histograms at the listed
+        bins, exact (k_pileup_ks); every listed bin needs a record in both"""
+        b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+        out = np.zeros(b.size, dtype=PILEUP_KS)
+        _check(self.L, self.L.unc_pileup_ks(self.h, other.h, b.size, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def ks_last_timing(self):
+        """kernel milliseconds of k_pileup_ks in the calling thread's last ks()"""
+        ms = C.c_float()
+        self.L.unc_pileup_ks_last_timing(C.byref(ms))
         return ms.value
 
 

@@ -185,3 +185,5 @@ void launch_align_prep(const AlignPrep &p, hipStream_t st) {
 #include "k_model.hip"
 // and k_pileup_accum with the covered-bin kernels, which sum a round's records per reference position into a pile-up
 #include "k_pileup.hip"
+// and the pile-up's level histograms with k_pileup_ks, the two-sample Kolmogorov-Smirnov distance of two of them
+#include "k_pileup_hist.hip"

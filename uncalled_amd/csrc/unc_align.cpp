@@ -53,6 +53,7 @@ void pileup_set_timing(float ms);
 int pileup_device(const unc_pileup *pu);
 const unc_refseq *pileup_refseq(const unc_pileup *pu);
 void pileup_args(unc_pileup *pu, PileupAccum *a);
+bool pileup_hist_args(unc_pileup *pu, PileupHist *h);
 }  // namespace unc
 
 namespace {
@@ -61,9 +62,10 @@ namespace {
 // that, over the same records
 struct SegmentsHook : DtwRoundHook {
     SegArgs args{};
-    bool accumulate = false, pile = false;
+    bool accumulate = false, pile = false, pile_hist = false;
     ModelAccum acc{};   // (with accumulate) everything but the round's jobs
     PileupAccum pu{};   // (with pile) the same
+    PileupHist hist{};  // (with pile_hist) the pile-up's histogram, fed by k_pileup_hist_accum behind k_pileup_accum
     DevEvents ev;       // (timing only) two per round, one more with an accumulator, one more with a pile-up
     size_t per_round() const { return 2 + (accumulate ? 1 : 0) + (pile ? 1 : 0); }
     int round(const DtwJob *d_jobs, uint32_t n_jobs, uint64_t n_rows, const uint32_t *d_path, const unc_dtw_result_t *d_res, hipStream_t st) override {
@@ -83,6 +85,8 @@ struct SegmentsHook : DtwRoundHook {
         if (pile) {
             pu.jobs = d_jobs; pu.n_jobs = n_jobs;
             launch_pileup_accum(pu, n_rows, st);
+            HIPCHK(hipGetLastError());
+            if (pile_hist) launch_pileup_hist_accum(pu, hist, n_rows, st);
             HIPCHK(hipGetLastError());
             HIPCHK(ev.record(i + per_round() - 1, st));
         }
@@ -337,6 +341,7 @@ struct AlignRun : AlignCall {
             HIPCHK(hipMemcpyAsync(d_stretches.p, stretches, (size_t)n_queries * sizeof(unc_ref_stretch_t), hipMemcpyHostToDevice, st));
             hook.pile = true;
             pileup_args(pileup, &hook.pu);
+            hook.pile_hist = pileup_hist_args(pileup, &hook.hist);
             hook.pu.info = d_seginfo.p; hook.pu.queries = d_q.p; hook.pu.seg_off = d_seg_off.p; hook.pu.seg = d_seg.p;
             hook.pu.stretches = d_stretches.p;
         }
@@ -545,6 +550,8 @@ static int align_dispatch(const unc_align_call_t &u, const char *who, unc_pileup
 #include "unc_model_acc.cpp"
 // and so is the pile-up's
 #include "unc_pileup.cpp"
+// with its histograms and their Kolmogorov-Smirnov distance
+#include "unc_pileup_hist.cpp"
 
 // unc_align_call with a pile-up behind the segments (and behind the accumulator, when there is one): the same record, the same body
 extern "C" int unc_align_pileup_call(const unc_align_call_t *call, unc_pileup_t *pileup) {

@@ -25,6 +25,13 @@ struct unc_pileup {
     DevBuf<PileupRegion> d_regions;
     DevBuf<unsigned long long> d_tab;       // PILEUP_WORDS * n_bins words, then PILEUP_COUNTERS
     size_t words() const { return (size_t)(PILEUP_WORDS * n_bins + PILEUP_COUNTERS); }
+    // the histogram (unc_pileup_hist.cpp), attached by unc_pileup_hist_enable: hist_w == 0 without one
+    int64_t hist_w = 0;
+    std::vector<int64_t> hist_ctab;         // the 1024 centres it was attached with, in k-mer order
+    DevBuf<uint32_t> d_hist;                // PILEUP_HIST_BUCKETS * n_bins buckets
+    DevBuf<int64_t> d_centres;              // n_bins
+    size_t buckets() const { return (size_t)(PILEUP_HIST_BUCKETS * n_bins); }
+    size_t hist_bytes() const { return hist_w ? std::max<size_t>(1, buckets()) * sizeof(uint32_t) + std::max<size_t>(1, (size_t)n_bins) * sizeof(int64_t) : 0; }
 };
 
 static thread_local float g_pileup_ms = 0;
@@ -50,6 +57,10 @@ const unc_refseq *pileup_refseq(const unc_pileup *pu) { return pu->rs; }
 void pileup_args(unc_pileup *pu, PileupAccum *a) {
     a->tab = pu->d_tab.p; a->regions = pu->d_regions.p; a->n_bins = pu->n_bins; a->n_regions = (uint32_t)pu->regions.size(); a->flags = pu->flags;
 }
+bool pileup_hist_args(unc_pileup *pu, PileupHist *h) {
+    h->hist = pu->d_hist.p; h->centres = pu->d_centres.p; h->w = pu->hist_w;
+    return pu->hist_w != 0;
+}
 }  // namespace unc
 
 namespace {
@@ -61,6 +72,9 @@ bool same_regions(const unc_pileup *a, const unc_pileup *b) {
     }
     return true;
 }
+
+// both without a histogram, or both with one of the same width and the same 1024 centres
+bool same_hist(const unc_pileup *a, const unc_pileup *b) { return a->hist_w == b->hist_w && a->hist_ctab == b->hist_ctab; }
 
 // the region that holds `bin`: the last one whose first bin is not behind it and that holds a bin at all
 const PileupRegion *region_of_bin(const unc_pileup *pu, uint64_t bin) {
@@ -167,11 +181,12 @@ extern "C" int unc_pileup_reset(unc_pileup_t *pu) {
     HIPCHK(hipSetDevice(pu->device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemset(pu->d_tab.p, 0, pu->words() * sizeof(unsigned long long)));
+    if (pu->hist_w && pu->buckets()) HIPCHK(hipMemset(pu->d_hist.p, 0, pu->buckets() * sizeof(uint32_t)));       // (the centres stay)
     return UNC_OK;
 }
 
 extern "C" uint64_t unc_pileup_device_bytes(const unc_pileup_t *pu) {
-    return pu ? pu->words() * sizeof(unsigned long long) + std::max<size_t>(1, pu->regions.size()) * sizeof(PileupRegion) : 0;
+    return pu ? pu->words() * sizeof(unsigned long long) + std::max<size_t>(1, pu->regions.size()) * sizeof(PileupRegion) + pu->hist_bytes() : 0;
 }
 extern "C" uint64_t unc_pileup_n_bins(const unc_pileup_t *pu) { return pu ? pu->n_bins : 0; }
 
@@ -220,6 +235,9 @@ extern "C" int unc_pileup_add(unc_pileup_t *pu, uint64_t n, const int32_t *rid, 
     a.n = n; a.rid = d_rid.p; a.pos = d_pos.p; a.fwd = d_fwd.p; a.level = d_level.p; a.smp_n = d_smp.p; a.shared = shared ? d_shared.p : nullptr;
     HIPCHK(ev.record(0, st));
     launch_pileup_accum(a, n, st);
+    HIPCHK(hipGetLastError());
+    PileupHist h{};
+    if (pileup_hist_args(pu, &h)) launch_pileup_hist_accum(a, h, n, st);       // (inside the two events: last_timing covers both)
     HIPCHK(hipGetLastError());
     HIPCHK(ev.record(1, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -306,8 +324,24 @@ extern "C" int unc_pileup_merge(unc_pileup_t *dst, const unc_pileup_t *src) {
     if (!dst || !src) return fail(UNC_ERR_ARG, "%s: null argument", who);
     if (dst == src) return fail(UNC_ERR_ARG, "%s: a pile-up cannot be merged into itself", who);
     if (!same_regions(dst, src)) return fail(UNC_ERR_ARG, "%s: the two pile-ups differ in their regions", who);
+    if (!same_hist(dst, src)) return fail(UNC_ERR_ARG, "%s: the two pile-ups differ in their histograms: one has none, or the widths or the centres differ", who);
     DevBuf<unsigned long long> staged;
+    DevBuf<uint32_t> staged_hist;
     const unsigned long long *d_src = src->d_tab.p;
+    const uint32_t *d_src_hist = src->d_hist.p;
+    if (src->device != dst->device && src->hist_w && src->buckets()) {
+        std::vector<uint32_t> h(src->buckets());
+        HIPCHK(hipSetDevice(src->device));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(h.data(), src->d_hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipSetDevice(dst->device));
+        if (staged_hist.alloc(h.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(UNC_ERR_NOMEM, "%s: no device memory for the other device's histogram", who);
+        }
+        HIPCHK(hipMemcpy(staged_hist.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        d_src_hist = staged_hist.p;
+    }
     if (src->device != dst->device) {       // through the host: no peer access is assumed
         std::vector<unsigned long long> h(src->words());
         HIPCHK(hipSetDevice(src->device));
@@ -324,6 +358,8 @@ extern "C" int unc_pileup_merge(unc_pileup_t *dst, const unc_pileup_t *src) {
     HIPCHK(hipSetDevice(dst->device));
     HIPCHK(hipDeviceSynchronize());
     launch_pileup_merge(dst->d_tab.p, d_src, dst->n_bins, nullptr);
+    HIPCHK(hipGetLastError());
+    if (dst->hist_w) launch_pileup_hist_merge(dst->d_hist.p, d_src_hist, dst->n_bins, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(nullptr));
     return UNC_OK;

@@ -73,6 +73,18 @@ __device__ __forceinline__ uint32_t excl_sum32(uint32_t v, uint32_t *total) {
     return x - v;
 }
 
+// inclusive prefix sum of 32-bit per-lane values (sums modulo 2^32); *total = sum over the wave
+__device__ __forceinline__ uint32_t incl_sum32(uint32_t v, uint32_t *total) {
+    uint32_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        uint32_t y = (uint32_t)__shfl_up((int)x, d);
+        if (lane_id() >= d) x += y;
+    }
+    *total = bcast32(x, 63);
+    return x;
+}
+
 // exclusive prefix max (identity 0); *total = max over the wave
 __device__ __forceinline__ uint32_t excl_max32(uint32_t v, uint32_t *total) {
     uint32_t x = v;
