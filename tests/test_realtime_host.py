@@ -164,7 +164,76 @@ def case_oversized_chunk_is_refused(unc):
     assert pool.all_finished() and pool.update() == []
 
 
-def case_client_sim_feeds_the_decision_loop(unc, tmp_path, goldens):
+def case_channel_transitions(unc, po, goldens):
+    """The rows of RealtimePool's channel table (unc_realtime.hpp) that no other case reaches: end_read in every state, the empty
+    chunk of try_add_chunk, a foreign read number in try_add_chunk, an oversized chunk on a channel that does not exist, stop_all."""
+    pool = unc.RealtimePool(_conf(unc, 2))
+    noise = (np.random.default_rng(5).normal(90.0, 12.0, 8000)).astype(np.float32).tolist()      # never maps
+    empty = lambda rid, ch, nm: unc.Chunk(rid, ch, nm, len(noise), noise, len(noise), 4000)      # past the read's end: no samples
+    assert empty("a", 1, 1).empty()
+
+    def unmapped_ended(out, ch, nm, rid, raw_len):
+        assert len(out) == 1 and out[0][:2] == (ch, nm) and out[0][2].is_ended() and not out[0][2].is_mapped()
+        assert str(out[0][2]).split("\t")[:2] == [rid, str(int(raw_len * 450.0 / 4000.0))]
+
+    # end_read on a read that is mapping: unmapped + ended at the next update; a wrong number or a channel past the end: nothing
+    assert pool.add_chunk(unc.Chunk("a", 1, 1, 0, noise, 0, 4000))
+    assert pool.update() == [] and pool.active_count() == 1
+    pool.end_read(0, 2)
+    pool.end_read(1, 1)
+    pool.end_read(2, 1)
+    pool.end_read(65535, 1)
+    assert pool.active_count() == 1 and pool.update() == [] and not pool.all_finished()
+    pool.end_read(0, 1)
+    assert pool.active_count() == 0 and not pool.all_finished()
+    unmapped_ended(pool.update(), 1, 1, "a", 4000)
+    assert pool.all_finished() and pool.update() == []
+    # a read whose first chunk is still only pending: an empty chunk changes nothing, end_read makes it vanish with no record
+    assert pool.add_chunk(unc.Chunk("b", 1, 2, 0, noise, 0, 4000))
+    assert not pool.try_add_chunk(empty("b", 1, 2)) and pool.active_count() == 1
+    pool.end_read(0, 2)
+    assert pool.active_count() == 0 and pool.all_finished() and pool.update() == []
+    # try_add_chunk, an empty chunk: nothing while a chunk is pending; once that one is mapped the read is given up, one record
+    assert pool.try_add_chunk(unc.Chunk("c", 2, 3, 0, noise, 0, 4000))
+    assert pool.update() == []
+    assert pool.try_add_chunk(unc.Chunk("c", 2, 3, 4000, noise, 4000, 4000))
+    assert not pool.try_add_chunk(empty("c", 2, 3)) and pool.active_count() == 1
+    assert pool.update() == [] and pool.active_count() == 1
+    assert not pool.try_add_chunk(unc.Chunk("d", 2, 4, 0, noise, 0, 4000))                       # another read: refused, nothing changes
+    assert pool.active_count() == 1 and pool.update() == [] and not pool.all_finished()
+    assert not pool.try_add_chunk(empty("c", 2, 3))
+    assert pool.active_count() == 0 and not pool.all_finished()
+    unmapped_ended(pool.update(), 2, 3, "c", 8000)
+    assert pool.all_finished()
+    # an oversized chunk on a channel past num_channels: add_chunk counts it as refused, try_add_chunk does not
+    assert not pool.add_chunk(unc.Chunk("big", 3, 9, 0, noise, 0, 4001)) and pool.refused_chunks() == 1
+    assert not pool.try_add_chunk(unc.Chunk("big", 3, 9, 0, noise, 0, 4001)) and pool.refused_chunks() == 1
+    assert not pool.add_chunk(unc.Chunk("far", 3, 9, 0, noise, 0, 4000)) and not pool.try_add_chunk(unc.Chunk("far", 3, 9, 0, noise, 0, 4000))
+    assert pool.refused_chunks() == 1 and pool.all_finished() and pool.update() == []
+    # try_add_chunk with another read's chunk between the chunks of a read that goes on to map: that read is not disturbed
+    off = goldens["sim_offsets"]
+    good = po.calibrate(goldens["sim_signal"][int(off[0]):int(off[1])], CAL_RANGE, CAL_OFFSET, CAL_DIGITISATION).tolist()
+    assert pool.try_add_chunk(unc.Chunk("good", 1, 6, 0, good, 0, 4000))
+    assert not pool.try_add_chunk(unc.Chunk("other", 1, 7, 0, noise, 0, 4000))                   # ... while the first chunk is pending
+    out, k = pool.update(), 1
+    while not out and k * 4000 < len(good):
+        assert not pool.try_add_chunk(unc.Chunk("other", 1, 7, 0, noise, 0, 4000))               # ... and while the read is mapping
+        assert pool.try_add_chunk(unc.Chunk("good", 1, 6, k * 4000, good, k * 4000, 4000))
+        out, k = pool.update(), k + 1
+    assert len(out) == 1 and out[0][:2] == (1, 6) and out[0][2].is_mapped() and str(out[0][2]).split("\t")[0] == "good"
+    assert pool.all_finished()
+    # stop_all: nothing is taken and nothing is reported any more, not even a read given up just before
+    assert pool.add_chunk(unc.Chunk("e", 2, 8, 0, noise, 0, 4000))
+    assert pool.update() == [] and pool.active_count() == 1
+    pool.end_read(1, 8)
+    assert not pool.all_finished()
+    pool.stop_all()
+    assert not pool.add_chunk(unc.Chunk("f", 1, 9, 0, noise, 0, 4000)) and not pool.try_add_chunk(unc.Chunk("f", 1, 9, 0, noise, 0, 4000))
+    assert not pool.add_chunk(unc.Chunk("f", 1, 9, 0, noise, 0, 4001)) and pool.refused_chunks() == 1
+    assert pool.update() == [] and pool.active_count() == 0 and pool.all_finished()
+
+
+def case_client_sim_feeds_the_decision_loop(unc, po, tmp_path, goldens):
     """ClientSim-shaped source over fast5 files + the enrich/deplete loop of scripts/uncalled:216-256 (uncalled_amd sim)."""
     off = goldens["sim_offsets"]
     cals = [_read_cal(i + 3) for i in range(4)]          # (the one with seven significant digits among them)
@@ -180,7 +249,6 @@ def case_client_sim_feeds_the_decision_loop(unc, tmp_path, goldens):
     first = client.get_read_chunks()
     assert [(ch, c.id, c.number, c.size()) for ch, c in first] == [(1, "sim-0", 0, 4000), (2, "sim-1", 1, 4000)]
     assert first[0][1].start == 0 and first[1][1].start == 1000
-    from oracle import pyoracle as po
     for k, (ch, c) in enumerate(first):                 # calibrated with the read's own calibration, as Fast5Reader reads it back
         want = po.calibrate(np.array(reads[k]["signal"][:4000], dtype=np.int16), *_as_read(cals[k]))
         assert np.array_equal(np.array(c.pop(), dtype=np.float32).view(np.uint32), want.view(np.uint32)), k
@@ -321,8 +389,13 @@ def test_oversized_chunk_is_refused(sim_host):
 
 
 @pytest.mark.lanesim
-def test_client_sim_feeds_the_decision_loop(sim_host, tmp_path, goldens):
-    case_client_sim_feeds_the_decision_loop(sim_host, tmp_path, goldens)
+def test_channel_transitions(sim_host, oracle_lib, goldens):
+    case_channel_transitions(sim_host, oracle_lib, goldens)
+
+
+@pytest.mark.lanesim
+def test_client_sim_feeds_the_decision_loop(sim_host, oracle_lib, tmp_path, goldens):
+    case_client_sim_feeds_the_decision_loop(sim_host, oracle_lib, tmp_path, goldens)
 
 
 @pytest.mark.lanesim

@@ -113,15 +113,7 @@ PYBIND11_MODULE(_uncalled_amd, m) {
         .def_property_readonly("channel", [](const RawRead &r) { return (uint16_t)(r.channel_idx + 1); })
         .def_property_readonly("calibration", [](const RawRead &r) { return py::make_tuple(r.calib.range, r.calib.offset, r.calib.digitisation); })
         .def_property_readonly("raw_i16", [](const RawRead &r) { return r.signal; })
-        .def_property_readonly("raw", [](const RawRead &r) {   // fast5.hpp raw_samples_to_float arithmetic
-            std::vector<float> out(r.signal.size());
-            for (size_t i = 0; i < out.size(); ++i) {
-                const float t1 = (float)(int)(uint16_t)r.signal[i] + r.calib.offset;
-                const float t2 = r.calib.range * t1;
-                out[i] = t2 / r.calib.digitisation;
-            }
-            return out;
-        });
+        .def_property_readonly("raw", &calibrated);
 
     m.def("write_fast5",
           [](const std::string &path, const std::vector<py::dict> &reads, bool multi, float sample_rate) {

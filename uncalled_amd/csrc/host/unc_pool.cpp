@@ -2,7 +2,6 @@
 
 #include <hdf5.h>
 
-#include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
@@ -62,20 +61,18 @@ bool Fast5Reader::add_read(const std::string &read_id) {
     return true;
 }
 
-bool Fast5Reader::load_fast5_list(const std::string &fname) {
+template <class F> static bool each_line(const std::string &fname, const char *what, F take) {
     std::ifstream f(fname);
-    if (!f.is_open()) { std::cerr << "Error: failed to open fast5 list \"" << fname << "\".\n"; return false; }
+    if (!f.is_open()) { std::cerr << "Error: failed to open " << what << " list \"" << fname << "\".\n"; return false; }
     std::string line;
-    while (std::getline(f, line)) if (!line.empty()) add_fast5(line);
+    while (std::getline(f, line) && take(line)) {}
     return true;
 }
-
+bool Fast5Reader::load_fast5_list(const std::string &fname) {
+    return each_line(fname, "fast5", [&](const std::string &l) { if (!l.empty()) add_fast5(l); return true; });
+}
 bool Fast5Reader::load_read_list(const std::string &fname) {
-    std::ifstream f(fname);
-    if (!f.is_open()) { std::cerr << "Error: failed to open read list \"" << fname << "\".\n"; return false; }
-    std::string line;
-    while (std::getline(f, line)) if (!add_read(line)) break;
-    return true;
+    return each_line(fname, "read", [&](const std::string &l) { return add_read(l); });
 }
 
 bool Fast5Reader::all_buffered() const {
@@ -84,57 +81,64 @@ bool Fast5Reader::all_buffered() const {
 
 bool Fast5Reader::empty() { return buffered_.empty() && read_paths_.empty() && (fast5_list_.empty() || all_buffered()); }
 
+// An HDF5 identifier that closes itself with the H5?close of its kind; move-only (the move constructor deletes copying)
+namespace {
+class H5 {
+public:
+    H5(hid_t id, herr_t (*close)(hid_t)) : id_(id), close_(close) {}
+    H5(H5 &&o) noexcept : id_(o.id_), close_(o.close_) { o.id_ = -1; }
+    ~H5() { if (id_ >= 0) close_(id_); }
+    operator hid_t() const { return id_; }
+    bool ok() const { return id_ >= 0; }
+private:
+    hid_t id_;
+    herr_t (*close_)(hid_t);
+};
+H5 string_type(size_t size) {      // a C string type of `size` bytes (or H5T_VARIABLE)
+    H5 t(H5Tcopy(H5T_C_S1), H5Tclose);
+    H5Tset_size(t, size);
+    return t;
+}
+}  // namespace
 static herr_t collect_names(hid_t, const char *name, const H5L_info_t *, void *op) {
     static_cast<std::vector<std::string> *>(op)->push_back(name);
     return 0;
 }
 static std::vector<std::string> list_group(hid_t f, const std::string &path) {
     std::vector<std::string> names;
-    hid_t g = H5Gopen2(f, path.c_str(), H5P_DEFAULT);
-    if (g < 0) return names;
-    H5Literate(g, H5_INDEX_NAME, H5_ITER_INC, nullptr, collect_names, &names);
-    H5Gclose(g);
+    const H5 g(H5Gopen2(f, path.c_str(), H5P_DEFAULT), H5Gclose);
+    if (g.ok()) H5Literate(g, H5_INDEX_NAME, H5_ITER_INC, nullptr, collect_names, &names);
     return names;
 }
 static bool attr_string(hid_t f, const std::string &obj, const char *name, std::string &out) {
-    hid_t a = H5Aopen_by_name(f, obj.c_str(), name, H5P_DEFAULT, H5P_DEFAULT);
-    if (a < 0) return false;
-    hid_t t = H5Aget_type(a);
-    bool ok = false;
-    if (H5Tget_class(t) == H5T_STRING) {
-        if (H5Tis_variable_str(t)) {
-            char *p = nullptr;
-            hid_t mt = H5Tcopy(H5T_C_S1);
-            H5Tset_size(mt, H5T_VARIABLE);
-            if (H5Aread(a, mt, &p) >= 0 && p) { out = p; free(p); ok = true; }
-            H5Tclose(mt);
-        } else {
-            size_t n = H5Tget_size(t);
-            std::vector<char> buf(n + 1, 0);
-            hid_t mt = H5Tcopy(H5T_C_S1);
-            H5Tset_size(mt, n);
-            if (H5Aread(a, mt, buf.data()) >= 0) { out = std::string(buf.data(), strnlen(buf.data(), n)); ok = true; }
-            H5Tclose(mt);
-        }
+    const H5 a(H5Aopen_by_name(f, obj.c_str(), name, H5P_DEFAULT, H5P_DEFAULT), H5Aclose);
+    if (!a.ok()) return false;
+    const H5 t(H5Aget_type(a), H5Tclose);
+    if (H5Tget_class(t) != H5T_STRING) return false;
+    if (H5Tis_variable_str(t)) {
+        char *p = nullptr;
+        if (H5Aread(a, string_type(H5T_VARIABLE), &p) < 0 || !p) return false;
+        out = p; free(p);
+        return true;
     }
-    H5Tclose(t);
-    H5Aclose(a);
-    return ok;
+    const size_t n = H5Tget_size(t);
+    std::vector<char> buf(n + 1, 0);
+    if (H5Aread(a, string_type(n), buf.data()) < 0) return false;
+    out = std::string(buf.data(), strnlen(buf.data(), n));
+    return true;
 }
 static bool attr_double(hid_t f, const std::string &obj, const char *name, double &out) {
-    hid_t a = H5Aopen_by_name(f, obj.c_str(), name, H5P_DEFAULT, H5P_DEFAULT);
-    if (a < 0) return false;
-    hid_t t = H5Aget_type(a);
-    bool ok = false;
+    const H5 a(H5Aopen_by_name(f, obj.c_str(), name, H5P_DEFAULT, H5P_DEFAULT), H5Aclose);
+    if (!a.ok()) return false;
+    const H5 t(H5Aget_type(a), H5Tclose);
     if (H5Tget_class(t) == H5T_STRING) {
-        H5Tclose(t); H5Aclose(a);
         std::string s;
         if (!attr_string(f, obj, name, s)) return false;
         out = atof(s.c_str());
         return true;
     }
-    ok = H5Aread(a, H5T_NATIVE_DOUBLE, &out) >= 0;
-    if (ok && H5Tget_class(t) == H5T_FLOAT) {
+    if (H5Aread(a, H5T_NATIVE_DOUBLE, &out) < 0) return false;
+    if (H5Tget_class(t) == H5T_FLOAT) {
         // ReadBuffer takes every attribute through get_attr_map's strings and atof (read_buffer.cpp:202-222); the fast5
         // library renders a floating attribute with a default-precision stream, i.e. 6 significant digits
         // (range 1534.141357421875 -> "1534.14").  Keep that rounding so the calibrated samples agree.
@@ -142,14 +146,14 @@ static bool attr_double(hid_t f, const std::string &obj, const char *name, doubl
         oss << out;
         out = atof(oss.str().c_str());
     }
-    H5Tclose(t);
-    H5Aclose(a);
-    return ok;
+    return true;
 }
+
+void Fast5Reader::close_file() { if (file_ >= 0) H5Fclose((hid_t)file_); file_ = -1; }
 
 bool Fast5Reader::open_next() {
     read_paths_.clear();
-    if (file_ >= 0) { H5Fclose((hid_t)file_); file_ = -1; }
+    close_file();
     if (fast5_list_.empty()) return false;
     const std::string fn = fast5_list_.front();
     fast5_list_.pop_front();
@@ -158,17 +162,10 @@ bool Fast5Reader::open_next() {
     const hid_t f = (hid_t)file_;
     multi_ = true;
     for (const std::string &s : list_group(f, "/")) if (s == "Raw") { multi_ = false; break; }
-    if (!multi_) {
-        for (const std::string &read : list_group(f, "/Raw/Reads")) {
-            std::string id;
-            if (!attr_string(f, "/Raw/Reads/" + read, "read_id", id) || id.empty()) { std::cerr << "Error: failed to find read_id\n"; return false; }
-            if (read_filter_.empty() || read_filter_.count(id)) read_paths_.push_back("/" + read);
-        }
-    } else {
-        for (const std::string &read : list_group(f, "/")) {
-            const std::string id = read.substr(read.find('_') + 1);
-            if (read_filter_.empty() || read_filter_.count(id)) read_paths_.push_back("/" + read);
-        }
+    for (const std::string &read : list_group(f, multi_ ? "/" : "/Raw/Reads")) {      // multi: the id is in the group's name
+        std::string id = read.substr(read.find('_') + 1);
+        if (!multi_ && (!attr_string(f, "/Raw/Reads/" + read, "read_id", id) || id.empty())) { std::cerr << "Error: failed to find read_id\n"; return false; }
+        if (read_filter_.empty() || read_filter_.count(id)) read_paths_.push_back("/" + read);
     }
     return true;
 }
@@ -181,21 +178,16 @@ bool Fast5Reader::read_one(const std::string &raw_path, const std::string &ch_pa
     if (attr_string(f, raw_path, "read_id", s)) r.id = s;
     if (attr_double(f, raw_path, "read_number", v)) r.number = (uint32_t)(int)v;
     if (attr_double(f, raw_path, "start_time", v)) r.start_sample = (uint64_t)(int)v;
-    float dig = 1, rng = 1, off = 0;
     if (attr_string(f, ch_path, "channel_number", s)) r.channel_idx = (uint16_t)(atoi(s.c_str()) - 1);
     else if (attr_double(f, ch_path, "channel_number", v)) r.channel_idx = (uint16_t)((int)v - 1);
-    if (attr_double(f, ch_path, "digitisation", v)) dig = (float)v;
-    if (attr_double(f, ch_path, "range", v)) rng = (float)v;
-    if (attr_double(f, ch_path, "offset", v)) off = (float)v;
-    r.calib.range = rng; r.calib.offset = off; r.calib.digitisation = dig;
-    hid_t d = H5Dopen2(f, (raw_path + "/Signal").c_str(), H5P_DEFAULT);
-    if (d < 0) return false;
-    hid_t sp = H5Dget_space(d);
-    const hssize_t n = H5Sget_simple_extent_npoints(sp);
+    if (attr_double(f, ch_path, "digitisation", v)) r.calib.digitisation = (float)v;      // (a missing one keeps RawRead's 1, 1, 0)
+    if (attr_double(f, ch_path, "range", v)) r.calib.range = (float)v;
+    if (attr_double(f, ch_path, "offset", v)) r.calib.offset = (float)v;
+    const H5 d(H5Dopen2(f, (raw_path + "/Signal").c_str(), H5P_DEFAULT), H5Dclose);
+    if (!d.ok()) return false;
+    const hssize_t n = H5Sget_simple_extent_npoints(H5(H5Dget_space(d), H5Sclose));
     r.signal.resize(n > 0 ? (size_t)n : 0);
-    bool ok = n <= 0 || H5Dread(d, H5T_NATIVE_INT16, H5S_ALL, H5S_ALL, H5P_DEFAULT, r.signal.data()) >= 0;
-    H5Sclose(sp);
-    H5Dclose(d);
+    const bool ok = n <= 0 || H5Dread(d, H5T_NATIVE_INT16, H5S_ALL, H5S_ALL, H5P_DEFAULT, r.signal.data()) >= 0;
     // chunk_count_ > max_chunks: the signal is cut to whole chunks (read_buffer.cpp:229-234)
     if (chunk_len_) {
         const uint64_t cc = r.signal.size() / chunk_len_ + (r.signal.size() % chunk_len_ != 0);
@@ -210,9 +202,8 @@ uint32_t Fast5Reader::fill_buffer() {
         if (all_buffered()) { read_paths_.clear(); fast5_list_.clear(); break; }
         while (read_paths_.empty()) if (!open_next()) break;
         if (read_paths_.empty()) break;
-        std::string raw_path, ch_path;
-        if (!multi_) { raw_path = "/Raw/Reads" + read_paths_.front(); ch_path = "/UniqueGlobalKey/channel_id"; }
-        else { raw_path = read_paths_.front() + "/Raw"; ch_path = read_paths_.front() + "/channel_id"; }
+        const std::string rp = read_paths_.front();
+        const std::string raw_path = multi_ ? rp + "/Raw" : "/Raw/Reads" + rp, ch_path = multi_ ? rp + "/channel_id" : "/UniqueGlobalKey/channel_id";
         read_paths_.pop_front();
         RawRead r;
         if (read_one(raw_path, ch_path, r)) {
@@ -233,53 +224,46 @@ RawRead Fast5Reader::pop_read() {
 }
 
 // ------------------------------------------------------------------ fast5 writer (simulators / tests)
-static void put_attr_str(hid_t obj, const char *name, const std::string &v) {
-    hid_t t = H5Tcopy(H5T_C_S1);
-    H5Tset_size(t, v.size() ? v.size() : 1);
-    hid_t sp = H5Screate(H5S_SCALAR);
-    hid_t a = H5Acreate2(obj, name, t, sp, H5P_DEFAULT, H5P_DEFAULT);
-    H5Awrite(a, t, v.c_str());
-    H5Aclose(a); H5Sclose(sp); H5Tclose(t);
+static bool put_attr(hid_t obj, const char *name, hid_t file_t, hid_t mem_t, const void *v) {
+    const H5 sp(H5Screate(H5S_SCALAR), H5Sclose);
+    const H5 a(H5Acreate2(obj, name, file_t, sp, H5P_DEFAULT, H5P_DEFAULT), H5Aclose);
+    return a.ok() && H5Awrite(a, mem_t, v) >= 0;
 }
-template <class T> static void put_attr_num(hid_t obj, const char *name, hid_t file_t, hid_t mem_t, T v) {
-    hid_t sp = H5Screate(H5S_SCALAR);
-    hid_t a = H5Acreate2(obj, name, file_t, sp, H5P_DEFAULT, H5P_DEFAULT);
-    H5Awrite(a, mem_t, &v);
-    H5Aclose(a); H5Sclose(sp);
+static bool put_attr_str(hid_t obj, const char *name, const std::string &v) {
+    const H5 t = string_type(v.size() ? v.size() : 1);
+    return put_attr(obj, name, t, t, v.c_str());
 }
-static void write_read(hid_t raw_g, hid_t ch_g, const RawRead &r, float sample_rate) {
-    put_attr_str(raw_g, "read_id", r.id);
-    put_attr_num<int32_t>(raw_g, "read_number", H5T_STD_I32LE, H5T_NATIVE_INT32, (int32_t)r.number);
-    put_attr_num<uint64_t>(raw_g, "start_time", H5T_STD_U64LE, H5T_NATIVE_UINT64, r.start_sample);
-    put_attr_num<uint32_t>(raw_g, "duration", H5T_STD_U32LE, H5T_NATIVE_UINT32, (uint32_t)r.signal.size());
-    hsize_t n = r.signal.size();
-    hid_t sp = H5Screate_simple(1, &n, nullptr);
-    hid_t d = H5Dcreate2(raw_g, "Signal", H5T_STD_I16LE, sp, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-    if (n) H5Dwrite(d, H5T_NATIVE_INT16, H5S_ALL, H5S_ALL, H5P_DEFAULT, r.signal.data());
-    H5Dclose(d); H5Sclose(sp);
-    put_attr_str(ch_g, "channel_number", std::to_string(r.channel_idx + 1));
-    put_attr_num<double>(ch_g, "digitisation", H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, r.calib.digitisation);
-    put_attr_num<double>(ch_g, "range", H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, r.calib.range);
-    put_attr_num<double>(ch_g, "offset", H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, r.calib.offset);
-    put_attr_num<double>(ch_g, "sampling_rate", H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, sample_rate);
+static bool write_read(hid_t raw_g, hid_t ch_g, const RawRead &r, float sample_rate) {
+    const int32_t number = (int32_t)r.number;
+    const uint32_t duration = (uint32_t)r.signal.size();
+    if (!put_attr_str(raw_g, "read_id", r.id) || !put_attr(raw_g, "read_number", H5T_STD_I32LE, H5T_NATIVE_INT32, &number) ||
+        !put_attr(raw_g, "start_time", H5T_STD_U64LE, H5T_NATIVE_UINT64, &r.start_sample) ||
+        !put_attr(raw_g, "duration", H5T_STD_U32LE, H5T_NATIVE_UINT32, &duration))
+        return false;
+    const hsize_t n = r.signal.size();
+    const H5 sp(H5Screate_simple(1, &n, nullptr), H5Sclose);
+    const H5 d(H5Dcreate2(raw_g, "Signal", H5T_STD_I16LE, sp, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), H5Dclose);
+    if (!d.ok() || (n && H5Dwrite(d, H5T_NATIVE_INT16, H5S_ALL, H5S_ALL, H5P_DEFAULT, r.signal.data()) < 0)) return false;
+    const double dig = r.calib.digitisation, range = r.calib.range, offset = r.calib.offset, rate = sample_rate;
+    return put_attr_str(ch_g, "channel_number", std::to_string(r.channel_idx + 1)) &&
+           put_attr(ch_g, "digitisation", H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, &dig) && put_attr(ch_g, "range", H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, &range) &&
+           put_attr(ch_g, "offset", H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, &offset) && put_attr(ch_g, "sampling_rate", H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, &rate);
 }
 
+// false when the file, a group, the dataset or an attribute could not be created or written
 bool write_fast5(const std::string &path, const std::vector<RawRead> &reads, bool multi, float sample_rate) {
     if (!multi && reads.size() != 1) return false;
-    hid_t f = H5Fcreate(path.c_str(), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT);
-    if (f < 0) return false;
-    hid_t lcpl = H5Pcreate(H5P_LINK_CREATE);
+    const H5 f(H5Fcreate(path.c_str(), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT), H5Fclose);
+    if (!f.ok()) return false;
+    const H5 lcpl(H5Pcreate(H5P_LINK_CREATE), H5Pclose);
     H5Pset_create_intermediate_group(lcpl, 1);
     for (const RawRead &r : reads) {
         const std::string raw = multi ? "/read_" + r.id + "/Raw" : "/Raw/Reads/Read_" + std::to_string(r.number);
         const std::string ch = multi ? "/read_" + r.id + "/channel_id" : "/UniqueGlobalKey/channel_id";
-        hid_t rg = H5Gcreate2(f, raw.c_str(), lcpl, H5P_DEFAULT, H5P_DEFAULT);
-        hid_t cg = H5Gcreate2(f, ch.c_str(), lcpl, H5P_DEFAULT, H5P_DEFAULT);
-        write_read(rg, cg, r, sample_rate);
-        H5Gclose(rg); H5Gclose(cg);
+        const H5 rg(H5Gcreate2(f, raw.c_str(), lcpl, H5P_DEFAULT, H5P_DEFAULT), H5Gclose);
+        const H5 cg(H5Gcreate2(f, ch.c_str(), lcpl, H5P_DEFAULT, H5P_DEFAULT), H5Gclose);
+        if (!rg.ok() || !cg.ok() || !write_read(rg, cg, r, sample_rate)) return false;
     }
-    H5Pclose(lcpl);
-    H5Fclose(f);
     return true;
 }
 
@@ -294,28 +278,49 @@ int index_set_model_path(unc_index_t *ix, const std::string &model_path) {
     return rc;
 }
 
-// ------------------------------------------------------------------ MapPool (map_pool.cpp:28-158), batched on one GPU
-MapPool::MapPool(const Conf &conf) : conf_(conf), reader_(conf) {
-    unc_params_t p;
+// ------------------------------------------------------------------ what MapPool and RealtimePool share
+void die_last_error() { std::cerr << "Error: " << unc_last_error() << "\n"; abort(); }
+unc_index_t *open_index(const Conf &conf, unc_params_t &p) {
     unc_params_default(&p);
-    p.max_events = conf.max_events;
-    p.max_chunks = conf.max_chunks;
-    p.chunk_time = conf.chunk_time;
-    p.sample_rate = conf.sample_rate;
-    bp_per_samp_ = p.bp_per_sec / p.sample_rate;
-    if (unc_index_load(conf.bwa_prefix.c_str(), conf.idx_preset.c_str(), conf.device, &ix_) != UNC_OK ||
-        index_set_model_path(ix_, conf.model_path) != UNC_OK || unc_mapper_create(ix_, &p, nullptr, &mapper_) != UNC_OK) {
-        std::cerr << "Error: " << unc_last_error() << "\n";   // Mapper::load_static aborts on a bad index, mapper.cpp:118-127
-        abort();
+    p.max_events = conf.max_events; p.max_chunks = conf.max_chunks;
+    p.chunk_time = conf.chunk_time; p.sample_rate = conf.sample_rate;
+    unc_index_t *ix = nullptr;
+    if (unc_index_load(conf.bwa_prefix.c_str(), conf.idx_preset.c_str(), conf.device, &ix) != UNC_OK ||
+        index_set_model_path(ix, conf.model_path) != UNC_OK) die_last_error();
+    return ix;
+}
+
+Paf paf_from_hit(const unc_index_t *ix, const std::string &id, uint16_t channel_idx, uint64_t start_sample, const unc_hit_t &h) {
+    Paf p(id, (uint16_t)(channel_idx + 1), start_sample);
+    p.set_read_len(h.rd_len);
+    if (h.mapped) p.set_mapped(h.rd_st, h.rd_en, unc_index_seq_name(ix, h.rid), h.rf_st, h.rf_en, h.rf_len, h.fwd != 0, (uint16_t)h.matches);
+    if (h.status) std::cerr << "Warning: read " << id << ": device scratch overflow (status " << h.status << "); reported unmapped\n";
+    return p;
+}
+Paf unmapped_paf(const unc_params_t &prms, const std::string &id, uint16_t channel_idx, uint64_t start_sample, uint64_t raw_len) {
+    Paf p(id, (uint16_t)(channel_idx + 1), start_sample);
+    p.set_read_len((uint64_t)((float)raw_len * (prms.bp_per_sec / prms.sample_rate)));      // bp_per_samp: here only
+    return p;
+}
+std::vector<float> calibrated(const RawRead &r) {
+    std::vector<float> out(r.signal.size());
+    for (size_t i = 0; i < out.size(); ++i) {
+        const float t1 = (float)(int)(uint16_t)r.signal[i] + r.calib.offset;     // (the u16 quirk)
+        const float t2 = r.calib.range * t1;
+        out[i] = t2 / r.calib.digitisation;
     }
+    return out;
+}
+
+// ------------------------------------------------------------------ MapPool (map_pool.cpp:28-158), batched on one GPU
+MapPool::MapPool(const Conf &conf) : reader_(conf) {
+    ix_ = open_index(conf, prms_);
+    if (unc_mapper_create(ix_, &prms_, nullptr, &mapper_) != UNC_OK) die_last_error();
     // -t 1 (the reference's default): ONE Mapper maps the reads in input order, and what a read leaves set in sources_added_ is seen
     // by the next (mapper.cpp:88,612-623).  The C ABI reproduces that order exactly (UNC_ORDER_T1: the few reads whose predecessor
     // left flags set are mapped a second time); -t N > 1, where the reference's own outcome depends on which thread gets which
     // read, maps every read independently.
-    if (conf.threads <= 1 && unc_mapper_set_read_order(mapper_, UNC_ORDER_T1) != UNC_OK) {
-        std::cerr << "Error: " << unc_last_error() << "\n";
-        abort();
-    }
+    if (conf.threads <= 1 && unc_mapper_set_read_order(mapper_, UNC_ORDER_T1) != UNC_OK) die_last_error();
     // a batch = four times as many reads as the mapper keeps in flight: every unc_map_batch call ends with the few reads that
     // run to max_events on a nearly idle chip, and at one load of the slots that tail is a third of the call (round 3: 11.5 k
     // reads/s end to end against 17 k in HBM); the FIRST batch is one load of the slots, so that the first PAF lines do not
@@ -325,8 +330,7 @@ MapPool::MapPool(const Conf &conf) : conf_(conf), reader_(conf) {
     first_batch_reads_ = geo[1] ? geo[1] : 4096;
     batch_reads_ = conf.batch_reads ? conf.batch_reads : 4 * first_batch_reads_;
     if (first_batch_reads_ > batch_reads_) first_batch_reads_ = batch_reads_;
-    free_.push_back(0);
-    free_.push_back(1);
+    free_ = {0, 1};
 }
 
 MapPool::~MapPool() {
@@ -349,7 +353,7 @@ void MapPool::release(Batch &b) {
 
 // Room for `need` samples.  Page-locked memory while the driver hands it out; pageable memory (the C ABI takes either, the
 // copy to the device is then staged by the runtime) with one warning when it does not -- a full pinned pool is no reason to
-// end a run.  The old buffer is released before the new one is the only copy only in the sense that both exist during memcpy.
+// end a run.
 bool MapPool::grow(Batch &b, uint64_t need) {
     if (need <= b.cap) return true;
     uint64_t cap = b.cap ? 2 * b.cap : (32ull << 20);            // at least double, at least what is asked for (in 32 M-sample steps)
@@ -384,81 +388,93 @@ bool MapPool::grow(Batch &b, uint64_t need) {
 // reference's worker threads (map_pool.cpp:31-42) the two threads live until stop(): files may be added at any time.
 void MapPool::loader_main() {
     for (;;) {
-        int bi;
-        {
-            std::unique_lock<std::mutex> lk(mtx_);
-            cv_.wait(lk, [&] { return stopped_ || !free_.empty(); });
-            if (stopped_) break;
-            bi = free_.front();
-            free_.pop_front();
-            while (!new_files_.empty()) { reader_.add_fast5(new_files_.front()); new_files_.pop_front(); }
-        }
+        const int bi = claim_buffer();
+        if (bi < 0) break;
         Batch &b = bufs_[bi];
-        b.used = 0; b.off.assign(1, 0); b.cal.clear(); b.meta.clear();
+        b.reset();
         const uint32_t target = batches_staged_ == 0 ? first_batch_reads_ : batch_reads_;
         std::vector<Paf> unstaged;      // reads no staging buffer could be had for: reported unmapped, like every read the reference is given
-        while (b.meta.size() < target) {
-            // the GPU has nothing to do and one load of its slots is staged: hand that over now.  Batches thus grow from one
-            // load towards four as long as reading keeps ahead of mapping, and the GPU never waits for a full batch.
-            if (b.meta.size() >= first_batch_reads_ && (b.meta.size() & 255u) == 0) {
-                std::lock_guard<std::mutex> lk(mtx_);
-                if (!mapper_busy_ && staged_.empty()) break;
-            }
-            if (!carry_valid_ && reader_.buffered() == 0 && (reader_.empty() || reader_.fill_buffer() == 0)) break;
-            // (a batch is also closed by bytes: whole reads with -c 1000000 are tens of MB each)
-            const uint64_t next_size = carry_valid_ ? carry_.signal.size() : reader_.front_size();
-            if (!b.meta.empty() && (b.used + next_size + 1) * 2 > kBatchBytes) break;
-            RawRead r;
-            if (carry_valid_) { r = std::move(carry_); carry_valid_ = false; }      // the read the last batch had no room for
-            else r = reader_.pop_read();
-            // a buffer that must grow goes straight to what a FULL batch will need, also while the short first batch is being
-            // read: page-locking is slow (seconds for the 4-5 GB of a batch) and holds up the HIP calls of the mapping thread
-            // meanwhile, so both buffers reach their final size during the first two batches and never grow again
-            uint64_t need = b.used + r.signal.size() + 1;
-            if (need > b.cap && b.meta.size() >= 16) {
-                // (... but never for more reads than are left: a small input must not page-lock gigabytes it will never fill -- round-3 advice)
-                const uint32_t left = reader_.reads_left_if_known();
-                const uint64_t full = left == 0xFFFFFFFFu ? batch_reads_ : std::min<uint64_t>(batch_reads_, b.meta.size() + 1u + left);
-                const uint64_t est = (uint64_t)((double)b.used / (double)b.meta.size() * (double)full * 1.1);
-                if (est > need) need = est < kBatchBytes / 2 ? est : kBatchBytes / 2;
-                if (need < b.used + r.signal.size() + 1) need = b.used + r.signal.size() + 1;
-            }
-            if (!grow(b, need) && !grow(b, b.used + r.signal.size() + 1)) {
-                // no memory for the buffer to grow.  A batch that holds reads is handed over as it is and this read opens the next
-                // one (whose buffer is then empty); a read that does not even fit an empty buffer gets its unmapped PAF line
-                // (every read gets a line, map_pool.cpp:130-158) and the loader goes on with the next read
-                if (!b.meta.empty()) {
-                    carry_ = std::move(r); carry_valid_ = true;
-                    break;
-                }
-                std::cerr << "Error: out of host memory for a staging buffer of " << ((r.signal.size() + 1) * 2 >> 20) << " MB; read " << r.id
-                          << " is reported unmapped\n";
-                Paf pf(r.id, (uint16_t)(r.channel_idx + 1), r.start_sample);
-                pf.set_read_len((uint64_t)((float)r.signal.size() * bp_per_samp_));     // (an unmapped read's length: read_buffer.cpp:133-155)
-                unstaged.push_back(std::move(pf));
-                continue;
-            }
-            if (!r.signal.empty()) memcpy(b.raw + b.used, r.signal.data(), r.signal.size() * 2);
-            b.used += r.signal.size();
-            b.off.push_back(b.used);
-            b.cal.push_back(r.calib);
-            b.meta.push_back(ReadMeta{r.id, r.channel_idx, r.start_sample});
+        RawRead r;
+        while (b.meta.size() < target && !hand_over_early(b) && fetch_read(b, r)) {
+            if (stage_read(b, r)) continue;
+            // no memory for it: a batch that holds reads is handed over as it is and this read opens the next one; a read that does
+            // not even fit an empty buffer gets its unmapped PAF line (every read gets a line, map_pool.cpp:130-158)
+            if (!b.meta.empty()) { carry_ = std::move(r); carry_valid_ = true; break; }
+            std::cerr << "Error: out of host memory for a staging buffer of " << ((r.signal.size() + 1) * 2 >> 20) << " MB; read " << r.id
+                      << " is reported unmapped\n";
+            unstaged.push_back(unmapped_paf(prms_, r.id, r.channel_idx, r.start_sample, r.signal.size()));
         }
-        std::unique_lock<std::mutex> lk(mtx_);
-        for (Paf &pf : unstaged) done_.push_back(std::move(pf));
-        if (b.meta.empty()) {          // the files ran dry: idle until another one is added
-            free_.push_front(bi);
-            loader_idle_ = true;
-            cv_.notify_all();
-            cv_.wait(lk, [&] { return stopped_ || !new_files_.empty(); });
-            loader_idle_ = false;
-            if (stopped_) break;
-            continue;
-        }
-        ++batches_staged_;
-        staged_.push_back(bi);
-        cv_.notify_all();
+        if (!publish(bi, unstaged)) break;
     }
+}
+
+int MapPool::claim_buffer() {
+    std::unique_lock<std::mutex> lk(mtx_);
+    cv_.wait(lk, [&] { return stopped_ || !free_.empty(); });
+    if (stopped_) return -1;
+    const int bi = free_.front();
+    free_.pop_front();
+    while (!new_files_.empty()) { reader_.add_fast5(new_files_.front()); new_files_.pop_front(); }
+    return bi;
+}
+// the GPU has nothing to do and one load of its slots is staged: batches grow from one load towards four while reading keeps ahead
+bool MapPool::hand_over_early(const Batch &b) {
+    if (b.meta.size() < first_batch_reads_ || (b.meta.size() & 255u) != 0) return false;
+    std::lock_guard<std::mutex> lk(mtx_);
+    return !mapper_busy_ && staged_.empty();
+}
+bool MapPool::fetch_read(const Batch &b, RawRead &r) {
+    if (!carry_valid_ && reader_.buffered() == 0 && (reader_.empty() || reader_.fill_buffer() == 0)) return false;
+    // (a batch is also closed by bytes: whole reads with -c 1000000 are tens of MB each)
+    const uint64_t next_size = carry_valid_ ? carry_.signal.size() : reader_.front_size();
+    if (!b.meta.empty() && (b.used + next_size + 1) * 2 > kBatchBytes) return false;
+    if (carry_valid_) { r = std::move(carry_); carry_valid_ = false; }      // the read the last batch had no room for
+    else r = reader_.pop_read();
+    return true;
+}
+
+// A buffer that must grow goes straight to what a FULL batch will need: page-locking is slow (seconds for the 4-5 GB of a batch)
+// and holds up the mapper thread's HIP calls, so both buffers reach their final size during the first two batches.  But never
+// for more reads than are left (UINT32_MAX = unknown): a small input must not page-lock gigabytes it will never fill
+uint64_t MapPool::room_wanted(uint64_t used, uint64_t n_staged, uint64_t read_size, uint32_t reads_left, uint32_t batch_reads) {
+    const uint64_t least = used + read_size + 1;
+    if (n_staged < 16) return least;
+    const uint64_t full = reads_left == 0xFFFFFFFFu ? batch_reads : std::min<uint64_t>(batch_reads, n_staged + 1u + reads_left);
+    const uint64_t est = (uint64_t)((double)used / (double)n_staged * (double)full * 1.1);
+    return std::max(least, std::min(est, kBatchBytes / 2));
+}
+
+// Invariant: a read is staged only into a buffer with room for its samples and one more, so a batch that holds reads -- the
+// only kind the mapper thread is given -- has cap >= 1 and raw != nullptr even when every read of it is empty (used == 0).
+bool MapPool::stage_read(Batch &b, const RawRead &r) {
+    const uint64_t least = b.used + r.signal.size() + 1;
+    if (least > b.cap && !grow(b, room_wanted(b.used, b.meta.size(), r.signal.size(), reader_.reads_left_if_known(), batch_reads_)) && !grow(b, least))
+        return false;
+    b.append(r);
+    return true;
+}
+void MapPool::Batch::append(const RawRead &r) {
+    if (!r.signal.empty()) memcpy(raw + used, r.signal.data(), r.signal.size() * 2);
+    used += r.signal.size();
+    off.push_back(used);
+    cal.push_back(r.calib);
+    meta.push_back(ReadMeta{r.id, r.channel_idx, r.start_sample});
+}
+
+bool MapPool::publish(int bi, std::vector<Paf> &unstaged) {
+    std::unique_lock<std::mutex> lk(mtx_);
+    for (Paf &pf : unstaged) done_.push_back(std::move(pf));
+    if (!bufs_[bi].meta.empty()) {
+        ++batches_staged_; staged_.push_back(bi);
+        cv_.notify_all();
+        return true;
+    }
+    free_.push_front(bi);          // the files ran dry: idle until another one is added
+    loader_idle_ = true;
+    cv_.notify_all();
+    cv_.wait(lk, [&] { return stopped_ || !new_files_.empty(); });
+    loader_idle_ = false;
+    return !stopped_;
 }
 
 void MapPool::mapper_main() {
@@ -475,23 +491,16 @@ void MapPool::mapper_main() {
         Batch &b = bufs_[bi];
         const size_t n = b.meta.size();
         std::vector<unc_hit_t> hits(n);
-        if (b.used == 0) { grow(b, 1); b.raw[0] = 0; }
+        if (b.used == 0) b.raw[0] = 0;       // (room for it: the invariant at stage_read)
         const int rc = unc_map_batch(mapper_, (uint32_t)n, b.raw, b.off.data(), b.cal.data(), 0, nullptr, hits.data());
-        if (rc != UNC_OK && rc != UNC_ERR_OVERFLOW) { std::cerr << "Error: " << unc_last_error() << "\n"; abort(); }
+        if (rc != UNC_OK && rc != UNC_ERR_OVERFLOW) die_last_error();
         std::vector<Paf> out;
         out.reserve(n);
         for (size_t i = 0; i < n; ++i) {
-            const unc_hit_t &h = hits[i];
-            Paf p(b.meta[i].id, (uint16_t)(b.meta[i].channel_idx + 1), b.meta[i].start_sample);
-            p.set_read_len(h.rd_len);
-            if (h.mapped) p.set_mapped(h.rd_st, h.rd_en, unc_index_seq_name(ix_, h.rid), h.rf_st, h.rf_en, h.rf_len, h.fwd != 0, (uint16_t)h.matches);
+            out.push_back(paf_from_hit(ix_, b.meta[i].id, b.meta[i].channel_idx, b.meta[i].start_sample, hits[i]));
             // the read's residence on the device, first event taken up -> result written (the reference times
             // Mapper::map_read on the read's own thread, mapper.cpp:197; here reads share wavefronts in time slices)
-            p.set_float(Paf::MAP_TIME, h.map_ms);
-            if (h.status)   // the reference's SeedTracker is unbounded: say so instead of printing a silent unmapped line
-                std::cerr << "Warning: read " << b.meta[i].id << ": device scratch overflow (status " << h.status
-                          << ") even after re-mapping with more room; reported unmapped\n";
-            out.push_back(std::move(p));
+            out.back().set_float(Paf::MAP_TIME, hits[i].map_ms);
         }
         std::lock_guard<std::mutex> lk(mtx_);
         for (Paf &p : out) done_.push_back(std::move(p));

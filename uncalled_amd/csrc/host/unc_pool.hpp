@@ -38,6 +38,10 @@ struct Conf {
 // model_path (Mapper::load_static, mapper.cpp:113-115): loads the model file and sets it on an index nothing was made from yet;
 // an empty path leaves the r9.4 template.  Returns the C ABI's status
 int index_set_model_path(unc_index_t *ix, const std::string &model_path);
+// What both pools do first: Conf -> unc_params_t, index load, model_path.  Like Mapper::load_static on a bad index
+// (mapper.cpp:118-127), a failure prints the C ABI's message and aborts (die_last_error)
+unc_index_t *open_index(const Conf &conf, unc_params_t &prms);
+[[noreturn]] void die_last_error();
 
 class Paf {
 public:
@@ -68,6 +72,12 @@ private:
     std::vector<std::pair<Tag, std::string>> str_tags_;
 };
 
+// A finished read's record from its hit: read length, mapped columns, and a warning where hit.status tells a scratch overflow (the
+// reference's SeedTracker is unbounded: no silent unmapped line); the caller sets MAP_TIME and `ended`.  unmapped_paf: the record of
+// a read without a hit, its length in bases worked out from its samples as Paf::set_read_len does (read_buffer.cpp:133-155,264-267)
+Paf paf_from_hit(const unc_index_t *ix, const std::string &id, uint16_t channel_idx, uint64_t start_sample, const unc_hit_t &hit);
+Paf unmapped_paf(const unc_params_t &prms, const std::string &id, uint16_t channel_idx, uint64_t start_sample, uint64_t raw_len);
+
 struct RawRead {   // ReadBuffer of the offline path, samples kept as stored
     std::string id;
     uint16_t channel_idx = 0;
@@ -76,10 +86,15 @@ struct RawRead {   // ReadBuffer of the offline path, samples kept as stored
     unc_calib_t calib{1.f, 0.f, 1.f};
     std::vector<int16_t> signal;
 };
+// the samples in pA as ReadBuffer calibrates them (read_buffer.cpp:239-241, fast5.hpp raw_samples_to_float): through uint16_t, and
+// in three float steps whose order the tests hold bit for bit
+std::vector<float> calibrated(const RawRead &r);
 
 class Fast5Reader {
 public:
     Fast5Reader(const Conf &c);
+    ~Fast5Reader() { close_file(); }      // (the file it has open)
+    Fast5Reader(const Fast5Reader &) = delete;
     void add_fast5(const std::string &path) { fast5_list_.push_back(path); }
     bool add_read(const std::string &read_id);
     bool load_fast5_list(const std::string &fname);
@@ -95,6 +110,7 @@ public:
 
 private:
     bool open_next();
+    void close_file();
     bool read_one(const std::string &raw_path, const std::string &ch_path, RawRead &out);
     uint32_t max_reads_, max_buffer_, max_chunks_, chunk_len_, total_buffered_ = 0;
     std::deque<std::string> fast5_list_, read_paths_;
@@ -112,6 +128,11 @@ bool write_fast5(const std::string &path, const std::vector<RawRead> &reads, boo
 // a loader thread reads fast5 files into page-locked staging buffers (two of them: batch k+1 is read and flattened while
 // batch k is on the GPU), a mapper thread feeds them to unc_map_batch, and update() returns whatever has finished.  Both
 // threads live until stop(): add_fast5 works at any time, running() turns true again when it does.
+//
+// The loader (loader_main) claims a free buffer, taking over the files added meanwhile.  Then, read by read: it hands a short
+// batch over early when the GPU has nothing to do; fetches the next read, from the carry or from the reader; works out the room
+// wanted; and stages the read -- or, with no memory for it, carries it over into the next batch or reports it unstaged.  Then
+// it publishes the batch, or goes idle until a file is added.
 class MapPool {
 public:
     explicit MapPool(const Conf &conf);
@@ -132,30 +153,42 @@ private:
         std::vector<uint64_t> off;
         std::vector<unc_calib_t> cal;
         std::vector<ReadMeta> meta;
+        void reset() { used = 0; off.assign(1, 0); cal.clear(); meta.clear(); }
+        void append(const RawRead &r);      // needs used + r.signal.size() <= cap
     };
     void loader_main();
-    void mapper_main();
+    int claim_buffer();                                  // -1: stopped
+    bool hand_over_early(const Batch &b);
+    bool fetch_read(const Batch &b, RawRead &r);         // false: the files ran dry, or the batch is full by bytes
+    static uint64_t room_wanted(uint64_t used, uint64_t n_staged, uint64_t read_size, uint32_t reads_left, uint32_t batch_reads);
+    bool stage_read(Batch &b, const RawRead &r);         // false: no memory for it
+    bool publish(int bi, std::vector<Paf> &unstaged);    // false: stopped
     bool grow(Batch &b, uint64_t need);
     void release(Batch &b);
+    void mapper_main();
     static constexpr uint64_t kBatchBytes = 8ull << 30;     // staged samples of one batch (two batches exist)
-    Conf conf_;
-    Fast5Reader reader_;
+
+    // set by the constructor, read-only afterwards (mapper_ is used by the mapper thread alone)
+    unc_params_t prms_;
     unc_index_t *ix_ = nullptr;
     unc_mapper_t *mapper_ = nullptr;
     uint32_t batch_reads_ = 0, first_batch_reads_ = 0;
+    // loader thread only (reader_: running() asks it before the first update() has started the threads)
+    Fast5Reader reader_;
+    RawRead carry_;                  // the read a closed batch had no room for; it opens the next batch
+    bool carry_valid_ = false;
     uint64_t batches_staged_ = 0;
     bool warned_pageable_ = false;
-    RawRead carry_;                  // loader thread only: the read a closed batch had no room for; it opens the next batch
-    bool carry_valid_ = false;
-    float bp_per_samp_ = 0.0f;
+    // a buffer belongs to the thread that took its index off a queue: the loader (off free_) or the mapper (off staged_)
     Batch bufs_[2];
+    // under mtx_
     std::deque<int> free_, staged_;       // indices into bufs_
     std::deque<std::string> new_files_;   // add_fast5 -> loader thread
     std::vector<Paf> done_;
+    bool started_ = false, stopped_ = false, loader_idle_ = false, mapper_busy_ = false;
     std::mutex mtx_;
     std::condition_variable cv_;
     std::thread loader_, mapper_thread_;
-    bool started_ = false, stopped_ = false, loader_idle_ = false, mapper_busy_ = false;
 };
 
 }  // namespace unc_host

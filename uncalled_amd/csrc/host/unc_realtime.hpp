@@ -44,6 +44,35 @@ private:
 
 using MapResult = std::tuple<uint16_t, uint32_t, Paf>;   // channel (1-based), read number, record
 
+// A channel of RealtimePool is in one of four states; every call picks a cell of this table and runs one of three transitions:
+//   IDLE (I)              no read (Mapper::State::INACTIVE)
+//   FIRST_PENDING (FP)    a new read's first chunk waits for update(); nothing of the read is mapped yet
+//   MAPPING (M)           the read's last chunk is fully mapped, the read undecided (Mapper::chunk_mapped, mapper.cpp:377-379)
+//   MAPPING_PENDING (MP)  ... and its next chunk waits for update()
+//   start      start_read: the chunk opens a read, -> FP, returns true (Mapper::new_read(Chunk&), mapper.cpp:210-217)
+//   take       take_chunk: the chunk is the read's next, M -> MP, returns true (Mapper::add_chunk, mapper.cpp:281-305)
+//   drop+/-    drop_read: -> I.  +: the read is reported, unmapped + ended, by the next update() (request_reset -> set_failed +
+//              set_ended, mapper.cpp:261-263,384-390); -: it vanishes, nothing of it was ever mapped
+//   no         returns false, nothing changes.  "same" / "other": the call's read number against the channel's; rp = realtime_pool.cpp
+//   call                       I       FP            M            MP           mirrors
+//   add_chunk, same            start   no            take         no           rp:93-100; mapper.cpp:284-287 (chunk not processed yet)
+//   add_chunk, other           start   drop-, start  drop+, start drop+, start rp:79-82 (prev_unfinished); FP: rp:61-70 (buffer_chunk)
+//   try_add_chunk, same        start   no            take         no           rp:126-138
+//   try_add_chunk, other       start   no            no           no           rp:141
+//   try_add_chunk, empty       no      no            drop+, false no           rp:116-122 (give up once the last chunk is mapped)
+//   oversized chunk, same      no      drop+, false  drop+, false drop+, false OWN
+//   end_read, same             -       drop-         drop+        drop+        OWN (rp:267-270 is commented out)
+//   oversized / end_read, other: nothing changes (the oversized chunk is refused and counted all the same)      OWN
+//   update(), round accepted   -       M, or result  -            M, or result rp:145-169; all of the chunk is mapped, map_pool_ord.cpp:61-112
+//   update(), round refused    -       drop+         -            drop+        OWN: reported by this very update()
+//   stop_all()                 I       I             I            I            reports nothing any more; both adds then return false
+//
+// "result": the read's record (mapped, or unmapped [+ ended]) and -> I.  OWN rows are this project's, not the reference's:
+// - a chunk longer than chunk_time * sample_rate fits no channel's staging on the device: it is refused, counted
+//   (refused_chunks()), and ends its read, so that the channel does not wait for a chunk that will never be accepted;
+// - a round the device side refuses as a whole ends the reads it carried and leaves the pool usable;
+// - a channel >= num_channels is refused (the reference indexes unchecked).  add_chunk tests that AFTER oversized, try_add_chunk
+//   BEFORE it: an oversized chunk on such a channel is counted by add_chunk only.  Kept as it is for compatibility.
 class RealtimePool {
 public:
     enum Mode { DEPLETE, ENRICH };
@@ -62,32 +91,32 @@ public:
     float last_round_ms() const { return last_ms_; }
     uint64_t refused_chunks() const { return refused_chunks_; }     // chunks longer than chunk_time * sample_rate, never staged
 
+private:
+    enum State { IDLE, FIRST_PENDING, MAPPING, MAPPING_PENDING };
     struct Chan {
-        bool active = false;         // a read is being mapped (Mapper state MAPPING; its last chunk is fully mapped)
-        bool has_pending = false;    // a chunk waits for the next update()
-        bool pending_first = false;  // ... and it starts a read (Mapper::new_read(Chunk&))
-        uint32_t number = 0, chunks = 0;
+        State state = IDLE;
+        uint32_t number = 0;
         uint64_t start = 0, raw_len = 0;
         std::string id;
         Chunk pending;
-        // request_reset: reads reported unmapped + ended by the next update().  A list, not one record: between two updates a channel
-        // can give up its mapping read (a new read takes it over) AND that new read's first chunk can be refused as oversized before it
-        // was ever mapped -- the reference reports every reset read (round-4 advice: one record lost the first of the two)
+        // reads to be reported unmapped + ended by the next update().  A list, not one record: between two updates a channel can give
+        // up its mapping read (a new read takes it over) AND that new read can be ended by an oversized chunk before it was ever mapped
         struct GivenUp { std::string id; uint32_t number; uint64_t start, raw_len; };
         std::vector<GivenUp> given_up;
+        bool waiting() const { return state == FIRST_PENDING || state == MAPPING_PENDING; }
     };
-private:
-    void start_read(Chan &c, Chunk &chunk);
-    Paf unmapped_paf(const std::string &id, uint16_t ch_idx, uint64_t start, uint64_t raw_len) const;
-    Conf conf_;
+    // the three transitions every row above is made of
+    void start_read(Chan &c, Chunk &chunk);      // any -> FIRST_PENDING
+    void take_chunk(Chan &c, Chunk &chunk);      // IDLE -> FIRST_PENDING, MAPPING -> MAPPING_PENDING
+    void drop_read(Chan &c, bool reported);      // -> IDLE
+    bool oversized(const Chunk &chunk);
+    void report_given_up(std::vector<MapResult> &out);
     unc_params_t prms_;
     unc_index_t *ix_ = nullptr;
     unc_rt_t *rt_ = nullptr;
     std::vector<Chan> chans_;
-    bool stopped_ = false;
-    bool warned_oversized_ = false;
+    bool stopped_ = false, warned_oversized_ = false;
     uint64_t refused_chunks_ = 0;
-    bool oversized(const Chunk &chunk);
     float last_ms_ = 0;
 };
 
